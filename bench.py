@@ -15,6 +15,13 @@ which are generated ON DEVICE, packed 2-bit, before the timed region starts.
             is the strong-scaling speed-up BASELINE.json's target is quoted in.
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
 python -m torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from env).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print
+the result line.  --full adds everything else this file measures or checks: the
+end-to-end leg from files, per-kernel times and the roofline (the timed steps then run
+with the library's event profiling on), the CPU baseline and the index's verification.
+--dump-outputs DIR writes what the last timed step built (index_summary.npy and a fixed,
+seeded sample of the index's entries: dump_outputs()) so that two builds can be compared.
 """
 import argparse
 import json
@@ -60,6 +67,9 @@ def main():
     ap.add_argument("--get", action="store_true", help="also time the get path afterwards (N=1): per-read sums of counts over the same reads; reported under \"get\"")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl == RCCL)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: all ranks use cuda:0")
+    ap.add_argument("--full", action="store_true", help="also run the end-to-end leg, the per-kernel profile and roofline, the CPU baseline and the "
+                                                        "index's verification; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step built to DIR/*.npy (float64)")
     args = ap.parse_args()
 
     import numpy as np
@@ -120,7 +130,7 @@ def main():
     # its child processes map their arenas from memory nobody has used -- run after the timed steps, next to (or right behind)
     # this process' own 146 GB index, their first arena mappings alone took 0.4-1.4 s.
     e2e_leg = None
-    if args.e2e_reads and N == 1:
+    if args.full and args.e2e_reads and N == 1:
         try:
             e2e_leg = end_to_end(k, m, b, L, min(args.e2e_reads, n_reads), d_packed)
         except Exception as e:  # noqa: BLE001  (the leg must never take the bench line with it)
@@ -160,7 +170,7 @@ def main():
     run_steps(args.warmup, False)
     barrier()
     t0 = time.perf_counter()
-    entries, prof = run_steps(args.steps, True)
+    entries, prof = run_steps(args.steps, args.full)  # (the per-kernel events feed the roofline: --full only)
     barrier()
     dt = time.perf_counter() - t0
 
@@ -172,19 +182,29 @@ def main():
     dt = float(t.item())
     entries_all = float(e.item())
 
-    # after the timed region: a size-independent parity property of what was just built -- every k-mer
-    # instance counted exactly once (sum of counts == reads x (L-k+1); no count wraps at this coverage) and
-    # an order-independent digest of the index (shard digests add up; equal digests <=> equal multisets)
-    ent, sumc, dig = ix.checksum()
-    limbs = [(dig >> (22 * i)) & ((1 << 22) - 1) for i in range(3)]  # int64 all-reduce cannot overflow on 22-bit limbs
-    chk = torch.tensor([ent, sumc] + limbs, dtype=torch.int64, device=dev)
-    if N > 1:
-        dist.all_reduce(chk, op=dist.ReduceOp.SUM)
-    chk = [int(v) for v in chk.cpu().tolist()]
-    whole = sc.stats()  # Brisk::stats of the sharded index: sums (and one max) over the owners
-    verify = {"entries": chk[0], "nb_kmers": whole["nb_kmers"], "nb_buckets": whole["nb_buckets"], "sum_counts": chk[1], "sum_counts_expected": total_reads * max(L - k + 1, 0),
-              "every_kmer_counted_once": chk[1] == total_reads * max(L - k + 1, 0),
-              "digest_mod_2_64": (chk[2] + (chk[3] << 22) + (chk[4] << 44)) % (1 << 64)}
+    def index_summary():
+        """COLLECTIVE: entries, sum of counts and the order-independent digest of the whole index (shard digests add up;
+        equal digests <=> equal multisets), with Brisk::stats of the sharded index (sums, and one max, over the owners)"""
+        ent, sumc, dig = ix.checksum()
+        limbs = [(dig >> (22 * i)) & ((1 << 22) - 1) for i in range(3)]  # int64 all-reduce cannot overflow on 22-bit limbs
+        chk = torch.tensor([ent, sumc] + limbs, dtype=torch.int64, device=dev)
+        if N > 1:
+            dist.all_reduce(chk, op=dist.ReduceOp.SUM)
+        chk = [int(v) for v in chk.cpu().tolist()]
+        whole = sc.stats()
+        return {"entries": chk[0], "nb_kmers": whole["nb_kmers"], "nb_buckets": whole["nb_buckets"], "sum_counts": chk[1],
+                "digest_mod_2_64": (chk[2] + (chk[3] << 22) + (chk[4] << 44)) % (1 << 64)}
+
+    verify = None
+    if args.full:
+        # after the timed region: a size-independent parity property of what was just built -- every k-mer
+        # instance counted exactly once (sum of counts == reads x (L-k+1); no count wraps at this coverage)
+        s = index_summary()
+        verify = {"entries": s["entries"], "nb_kmers": s["nb_kmers"], "nb_buckets": s["nb_buckets"], "sum_counts": s["sum_counts"],
+                  "sum_counts_expected": total_reads * max(L - k + 1, 0), "every_kmer_counted_once": s["sum_counts"] == total_reads * max(L - k + 1, 0),
+                  "digest_mod_2_64": s["digest_mod_2_64"]}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ix, index_summary(), rank)
 
     get_leg = None
     if args.get and N == 1:
@@ -224,7 +244,7 @@ def main():
                         "avg_launch_ms": round(avg_ms, 3), "alg_bytes_per_read": b_alg(k, m, b, L, n_skm),
                         "kernels_ms_per_step": {n: round(v["ms"] / args.steps, 3) for n, v in prof.items() if v["launches"]}}
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(k, m, b, L, args.coverage, args.cpu_sample_reads)
         line = {
             "metric": "distinct k-mers indexed/sec (k=%d,m=%d)" % (k, m), "value": round(value, 1), "unit": "k-mers/s",
@@ -236,16 +256,70 @@ def main():
                        "reads_per_gpu": n_reads, "total_reads": total_reads, "part_bits": ix.layout["part_bits"],
                        "ownership": ({"cut_points": "histogram-balanced" if cuts else "equal partition ranges", **getattr(sc, "owner_load", {})} if N > 1 else None), "genome_len": genome_len, "entries_per_step": entries_all / args.steps,
                        "parallelism": "bucket-range shard x%d + all-to-all" % N if N > 1 else "single GPU"},
-            "roofline": roofline, "cpu_baseline": cpu,
         }
-        line["verify"] = verify
+        if args.full:
+            line["roofline"] = roofline
+            line["cpu_baseline"] = cpu
+            line["verify"] = verify
         if get_leg:
             line["get"] = get_leg
-        if args.e2e_reads and N == 1:
+        if args.full and args.e2e_reads and N == 1:
             line["end_to_end"] = e2e_leg
         print(json.dumps(line))
     if N > 1:
         dist.destroy_process_group()
+
+
+DUMP_SEED, DUMP_STARTS, DUMP_CAP, DUMP_MAX_ENTRIES = 20261016, 64, 4096, 1 << 20
+
+
+def dump_outputs(out_dir, ix, summary, rank):
+    """--dump-outputs: what a caller of the counting path receives from the index the last timed step built, as float64
+    .npy files (every value is below 2^53, so exact):
+      index_summary.npy          [entries, nb_kmers, nb_buckets, sum_counts, digest bits 0-31, digest bits 32-63] of the
+                                 whole index (the order-independent digest of brisk_hip_checksum, include/brisk_hip.h);
+      entries_kmer.npy           (n, 4): the sampled entries' k-mers, unhashed as Brisk::next yields them, in 32-bit
+                                 words (lo bits 0-31, lo bits 32-63, hi bits 0-31, hi bits 32-63);
+      entries_minimizer_idx.npy  (n,): their minimizer_idx;
+      entries_count.npy          (n,): their counts.
+    The sample is fixed and seeded: the whole partitions brisk_hip_enumerate returns from DUMP_STARTS partitions drawn
+    with DUMP_SEED, about DUMP_CAP entries from each (~13 MB in all), sorted by k-mer and minimizer_idx because the
+    order inside a partition follows the device's atomics.  N > 1: the summary is of the whole sharded index, the
+    sample of rank 0's shard; rank 0 writes."""
+    if rank != 0:
+        return
+    import ctypes as C
+    import numpy as np
+    from brisk_amd.hipapi import ECAPACITY
+    n_parts = 1 << ix.layout["part_bits"]
+    starts = np.sort(np.random.default_rng(DUMP_SEED).choice(n_parts, size=min(DUMP_STARTS, n_parts), replace=False))
+    got = {"lo": [], "hi": [], "idx": [], "cnt": []}
+    end = 0  # (a start inside what the previous call returned continues after it: no entry twice)
+    for p in starts:
+        cur, n, cap = C.c_uint64(max(int(p), end)), C.c_uint64(0), DUMP_CAP
+        while True:
+            lo, hi = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+            idx, cnt = np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+            rc = ix.L.brisk_hip_enumerate(ix.h, C.byref(cur), lo, hi, idx, cnt, cap, C.byref(n))
+            if rc != ECAPACITY:
+                break
+            cap *= 4  # one partition holds more than cap entries
+        ix._chk(rc)
+        end = cur.value
+        for key, a in (("lo", lo), ("hi", hi), ("idx", idx), ("cnt", cnt)):
+            got[key].append(a[:n.value])
+    lo, hi, idx, cnt = (np.concatenate(got[key]) for key in ("lo", "hi", "idx", "cnt"))
+    order = np.lexsort((idx, lo, hi))[:DUMP_MAX_ENTRIES]
+    lo, hi, idx, cnt = lo[order], hi[order], idx[order], cnt[order]
+    w32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    d = summary["digest_mod_2_64"]
+    out = {"index_summary": np.array([summary["entries"], summary["nb_kmers"], summary["nb_buckets"], summary["sum_counts"], d & 0xFFFFFFFF, d >> 32], np.float64),
+           "entries_kmer": np.stack([lo & w32, lo >> s32, hi & w32, hi >> s32], axis=1).astype(np.float64),
+           "entries_minimizer_idx": idx.astype(np.float64),
+           "entries_count": cnt.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def pmc_traffic(kernel, k, m, b, n_reads):

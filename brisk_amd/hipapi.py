@@ -47,9 +47,8 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_apps(verbose: bool = False) -> dict:
-    """C++ host side: this repo's brisk_count over the facade headers, and -- where the reference
-    tree exists -- the reference's own apps/counter.cpp compiled UNCHANGED against
-    brisk_amd/include (its CLI11/zstr third-party headers are taken from the reference tree)."""
+    """C++ host side: this repo's brisk_count and brisk_shard over the facade headers.  (The reference's own
+    apps/counter.cpp, compiled UNCHANGED against brisk_amd/include, is test infrastructure: oracle/Makefile.)"""
     apps = os.path.join(HERE, "apps")
     inc = ["-I" + os.path.join(HERE, "include"), "-I" + os.path.join(ROOT, "include")]
     link = ["-L" + HERE, "-lbrisk_hip", "-Wl,-rpath,$ORIGIN/.."]
@@ -67,14 +66,6 @@ def build_apps(verbose: bool = False) -> dict:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
     out["brisk_shard"] = os.path.join(apps, "brisk_shard")
-    ref_counter = "/root/reference/apps/counter.cpp"
-    if os.path.exists(ref_counter):
-        cmd = ["g++", "-std=gnu++17", "-O2", "-w", "-include", "cstdint", "-fopenmp"] + inc + ["-I/root/reference/apps", ref_counter] + link + \
-              ["-lz", "-o", os.path.join(apps, "counter_ref")]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        out["counter_ref"] = os.path.join(apps, "counter_ref")
     return out
 
 

@@ -9,6 +9,8 @@ Two libraries, same calling conventions:
   * ``Ref``     -- oracle/_ref/libbrisk_ref.so, the REAL reference sources
                    compiled where they lie (only buildable where /root/reference
                    exists; the built .so travels to the GPU box, sources never do).
+``COUNTER_REF`` (oracle/_ref/counter_ref) is the reference's apps/counter.cpp
+compiled unchanged against the facade headers, built and travelling the same way.
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "libbrisk_oracle.so")
 REF_SO = os.path.join(HERE, "_ref", "libbrisk_ref.so")
+COUNTER_REF = os.path.join(HERE, "_ref", "counter_ref")
 REFERENCE_ROOT = "/root/reference"
 
 u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
@@ -30,11 +33,12 @@ u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 
 
-def build(ref: bool = True) -> None:
-    """Compile the restatement and, where /root/reference exists, oracle/_ref."""
+def build(ref: bool = True, counter: bool = False) -> None:
+    """Compile the restatement and, where the reference tree exists, oracle/_ref; with `counter`, also the
+    reference's apps/counter.cpp over the facade headers (COUNTER_REF; needs brisk_amd's library built)."""
     subprocess.check_call(["make", "-s", "-C", HERE, "oracle"])
     if ref and os.path.isdir(REFERENCE_ROOT):
-        subprocess.check_call(["make", "-s", "-C", HERE, "ref"])
+        subprocess.check_call(["make", "-s", "-C", HERE, "ref"] + (["counter"] if counter else []))
 
 
 def have_ref() -> bool:

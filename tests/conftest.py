@@ -29,13 +29,3 @@ def O():
     import oracle
     oracle.build(ref=False)
     return oracle.Oracle()
-
-
-@pytest.fixture(scope="session")
-def R():
-    """The real reference build; only where oracle/_ref exists (never on a box
-    without /root/reference unless the prebuilt .so travelled with the snapshot)."""
-    import oracle
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    return oracle.Ref()

@@ -3,6 +3,7 @@
 
 Run in the build container only (needs /root/reference):
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py reference_build    # tests/golden/reference_build.json alone
 
 Every expected value written here is an output of the reference's own code
 (Kmers.cpp, hashing.cpp, Decycling.cpp, buckets.hpp, SuperKmerLight.hpp)
@@ -17,6 +18,8 @@ import os
 import random
 import shutil
 import sys
+
+import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
@@ -161,7 +164,60 @@ def multisets(R, O, rng):
     return summary
 
 
+def stream_md5(arrays):
+    """md5 of numeric arrays, each as little-endian uint64 words, in order"""
+    h = hashlib.md5()
+    for a in arrays:
+        h.update(np.asarray(a).astype("<u8").tobytes())
+    return h.hexdigest()
+
+
+def random_reads(rng, n, glen, L=150):
+    """tests/test_gpu_parity.py's _random_reads: the same draws from the same seed"""
+    genome = "".join(rng.choice("ACGT") for _ in range(glen))
+    out = []
+    for _ in range(n):
+        p = rng.randrange(0, glen - L)
+        s = genome[p:p + L]
+        if rng.random() < 0.5:
+            s = s[::-1].translate(str.maketrans("ACGT", "TGCA"))
+        out.append(s)
+    return out
+
+
+GPU_SPECIAL = ["A" * 150, "C" * 150, "G" * 150, "T" * 150, "AC" * 75, "ACG" * 50, "ACGT" * 40, "T" * 149 + "A",
+               "A" * 70 + "ACGTTGCA" * 10, "acgt" * 40, "ACGTTGCATGCA" * 13]  # tests/test_gpu_parity.py's SPECIAL
+
+
+def reference_build(R):
+    """What the tests that once called oracle/_ref directly compare with, so that they run where it is absent:
+    the reference's outputs on the inputs those tests draw from their own seeds (test_oracle.py:
+    test_against_reference_build_*, test_gpu_parity.py: test_gpu_against_the_reference_build_itself)."""
+    out = {"random_reads": [], "units": {}, "gpu": []}
+    rng = random.Random(99)
+    for k, m, b in ((31, 11, 4), (63, 21, 9), (33, 11, 7), (47, 15, 10), (21, 7, 3), (63, 31, 12)):
+        reads = random_reads(rng, 300, 3000) + ["A" * 150, "AC" * 75, "ACG" * 50, "T" * 149 + "A"]
+        lines, nk, nb = R.count(reads, k, m, b, threads=2)
+        out["random_reads"].append({"k": k, "m": m, "b": b, "nb_kmers": nk, "nb_buckets": nb, "md5": md5_lines(lines),
+                                    "enumerate_first40_md5": stream_md5([a for s in reads[:40] for a in R.enumerate(s, k, m)])})
+    rng = random.Random(5)
+    for m in (7, 11, 21, 31):
+        xs = [rng.getrandbits(2 * m) for _ in range(3000)]
+        out["units"][str(m)] = {"class_md5": stream_md5([R.class_many(xs, m)]), "key_md5": stream_md5([R.key_many(xs, m)]),
+                                "coef_hex": [float(c).hex() for c in R.coef_table(m)]}
+    rng = random.Random(91)
+    reads = random_reads(rng, 600, 8000) + GPU_SPECIAL
+    for k, m, b in ((63, 21, 14), (31, 11, 4), (31, 15, 14)):
+        lines, nk, nb = R.count(reads, k, m, b)
+        out["gpu"].append({"k": k, "m": m, "b": b, "nb_kmers": nk, "nb_buckets": nb, "md5": md5_lines(lines)})
+    return out
+
+
 def main():
+    if sys.argv[1:] == ["reference_build"]:  # only tests/golden/reference_build.json
+        oracle.build()
+        json.dump(reference_build(oracle.Ref()), open(os.path.join(HERE, "reference_build.json"), "w"), indent=1)
+        return
     oracle.build()
     R, O = oracle.Ref(), oracle.Oracle()
     rng = random.Random(20250321)
@@ -171,6 +227,7 @@ def main():
     dump("get_minimizer.json.gz", minimizer_vectors(R, rng))
     dump("enumerator.json.gz", enum_vectors(R, rng))
     json.dump(multisets(R, O, rng), open(os.path.join(HERE, "multisets.json"), "w"), indent=1)
+    json.dump(reference_build(R), open(os.path.join(HERE, "reference_build.json"), "w"), indent=1)
     print("golden fixtures written to", HERE)
 
 

@@ -11,6 +11,7 @@ import sys
 import pytest
 
 import brisk_amd
+import oracle
 from conftest import GOLDEN, load_golden
 
 APPS = os.path.join(os.path.dirname(brisk_amd.__file__), "apps")
@@ -21,8 +22,9 @@ def test_facade_compiles_and_counter_cpp_links_unchanged():
     brisk_amd.build_library()
     apps = brisk_amd.build_apps()
     assert os.path.exists(apps["brisk_count"])
-    if os.path.isdir("/root/reference"):
-        assert os.path.exists(apps["counter_ref"]), "apps/counter.cpp did not compile against the facade headers"
+    if os.path.isdir(oracle.REFERENCE_ROOT):
+        oracle.build(ref=True, counter=True)
+        assert os.path.exists(oracle.COUNTER_REF), "apps/counter.cpp did not compile against the facade headers"
 
 
 def test_facade_headers_carry_the_reference_surface():
@@ -67,9 +69,9 @@ def test_brisk_count_binary_on_reference_fixture(tmp_path, mode):
 @pytest.mark.gpu
 def test_reference_counter_cpp_runs_on_the_gpu_index():
     """BASELINE config #1: apps/counter on data/test.fa, k=31 m=11 b=4, with its own --mode 2 self-check.
-    The binary is the reference's counter.cpp compiled unchanged against brisk_amd/include (built where
+    The binary is the reference's counter.cpp compiled unchanged against brisk_amd/include (built into oracle/_ref where
     the reference tree exists; it travels to the GPU box as a built artefact)."""
-    exe = os.path.join(APPS, "counter_ref")
+    exe = oracle.COUNTER_REF
     if not os.path.exists(exe):
         pytest.skip("counter_ref not built (needs the reference tree at build time)")
     out = subprocess.run([exe, "-f", os.path.join(GOLDEN, "test.fa"), "-k", "31", "-m", "11", "-b", "4", "-t", "1", "--mode", "2"],
@@ -101,10 +103,10 @@ def test_reference_counter_cpp_runs_on_the_gpu_index():
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the keys the driver reads, a roofline and a cpu_baseline object, and its
+    """bench.py --full prints ONE JSON line with the keys the driver reads, a roofline and a cpu_baseline object, and its
     own size-independent verification of what it built."""
     import json
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "300000", "--steps", "1", "--warmup", "1", "--cpu-sample-reads", "20000"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--reads", "300000", "--steps", "1", "--warmup", "1", "--cpu-sample-reads", "20000"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -123,17 +125,58 @@ def test_bench_line_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run times --steps steps and prints the headline keys only; --dump-outputs writes the last step's
+    index (summary + a fixed sample of entries) as float64 .npy files, which agree with the oracle's view of that index."""
+    import json
+    import numpy as np
+    import oracle
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "200000", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    for key in ("roofline", "cpu_baseline", "verify", "end_to_end"):
+        assert key not in d, key
+    files = {f: np.load(str(tmp_path / f)) for f in os.listdir(tmp_path)}
+    assert sorted(files) == ["entries_count.npy", "entries_kmer.npy", "entries_minimizer_idx.npy", "index_summary.npy"]
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    entries, nb_kmers, nb_buckets, sum_counts = files["index_summary.npy"][:4]
+    assert entries == nb_kmers == d["config"]["entries_per_step"] and sum_counts == 200000 * (150 - 63 + 1) and nb_buckets > 0
+    kw = files["entries_kmer.npy"].astype(np.uint64)
+    n = len(kw)
+    assert n > 1000 and kw.shape == (n, 4) and len(files["entries_count.npy"]) == len(files["entries_minimizer_idx.npy"]) == n
+    assert files["entries_count.npy"].min() >= 1
+    # the sampled k-mers are k-mers of the bench's reads (the oracle's generator makes the same reads)
+    O = oracle.Oracle()
+    reads = O.synth_reads(int(200000 * 150 / 15.0), 0, 200000)
+    lo = kw[:, 0] | (kw[:, 1] << np.uint64(32))
+    hi = kw[:, 2] | (kw[:, 3] << np.uint64(32))
+    h = O.index_new(63, 21, 14)
+    O.index_insert_reads(h, np.ascontiguousarray(reads.reshape(-1)), np.arange(200001, dtype=np.uint64) * np.uint64(150))
+    got = [O.index_get(h, int(a), int(b), int(i)) for a, b, i in zip(lo[:2000], hi[:2000], files["entries_minimizer_idx.npy"][:2000].astype(int))]
+    want_stats = O.index_stats(h)
+    O.index_free(h)
+    assert (nb_kmers, nb_buckets) == want_stats
+    assert got == [int(c) for c in files["entries_count.npy"][:2000]]
+
+
+@pytest.mark.gpu
 def test_two_rank_rehearsal_matches_single_rank():
     """The N>1 flow of bench.py (pieces, route, all-to-alls of records and histogram slices, one insert per owner) on
     two gloo ranks sharing the GPU builds the same index -- entry count and digest -- as one rank over the same reads."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "600000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"],
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--reads", "600000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                           str(29600 + os.getpid() % 300), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--reads", "300000",
-                          "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert two.returncode == 0, two.stderr[-2000:]
     v1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])["verify"]
     d2 = json.loads([l for l in two.stdout.splitlines() if l.startswith("{")][-1])
@@ -150,12 +193,12 @@ def test_strong_scaling_rehearsal_three_ranks_odd_reads():
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     reads = "500001"
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", reads, "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--scaling", "strong"],
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--reads", reads, "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--scaling", "strong"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
     three = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1", "--master-port",
                             str(29950 + os.getpid() % 300), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--backend", "gloo", "--share-gpu", "--reads", reads,
-                            "--scaling", "strong", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                            "--scaling", "strong", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert three.returncode == 0, three.stderr[-2000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     d3 = json.loads([l for l in three.stdout.splitlines() if l.startswith("{")][-1])

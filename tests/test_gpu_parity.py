@@ -975,12 +975,16 @@ def test_arena_reuse_across_many_indexes(B, O):
         assert ix.memory_info()["pooled"] == 0 or True  # the arena just taken came out of the pool; others may still be in it
 
 
-def test_gpu_against_the_reference_build_itself(B, R):
+def test_gpu_against_the_reference_build_itself(B):
     """the HIP path against oracle/_ref -- the reference's OWN Kmers.cpp / hashing.cpp / Decycling.cpp
     and Bucket<DATA> / SKL, compiled where they lie -- with no restatement in between (every other parity test goes
-    through oracle/brisk_oracle.c, which is itself pinned by the same build).  Skipped where the reference build did
-    not travel."""
+    through oracle/brisk_oracle.c, which is itself pinned by the same build).  What that build computed on these reads
+    is stored in tests/golden/reference_build.json (make_golden.py reference_build)."""
+    want = load_golden("reference_build.json")["gpu"]
     rng = random.Random(91)
     reads = _random_reads(rng, 600, 8000) + SPECIAL
-    for k, m, b in ((63, 21, 14), (31, 11, 4), (31, 15, 14)):
-        assert gpu_count(B, reads, k, m, b, batches=3) == R.count(reads, k, m, b), (k, m, b)
+    configs = ((63, 21, 14), (31, 11, 4), (31, 15, 14))
+    assert [(w["k"], w["m"], w["b"]) for w in want] == list(configs)
+    for (k, m, b), w in zip(configs, want):
+        lines, nk, nb = gpu_count(B, reads, k, m, b, batches=3)
+        assert (nk, nb, md5_lines(lines)) == (w["nb_kmers"], w["nb_buckets"], w["md5"]), (k, m, b)
