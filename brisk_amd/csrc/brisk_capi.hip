@@ -96,6 +96,7 @@ struct brisk_hip_index {
     bool trace = false;         // BRISK_TRACE=1 at create: one stderr line per batch saying which host path and which insert kernel took it
     DevBuf staging, parted, desc, chunk_buf, tags_a, tags_b, packed_tmp, bases_tmp, starts_tmp, sums_tmp, enum_out, lookup_buf;
     DevBuf packed_tmp2, starts_tmp2;  // the second set of insert_reads_pipelined: one sub-batch is scanned while the next one arrives
+    DevBuf anchors, slot_buf, kout_tmp;  // per-position mode (brisk_hip_get_kmers): records' slot anchors, the batch's slot bases, host-call output
     u32* d_ovf_cnt = nullptr;              // OVF_REGIONS counters of the binned scan's overflow area
     std::vector<u64> owner_cut;            // sharded index: owner o holds partitions [owner_cut[o], owner_cut[o + 1]) (n_owners + 1 entries)
     u32* d_owner_cut = nullptr;            // the same on the device once brisk_hip_set_owner_cuts has replaced the equal ranges (else null)
@@ -619,10 +620,11 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
 
 // scan reads -> records in d_rec (cap records).  n_rec_out on host after a sync.
 // one scan launch over n_items reads (or virtual reads when cc.vreads is set); counters are NOT reset here
+// pos: per-position mode (out.ret receives the slot anchors, out.slot_base is set; always k_scan2)
 int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_items, const ScanOut& out, bool query_mode, bool plain,
-                const ChunkCtl& cc) {
+                const ChunkCtl& cc, bool pos = false) {
     ProfScope ps(h, S_SCAN);
-    if (plain) {  // sequence mode needs the minimizer values: the plain kernel carries them
+    if (plain && !pos) {  // sequence mode needs the minimizer values: the plain kernel carries them
         BriskParams P = h->P;
         if (out.ret) {  // and whole vectors: see brisk_hip_scan_sequence
             P.ext_bits -= P.cls_bits;
@@ -639,7 +641,9 @@ int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
     hipLaunchKernelGGL((k_scan2<NCH, MODE, KK, MM>), grid, block, h->scan_lds, h->stream, h->P, h->scfg, d_packed, d_starts, n_items, h->d_tabs, out, cc)
 #define LAUNCH_SCAN2_MODES(NCH, KK, MM)                    \
     {                                                      \
-        if (cc.vreads) LAUNCH_SCAN2(NCH, 2, KK, MM);       \
+        if (pos && cc.vreads) LAUNCH_SCAN2(NCH, 4, KK, MM);  \
+        else if (pos) LAUNCH_SCAN2(NCH, 3, KK, MM);        \
+        else if (cc.vreads) LAUNCH_SCAN2(NCH, 2, KK, MM);  \
         else if (query_mode) LAUNCH_SCAN2(NCH, 1, KK, MM); \
         else LAUNCH_SCAN2(NCH, 0, KK, MM);                 \
     }
@@ -660,20 +664,25 @@ int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
 // Scan a batch into d_rec.  Long sequences (insert mode only) are scanned as chunks, checked at the
 // seams and, if a seam does not match, re-scanned whole; *hist_valid tells whether d_hist still
 // describes exactly the records in d_rec.
+// Per-position mode (d_anchor set, query_mode false; brisk_hip_get_kmers): the insert's records, d_anchor[i] the slot anchor of record i
+// (pos_anchor) from d_slot_base (k_slot_apply), d_tags[i] meaningless on return (the caller numbers the records).
 int scan_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u64* d_rec, u64 cap, bool with_hist,
-              bool query_mode, u32* d_tags, u64* n_rec_out, u64* d_ret = nullptr, u64 kmer_bound = 0, bool* hist_valid = nullptr, bool keep_hist = false) {
+              bool query_mode, u32* d_tags, u64* n_rec_out, u64* d_ret = nullptr, u64 kmer_bound = 0, bool* hist_valid = nullptr, bool keep_hist = false,
+              u64* d_anchor = nullptr, const u64* d_slot_base = nullptr) {
+    const bool pos = d_anchor != nullptr;
     if (hist_valid) *hist_valid = with_hist;
     if (with_hist) {
         h->scan_hist_valid = false;
         if (!keep_hist) HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));  // (keep_hist: add to the pending records' counts)
     }
     HIPCHK(h, hipMemsetAsync(h->d_small, 0, 16, h->stream));
-    ScanOut out{d_rec, cap, h->d_small, with_hist ? h->d_hist : nullptr, (u32*)(h->d_small + 1), d_tags, d_ret, nullptr, 0u, nullptr, 0u, nullptr};
-    const bool plain = h->scan_v1 || d_ret;
+    ScanOut out{d_rec, cap, h->d_small, with_hist ? h->d_hist : nullptr, (u32*)(h->d_small + 1), d_tags, pos ? d_anchor : d_ret, nullptr, 0u, nullptr, 0u, nullptr};
+    const bool plain = !pos && (h->scan_v1 || d_ret);
     int rc;
     u32 n_vr = 0;
     // long sequences are chunked in insert mode (no tags) and in query mode (read tags); not in sequence mode (plain)
-    const bool may_chunk = !plain && kmer_bound > SCAN_LONG && (query_mode ? d_tags != nullptr : !d_tags);
+    const bool may_chunk = !plain && kmer_bound > SCAN_LONG && (pos || (query_mode ? d_tags != nullptr : !d_tags));
+    u64* d_cbase = nullptr;  // per-position mode: the slot base of every chunk's sequence (chunk records carry the chunk as their tag)
     VRead *d_vr = nullptr, *d_rerun = nullptr;
     ChunkState *d_spec = nullptr, *d_truth = nullptr;
     u32 *d_status = nullptr, *d_cursor = nullptr, *d_stop = nullptr;
@@ -684,7 +693,7 @@ int scan_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 
     if (may_chunk) {
         cap_vr = kmer_bound / chunk + kmer_bound / SCAN_LONG + 2;
         const u64 cap_long = kmer_bound / SCAN_LONG + 1;
-        const size_t bytes = 2 * cap_vr * sizeof(VRead) + (2 * cap_vr + 1) * sizeof(ChunkState) + 3 * cap_vr * 4 + cap_long * sizeof(LongRead);
+        const size_t bytes = 2 * cap_vr * sizeof(VRead) + (2 * cap_vr + 1) * sizeof(ChunkState) + 3 * cap_vr * 4 + cap_long * sizeof(LongRead) + (pos ? cap_vr * 8 + 8 : 0);
         if ((rc = ensure(h, h->chunk_buf, bytes))) return rc;
         d_vr = (VRead*)h->chunk_buf.p;
         d_rerun = d_vr + cap_vr;
@@ -694,6 +703,7 @@ int scan_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 
         d_cursor = d_status + cap_vr;
         d_stop = d_cursor + cap_vr;
         LongRead* d_long = (LongRead*)(d_stop + cap_vr + (cap_vr & 1));
+        if (pos) d_cbase = (u64*)(d_long + cap_long);
         HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 16, h->stream));
         hipLaunchKernelGGL(k_plan_chunks, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_starts, n_reads, h->P.k, chunk, (u32)cap_vr,
                            (u32*)(h->d_small + 7), d_long, (u32*)(h->d_small + 6));
@@ -708,8 +718,8 @@ int scan_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 
         n_vr = (u32)h->h_small[7];
         if (n_vr > cap_vr) return fail(h, BRISK_HIP_EHIP, "chunk plan exceeds its bound");
     }
-    ChunkCtl cc{nullptr, nullptr, nullptr, n_vr ? SCAN_LONG : 0u};
-    if ((rc = launch_scan(h, d_packed, d_starts, n_reads, out, query_mode, plain, cc))) return rc;
+    ChunkCtl cc{nullptr, nullptr, nullptr, n_vr ? SCAN_LONG : 0u, d_slot_base};
+    if ((rc = launch_scan(h, d_packed, d_starts, n_reads, out, query_mode, plain, cc, pos))) return rc;
     if (n_vr) {
         // records of the short reads are in [0, n1); the chunked launch appends after them and tags its records with
         // their chunk; seeded re-scans append after those
@@ -718,7 +728,10 @@ int scan_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 
         const u64 n1 = std::min<u64>(h->h_small[0], cap);
         u32* d_ctags = d_tags;  // chunk index per record of the chunked launches (query mode: in the caller's tag array, read indices later)
         u64* d_qret = nullptr;  // query mode: where a record's vector starts | its minimizer is 0 << 63
-        if (!query_mode) {
+        if (pos) {
+            hipLaunchKernelGGL(k_chunk_slot_base, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, d_vr, n_vr, d_slot_base, d_cbase);
+            if (int lrc = launch_check(h, "k_chunk_slot_base")) return lrc;
+        } else if (!query_mode) {
             if ((rc = ensure(h, h->tags_a, cap * 4))) return rc;
             d_ctags = (u32*)h->tags_a.p;
         } else {
@@ -729,9 +742,9 @@ int scan_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 
         HIPCHK(h, hipMemsetAsync(d_stop, 0xff, cap_vr * 4, h->stream));
         ScanOut out2 = out;
         out2.tag = d_ctags;
-        out2.ret = d_qret;
-        ChunkCtl c2{d_vr, d_spec, d_truth, 0u};
-        if ((rc = launch_scan(h, d_packed, d_starts, n_vr, out2, false, false, c2))) return rc;
+        out2.ret = pos ? d_anchor : d_qret;
+        ChunkCtl c2{d_vr, d_spec, d_truth, 0u, d_cbase};
+        if ((rc = launch_scan(h, d_packed, d_starts, n_vr, out2, false, false, c2, pos))) return rc;
         HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         const u64 n2 = std::min<u64>(h->h_small[0], cap);
@@ -751,13 +764,40 @@ int scan_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 
             const u32 n_rerun = (u32)h->h_small[7];
             if (!n_rerun) break;
             total_rerun += n_rerun;
-            ChunkCtl c3{d_rerun, d_spec, d_truth, 0u};
-            if ((rc = launch_scan(h, d_packed, d_starts, n_rerun, out3, false, false, c3))) return rc;
+            ChunkCtl c3{d_rerun, d_spec, d_truth, 0u, d_cbase};
+            if ((rc = launch_scan(h, d_packed, d_starts, n_rerun, out3, false, false, c3, pos))) return rc;
         }
         static const bool dbg_chunks = getenv("BRISK_DEBUG_CHUNKS") != nullptr;
         if (dbg_chunks) fprintf(stderr, "[brisk_hip] chunked scan: %u chunks of %u steps, %llu seeded re-scans in %u rounds\n", n_vr, chunk,
                                 (unsigned long long)total_rerun, rounds);
-        if (query_mode) {
+        if (pos && total_rerun) {
+            // drop what the re-scanned chunks emitted speculatively, anchors alongside; what the seeded scans emitted stays
+            HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (!(u32)h->h_small[1]) {
+                const u64 n3 = std::min<u64>(h->h_small[0], cap);
+                if ((rc = ensure(h, h->parted, (n3 - n1 + 1) * (h->P.stride * 8 + 8)))) return rc;
+                u64* stage = (u64*)h->parted.p;
+                u64* stage_anc = stage + (n3 - n1 + 1) * h->P.stride;
+                HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 8, h->stream));
+                hipLaunchKernelGGL(k_pos_filter, dim3(nblocks(n3 - n1, 256)), dim3(256), 0, h->stream, h->P, d_rec, d_anchor, d_ctags, n1, n2, n3, d_status, stage, stage_anc,
+                                   h->d_small + 6);
+                if (int lrc = launch_check(h, "k_pos_filter")) return lrc;
+                HIPCHK(h, hipMemcpyAsync(h->h_small + 6, h->d_small + 6, 8, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                const u64 kept = h->h_small[6];
+                if (kept) {
+                    HIPCHK(h, hipMemcpyAsync(d_rec + n1 * h->P.stride, stage, kept * h->P.stride * 8, hipMemcpyDeviceToDevice, h->stream));
+                    HIPCHK(h, hipMemcpyAsync(d_anchor + n1, stage_anc, kept * 8, hipMemcpyDeviceToDevice, h->stream));
+                }
+                h->h_small[6] = n1 + kept;  // pinned: stays untouched until the copy below has run
+                HIPCHK(h, hipMemcpyAsync(h->d_small, h->h_small + 6, 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+            }
+            if (hist_valid) *hist_valid = false;
+        } else if (pos) {
+            // no chunk was re-scanned: every record stands
+        } else if (query_mode) {
             // stop every sequence where query_sequence stops it, drop the void records, tag the rest with their read
             HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -876,15 +916,19 @@ static bool has_fast_geometry(const BriskParams& P) {
 
 // Scan a batch straight into per-partition bins (insert or query mode).  *applied = false: the batch does not qualify, or its
 // records did not fit (nothing of the index has been touched): the classic path takes it.
-int scan_binned(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, bool query_mode, bool* applied, BinLayout* bl, u64* n_rec_out) {
+// pos_slot_base (per-position mode, query_mode false): the batch's slot bases; every record's slot anchor goes to h->anchors, laid out as
+// the tags, and its tag is its own index there.
+int scan_binned(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, bool query_mode, bool* applied, BinLayout* bl, u64* n_rec_out,
+                const u64* pos_slot_base = nullptr) {
     *applied = false;
+    const bool pos = pos_slot_base != nullptr;
     static const long forced = getenv("BRISK_BINS") ? atol(getenv("BRISK_BINS")) : -1;  // 0: never; S > 0: always, with bins of S records (tests)
     if (forced == 0 || h->entry_ids || h->scan_v1 || h->P.n_owners > 1) return BRISK_HIP_OK;
     // minimizers short enough for class bits are few and unevenly used: a tenth of the partitions hold everything, and bins sized for
     // the mean overflow
     if (forced < 0 && h->P.cls_bits) return BRISK_HIP_OK;
     static const bool query_generic = getenv("BRISK_QUERY_GENERIC") != nullptr;
-    if (query_mode && (query_generic || !has_fast_geometry(h->P))) return BRISK_HIP_OK;
+    if ((query_mode || pos) && (query_generic || !has_fast_geometry(h->P))) return BRISK_HIP_OK;
     int rc;
     u64 bound = 0, in_long = 0;
     if ((rc = count_kmers(h, d_starts, n_reads, &bound, &in_long))) return rc;
@@ -903,18 +947,20 @@ int scan_binned(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
     if ((rc = ensure(h, h->bins, bytes))) return rc == BRISK_HIP_ENOMEM ? (h->err.clear(), BRISK_HIP_OK) : rc;
     if ((rc = ensure(h, h->staging, ovf_cap * h->P.stride * 8))) return rc;
     u32* tags = nullptr;
-    if (query_mode) {
+    if (query_mode || pos) {
         if ((rc = ensure(h, h->tags_a, (h->n_parts * cap + ovf_cap) * 4))) return rc == BRISK_HIP_ENOMEM ? (h->err.clear(), BRISK_HIP_OK) : rc;
         tags = (u32*)h->tags_a.p;
     }
+    if (pos && (rc = ensure(h, h->anchors, (h->n_parts * cap + ovf_cap) * 8))) return rc == BRISK_HIP_ENOMEM ? (h->err.clear(), BRISK_HIP_OK) : rc;
     h->scan_hist_valid = false;
     HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_small, 0, 16, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_small + 7, 0, 8, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_ovf_cnt, 0, OVF_REGIONS * 4, h->stream));
-    ScanOut out{nullptr, 0, h->d_small, h->d_hist, (u32*)(h->d_small + 1), tags, nullptr, (u64*)h->bins.p, (u32)cap, (u64*)h->staging.p, ovf_region_cap, h->d_ovf_cnt};
-    ChunkCtl cc{nullptr, nullptr, nullptr, 0u};
-    if ((rc = launch_scan(h, d_packed, d_starts, n_reads, out, query_mode, false, cc))) return rc;
+    ScanOut out{nullptr, 0, h->d_small, h->d_hist, (u32*)(h->d_small + 1), tags, pos ? (u64*)h->anchors.p : nullptr, (u64*)h->bins.p, (u32)cap, (u64*)h->staging.p,
+                ovf_region_cap, h->d_ovf_cnt};
+    ChunkCtl cc{nullptr, nullptr, nullptr, 0u, pos_slot_base};
+    if ((rc = launch_scan(h, d_packed, d_starts, n_reads, out, query_mode, false, cc, pos))) return rc;
     hipLaunchKernelGGL(k_sum_regions, dim3(1), dim3(1024), 0, h->stream, h->d_ovf_cnt, ovf_region_cap, h->d_small + 7);
     if ((rc = launch_check(h, "k_sum_regions"))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
@@ -925,7 +971,7 @@ int scan_binned(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
     if (h->trace) fprintf(stderr, "[brisk_hip] path: binned scan of %llu reads: %llu records, bins of %llu, %llu records beyond their bins\n", (unsigned long long)n_reads,
                           (unsigned long long)h->h_small[0], (unsigned long long)cap, (unsigned long long)h->h_small[7]);
     *bl = BinLayout{(u64*)h->bins.p, (u32)cap, (u64*)h->staging.p, h->h_small[7], h->d_ovf_cnt, ovf_region_cap, tags};
-    if (h->verify && !query_mode && (rc = verify_hist(h, h->h_small[0], bound, "binned scan"))) return rc;
+    if (h->verify && !query_mode && !pos && (rc = verify_hist(h, h->h_small[0], bound, "binned scan"))) return rc;
     *applied = true;
     return BRISK_HIP_OK;
 }
@@ -1055,7 +1101,10 @@ int insert_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_sta
 
 // records (with a tag each) -> d_sums[tag] += sum of the counts of the record's k-mers that are present.
 // d_hist holds the records' per-partition histogram; d_sums must be zeroed by the caller.
-int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, u64 n_rec, unsigned long long* d_sums, const BinLayout* bl = nullptr);
+// per-position mode (kout set, d_sums null): a record's tag indexes its slot anchor in `anchors`, and every k-mer found writes
+// 0x100 | count to its slot of kout (zeroed by the caller)
+int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, u64 n_rec, unsigned long long* d_sums, const BinLayout* bl = nullptr,
+                       const u64* anchors = nullptr, uint16_t* kout = nullptr, u64 kout_n = 0);
 
 int query_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, unsigned long long* d_sums) {
     // d_sums[n_reads] must be zeroed by the caller
@@ -1079,7 +1128,8 @@ int query_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_star
 }
 
 // `bl`: the records (and bl->tags) lie in per-partition bins, the ones beyond them in bl->ovf (fast geometries only); else d_rec / d_tags
-int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, u64 n_rec, unsigned long long* d_sums, const BinLayout* bl) {
+int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, u64 n_rec, unsigned long long* d_sums, const BinLayout* bl,
+                       const u64* anchors, uint16_t* kout, u64 kout_n) {
     const BriskParams& P = h->P;
     h->scan_hist_valid = false;
     int rc;
@@ -1131,9 +1181,16 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
         // + 8: 135 slots per partition), which keeps twice the waves resident; else 256
         static const long ent_env = getenv("BRISK_QUERY_ENT") ? atol(getenv("BRISK_QUERY_ENT")) : 0;  // experiments and tests: 128 | 256
         const bool small = ent_env ? ent_env == 128 : h->arena_used_host / own_partitions(h).len <= 135;
-#define LAUNCH_QUERY_FAST_ENT(NW, KB, SH, ENT)                                                                                                                    \
-    hipLaunchKernelGGL((k_query_fast<NW, KB, SH, ENT>), dim3(std::min<u32>(batches, resident((const void*)k_query_fast<NW, KB, SH, ENT>))), dim3(64), 0, h->stream, P, \
-                       src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6))
+#define LAUNCH_QUERY_FAST_ENT(NW, KB, SH, ENT)                                                                                                                      \
+    do {                                                                                                                                                              \
+        if (kout)                                                                                                                                                     \
+            hipLaunchKernelGGL((k_query_fast<NW, KB, SH, ENT, true>), dim3(std::min<u32>(batches, resident((const void*)k_query_fast<NW, KB, SH, ENT, true>))), dim3(64), \
+                               0, h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6),  \
+                               anchors, kout, kout_n);                                                                                                                \
+        else                                                                                                                                                          \
+            hipLaunchKernelGGL((k_query_fast<NW, KB, SH, ENT>), dim3(std::min<u32>(batches, resident((const void*)k_query_fast<NW, KB, SH, ENT>))), dim3(64), 0,        \
+                               h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6)); \
+    } while (0)
 #define LAUNCH_QUERY_FAST(NW, KB, SH)                     \
     {                                                     \
         if (small) LAUNCH_QUERY_FAST_ENT(NW, KB, SH, 128); \
@@ -1150,17 +1207,72 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
         else if (fast && P.nw == 2 && P.kb == 17 && P.shift == 6) LAUNCH_QUERY_FAST(2, 17, 6)
         else if (fast && P.nw == 2 && P.kb == 20 && P.shift == 0) LAUNCH_QUERY_FAST(2, 20, 0)  // k31 m11 b11
         else if (bl) return fail(h, BRISK_HIP_EHIP, "binned query without a kernel for this geometry");
+        else if (kout)
+            hipLaunchKernelGGL(k_query<true>, dim3(std::min<u32>(batches, INSERT_SLOTS)), dim3(64), 0, h->stream, P, (const u64*)h->parted.p, (const u32*)h->tags_b.p,
+                               (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6), anchors, kout, kout_n);
         else
-            hipLaunchKernelGGL(k_query, dim3(std::min<u32>(batches, INSERT_SLOTS)), dim3(64), 0, h->stream, P, (const u64*)h->parted.p, (const u32*)h->tags_b.p,
+            hipLaunchKernelGGL(k_query<>, dim3(std::min<u32>(batches, INSERT_SLOTS)), dim3(64), 0, h->stream, P, (const u64*)h->parted.p, (const u32*)h->tags_b.p,
                                (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6));
 #undef LAUNCH_QUERY_FAST
 #undef LAUNCH_QUERY_FAST_ENT
         if (int lrc = launch_check(h, "k_query")) return lrc;
         // the listed partitions (none, as a rule: the kernel reads the list's length on the device and returns)
-        hipLaunchKernelGGL(k_query_huge, dim3(256), dim3(HG_THREADS), 0, h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, (const u32*)h->huge.p + 1,
-                           (const u32*)h->huge.p, h->ix, d_sums);
+        if (kout)
+            hipLaunchKernelGGL(k_query_huge<true>, dim3(256), dim3(HG_THREADS), 0, h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p,
+                               (const u32*)h->huge.p + 1, (const u32*)h->huge.p, h->ix, d_sums, anchors, kout, kout_n);
+        else
+            hipLaunchKernelGGL(k_query_huge<>, dim3(256), dim3(HG_THREADS), 0, h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p,
+                               (const u32*)h->huge.p + 1, (const u32*)h->huge.p, h->ix, d_sums);
     }
     return launch_check(h, "k_query_huge");
+}
+
+// Per-position query of one batch (brisk_hip_get_kmers): d_out[base_r + i] = 0x100 | count of the k-mer at nucleotide i of read r
+// when present; d_out (the batch's slots, base_0 = 0) zeroed by the caller.  The scan runs as for an insert (every k-mer, no query
+// stop) and gives every record the slot of its minimizer (pos_anchor); the probe kernels then write each k-mer's answer to its slot.
+int kmers_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, uint16_t* d_out, u64 n_slots) {
+    int rc;
+    const u32 nb = nblocks(n_reads, 256 * SLOT_ITEMS);
+    if ((rc = ensure(h, h->slot_buf, (n_reads + nb + 1) * 8))) return rc;
+    u64* d_slot_base = (u64*)h->slot_buf.p;
+    u64* d_bsum = d_slot_base + n_reads;
+    hipLaunchKernelGGL(k_slot_block, dim3(nb), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, d_bsum);
+    hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bsum, nb);
+    hipLaunchKernelGGL(k_slot_apply, dim3(nb), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, (const u64*)d_bsum, d_slot_base);
+    if ((rc = launch_check(h, "k_slot_block/top/apply"))) return rc;
+    u64 n_rec = 0;
+    {  // the scan bins the records, their own indices as tags and their anchors alongside
+        BinLayout bl{};
+        bool binned = false;
+        if ((rc = scan_binned(h, d_packed, d_starts, n_reads, false, &binned, &bl, &n_rec, d_slot_base))) return rc;
+        if (binned) return n_rec ? query_records_impl(h, nullptr, nullptr, n_rec, nullptr, &bl, (const u64*)h->anchors.p, d_out, n_slots) : BRISK_HIP_OK;
+    }
+    u64 bound = 0;
+    if ((rc = count_kmers(h, d_starts, n_reads, &bound))) return rc;
+    if (bound == 0) return BRISK_HIP_OK;
+    u64 cap = records_estimate(h, bound, n_reads);
+    bool hist_ok = true;
+    for (int attempt = 0;; attempt++) {
+        if ((rc = ensure(h, h->staging, cap * h->P.stride * 8))) return rc;
+        if ((rc = ensure(h, h->tags_a, cap * 4))) return rc;
+        if ((rc = ensure(h, h->anchors, cap * 8))) return rc;
+        rc = scan_impl(h, d_packed, d_starts, n_reads, (u64*)h->staging.p, cap, true, false, (u32*)h->tags_a.p, &n_rec, nullptr, bound, &hist_ok, false,
+                       (u64*)h->anchors.p, d_slot_base);
+        if (rc != BRISK_HIP_ECAPACITY) break;
+        if (attempt) return fail(h, BRISK_HIP_EHIP, "scan overflowed its exact bound");
+        cap = bound;
+    }
+    if (rc) return rc;
+    if (n_rec == 0) return BRISK_HIP_OK;
+    if (n_rec >= (1ull << 32)) return fail(h, BRISK_HIP_EINVAL, "more than 2^32-1 records in one batch: lower max_batch_reads");
+    if (!hist_ok) {  // re-scanned chunks: count the records that are left
+        HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
+        hipLaunchKernelGGL(k_part_hist, dim3(nblocks(n_rec, 256)), dim3(256), 0, h->stream, h->P, (const u64*)h->staging.p, n_rec, h->d_hist);
+        if (int lrc = launch_check(h, "k_part_hist")) return lrc;
+    }
+    hipLaunchKernelGGL(k_iota, dim3(nblocks(n_rec, 256)), dim3(256), 0, h->stream, (u32*)h->tags_a.p, n_rec);
+    if ((rc = launch_check(h, "k_iota"))) return rc;
+    return query_records_impl(h, (const u64*)h->staging.p, (const u32*)h->tags_a.p, n_rec, nullptr, nullptr, (const u64*)h->anchors.p, d_out, n_slots);
 }
 
 // nuc2int (Kmers.cpp:442-444) in bulk on the host: n ASCII bytes -> (n + 15) / 16 words of the packed stream, first nucleotide of a
@@ -1720,7 +1832,8 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
             static size_t lds_attr = 0;
             if (h->scan_lds > lds_attr) {
                 lds_attr = h->scan_lds;
-#define SCAN2_FNS(NCH, KK, MM) (const void*)k_scan2<NCH, 0, KK, MM>, (const void*)k_scan2<NCH, 1, KK, MM>, (const void*)k_scan2<NCH, 2, KK, MM>
+#define SCAN2_FNS(NCH, KK, MM) (const void*)k_scan2<NCH, 0, KK, MM>, (const void*)k_scan2<NCH, 1, KK, MM>, (const void*)k_scan2<NCH, 2, KK, MM>, \
+                               (const void*)k_scan2<NCH, 3, KK, MM>, (const void*)k_scan2<NCH, 4, KK, MM>
                 const void* fns[] = {SCAN2_FNS(0, 0, 0), SCAN2_FNS(3, 0, 0), SCAN2_FNS(4, 0, 0), SCAN2_FNS(6, 0, 0), SCAN2_FNS(0, 31, 11), SCAN2_FNS(0, 31, 15), SCAN2_FNS(0, 63, 21),
                                      (const void*)k_debug_keys};
 #undef SCAN2_FNS
@@ -1846,7 +1959,7 @@ static int check_device_flags(brisk_hip_index* h) {
     HIPCHK(h, hipMemcpyAsync(&e, h->ix.err, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (e) return fail(h, BRISK_HIP_EHIP, "device-side consistency check failed, flags=" + std::to_string(e) +
-                                              " (1 scatter slot out of range, 2 arena exhausted, 4 chunk overflow): the index is not valid");
+                                              " (1 scatter slot out of range, 2 arena exhausted, 4 chunk overflow, 8 per-k-mer slot out of range): the index is not valid");
     return BRISK_HIP_OK;
 }
 
@@ -1925,6 +2038,67 @@ BRISK_API int brisk_hip_get_packed(brisk_hip_index* h, const uint32_t* d_packed,
     for (u64 r0 = 0; r0 < n_reads; r0 += h->max_batch_reads) {  // the record tags of a batch are indices into its own slice of the sums
         const u64 nb = std::min<u64>(h->max_batch_reads, n_reads - r0);
         if (int rc = query_packed_impl(h, d_packed, d_starts + r0, nb, (unsigned long long*)d_per_read_sum + r0)) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return check_device_flags(h);
+}
+
+static u64 host_slots(const uint64_t* offsets, u64 r0, u64 r1, u32 k) {  // slots of reads [r0, r1)
+    u64 n = 0;
+    for (u64 r = r0; r < r1; r++) {
+        const u64 len = offsets[r + 1] - offsets[r];
+        if (len >= k) n += len - k + 1;
+    }
+    return n;
+}
+
+BRISK_API int brisk_hip_get_kmers(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint16_t* out, uint64_t cap) {
+    if (!h || (n_reads && (!bases || !offsets))) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "get_kmers on a sharded index sees one bucket range only");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "get_kmers on an entry-id index: DATA lives with the caller (find_kmers)");
+    for (u64 r = 0; r < n_reads; r++)
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i])");
+    const u64 total = host_slots(offsets, 0, n_reads, h->P.k);
+    if (cap < total) return fail(h, BRISK_HIP_ECAPACITY, "get_kmers: " + std::to_string(total) + " slots, out holds " + std::to_string(cap));
+    if (total && !out) return BRISK_HIP_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    u64 done = 0;  // slots of the batches before this one
+    int rc = for_each_host_batch(h, bases, offsets, n_reads, [&](u64 r0, u64 nr) -> int {
+        const u64 ns = host_slots(offsets, r0, r0 + nr, h->P.k);
+        if (!ns) return BRISK_HIP_OK;
+        int rc2;
+        if ((rc2 = ensure(h, h->kout_tmp, ns * 2))) return rc2;
+        HIPCHK(h, hipMemsetAsync(h->kout_tmp.p, 0, ns * 2, h->stream));
+        if ((rc2 = kmers_packed_impl(h, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, nr, (uint16_t*)h->kout_tmp.p, ns))) return rc2;
+        HIPCHK(h, hipMemcpyAsync(out + done, h->kout_tmp.p, ns * 2, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        done += ns;
+        return BRISK_HIP_OK;
+    });
+    if (rc) return rc;
+    return check_device_flags(h);
+}
+
+BRISK_API int brisk_hip_get_kmers_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint16_t* d_out) {
+    if (!h || (n_reads && (!d_packed || !d_starts || !d_out))) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "get_kmers_packed on a sharded index sees one bucket range only");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "get_kmers_packed on an entry-id index: DATA lives with the caller (find_kmers)");
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    u64 done = 0;  // slots of the batches before this one
+    for (u64 r0 = 0; r0 < n_reads; r0 += h->max_batch_reads) {
+        const u64 nb = std::min<u64>(h->max_batch_reads, n_reads - r0);
+        u64 ns = 0;
+        int rc;
+        if ((rc = count_kmers(h, d_starts + r0, nb, &ns))) return rc;
+        if (!ns) continue;
+        HIPCHK(h, hipMemsetAsync(d_out + done, 0, ns * 2, h->stream));
+        if ((rc = kmers_packed_impl(h, d_packed, d_starts + r0, nb, d_out + done, ns))) return rc;
+        done += ns;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return check_device_flags(h);

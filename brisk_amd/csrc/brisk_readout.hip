@@ -6,9 +6,26 @@
 // chain), the partition's entries stream through it, and every hit adds the entry's count to the
 // instance's record; a record's total goes to its read with one atomic
 // (get_superkmer, Brisk.hpp:102-118; summed per read as counter.cpp:296-301 does).
+// POS (per-position mode, brisk_hip_get_kmers): a record's tag indexes its slot anchor (anchors[], pos_anchor in brisk_scan.hip), and
+// every instance found writes 0x100 | count to its own slot of kout[] instead of adding to a sum; per_read_sum is not used.
+// k-mer j of a record (the order its key is built in: minimizer_idx rising) and where it goes
+__device__ __forceinline__ u64 pos_slot0(const BriskParams& P, u64 anchor, u32 idx0p) {  // slot of k-mer 0 | descending << 63
+    const u32 idx0 = idx0p - P.suff_reduc;
+    const u64 a = anchor & ~(1ull << 63);
+    return (anchor >> 63) ? (a - idx0) | (1ull << 63) : a + idx0 - P.w;
+}
+__device__ __forceinline__ u64 pos_slot(u64 s0, u32 j) { return (s0 >> 63) ? (s0 & ~(1ull << 63)) - j : s0 + j; }
+// the store, never outside the caller's n slots (a slot out of range means a broken anchor: flag 8 in IndexDev::err)
+__device__ __forceinline__ void pos_store(uint16_t* kout, u64 n, u64 slot, u32 v, u32* err) {
+    if (slot < n) kout[slot] = (uint16_t)v;
+    else atomicOr(err, 8u);
+}
+template <bool POS = false>
 __global__ void __launch_bounds__(64) k_query(BriskParams P, const u64* __restrict__ rec, const u32* __restrict__ tags,
                                               const PartDesc* __restrict__ desc, u32 n_touched, IndexDev ix,
-                                              unsigned long long* __restrict__ per_read_sum, u32* __restrict__ work_counter) {
+                                              unsigned long long* __restrict__ per_read_sum, u32* __restrict__ work_counter,
+                                              const u64* __restrict__ anchors = nullptr, uint16_t* __restrict__ kout = nullptr, u64 kout_n = 0) {
+    __shared__ u64 s_pos[POS ? WI_MAX_REC : 1];
     __shared__ u64 s_key[2 * WI_MAX_INST];
     __shared__ u64 s_rec[WI_MAX_REC * 5];
     __shared__ u32 s_tab[WI_TABLE];
@@ -49,6 +66,7 @@ __global__ void __launch_bounds__(64) k_query(BriskParams P, const u64* __restri
                 s_pref[lane + 1] = x0;
                 if (lane == 0) s_pref[0] = 0;
                 s_rsum[lane] = 0;
+                if (POS && lane < nrec) s_pos[lane] = pos_slot0(P, anchors[tags[rc + lane]], hdr_idx0(my_hdr));
 #pragma unroll
                 for (u32 w = 0; w < WI_TS; w++) s_tab[w * 64 + lane] = EMPTY_SLOT;
                 {
@@ -77,12 +95,15 @@ __global__ void __launch_bounds__(64) k_query(BriskParams P, const u64* __restri
                     for (;;) {
                         const u32 v = s_tab[h];
                         if (v == EMPTY_SLOT) break;
-                        if (s_key[2 * v] == key.lo && s_key[2 * v + 1] == key.hi) atomicAdd(&s_rsum[s_irec[v]], cnt);
+                        if (s_key[2 * v] == key.lo && s_key[2 * v + 1] == key.hi) {
+                            if (POS) pos_store(kout, kout_n, pos_slot(s_pos[s_irec[v]], v - s_pref[s_irec[v]]), 0x100u | cnt, ix.err);
+                            else atomicAdd(&s_rsum[s_irec[v]], cnt);
+                        }
                         h = (h + 1) & (WI_TABLE - 1);
                     }
                 }
                 wave_sync();
-                if (lane < nrec) {
+                if (!POS && lane < nrec) {
                     const u32 sum = s_rsum[lane];
                     if (sum) atomicAdd(&per_read_sum[tags[rc + lane]], (unsigned long long)sum);
                 }
@@ -132,10 +153,12 @@ __device__ __forceinline__ void inst_key_words(const u32* s_rw, u32 r, u32 i, u6
     *lo_out = lo;
     *hi_out = hi;
 }
-template <u32 NW, u32 KB, u32 SHIFT, u32 ENT>
+// POS: per-position mode, as in k_query
+template <u32 NW, u32 KB, u32 SHIFT, u32 ENT, bool POS = false>
 __global__ void __launch_bounds__(64) k_query_fast(BriskParams PP, RecSrc src, const u32* __restrict__ tags_binned, const u32* __restrict__ tags,
                                                    const PartDesc* __restrict__ desc, u32 n_touched, IndexDev ix, unsigned long long* __restrict__ per_read_sum,
-                                                   u32* __restrict__ work_counter) {
+                                                   u32* __restrict__ work_counter, const u64* __restrict__ anchors = nullptr, uint16_t* __restrict__ kout = nullptr,
+                                                   u64 kout_n = 0) {
     // records and their reads' indices: classic layout (src.bin_cap == 0) src.rec / tags in partition order; binned: record i of a
     // partition in its bin (tags_binned alongside) for i < bin_cap, beyond it among the overflow records src.ovf / tags (RecSrc)
     constexpr u32 RS = RecGeom<NW>::RS;
@@ -149,6 +172,7 @@ __global__ void __launch_bounds__(64) k_query_fast(BriskParams PP, RecSrc src, c
     __shared__ u32 s_tab[QF_TABLE];
     __shared__ u32 s_rw[QF_REC * RS + 4];
     __shared__ u32 s_rsum[QF_REC];
+    __shared__ u64 s_pos[POS ? QF_REC : 1];
     __shared__ __attribute__((aligned(4))) uint8_t s_irec[QF_MAX_INST];
     u32* irec32 = (u32*)s_irec;
     const u32 lane = threadIdx.x;
@@ -195,6 +219,11 @@ __global__ void __launch_bounds__(64) k_query_fast(BriskParams PP, RecSrc src, c
                         const u32 info = start | (raw_n << 10) | (hdr_idx0(my_hdr) << 18) | ((hdr_bucket(my_hdr) & ((1u << SHIFT) - 1)) << 26);
                         store_rec_words<NW>(s_rw + lane * RS, rr, info);
                         if (raw_n) s_irec[start] = (uint8_t)(lane + 1);  // instance -> record: a mark on every record's first instance ...
+                        if (POS) {
+                            const u32 i = rc - d.r_begin + lane;
+                            const u32 tag = !src.bin_cap ? tags[rc + lane] : i < src.bin_cap ? tags_binned[(u64)d.part * src.bin_cap + i] : tags[d.r_begin + i - src.bin_cap];
+                            s_pos[lane] = pos_slot0(P, anchors[tag], hdr_idx0(my_hdr));
+                        }
                     }
                     wave_sync();
                     {  // ... and a running maximum spreads the marks (records lie in lane order); a lane owns IW * 4 consecutive instances here
@@ -232,20 +261,25 @@ __global__ void __launch_bounds__(64) k_query_fast(BriskParams PP, RecSrc src, c
                                 if (pa) {
                                     if (ea == EMPTY_SLOT) pa = false;
                                     else if (qa0 == alo && qa1 == ahi) {
-                                        fa = ea >> 16;
+                                        fa = (ea >> 16) | (POS ? 0x100u : 0u);  // (POS: a present k-mer whose count wrapped to 0 is still found)
                                         pa = false;
                                     } else ha = (ha + 1) & (QF_TABLE - 1);
                                 }
                                 if (pb) {
                                     if (eb == EMPTY_SLOT) pb = false;
                                     else if (qb0 == blo && qb1 == bhi) {
-                                        fb = eb >> 16;
+                                        fb = (eb >> 16) | (POS ? 0x100u : 0u);
                                         pb = false;
                                     } else hb = (hb + 1) & (QF_TABLE - 1);
                                 }
                             }
-                            if (fa) atomicAdd(&s_rsum[ra], fa);
-                            if (fb) atomicAdd(&s_rsum[rb], fb);
+                            if (POS) {  // (consecutive lanes, consecutive k-mers of a record: neighbouring slots)
+                                if (fa) pos_store(kout, kout_n, pos_slot(s_pos[ra], ia - (s_rw[ra * RS + RecGeom<NW>::INFO] & 0x3ffu)), fa, ix.err);
+                                if (fb) pos_store(kout, kout_n, pos_slot(s_pos[rb], ib - (s_rw[rb * RS + RecGeom<NW>::INFO] & 0x3ffu)), fb, ix.err);
+                            } else {
+                                if (fa) atomicAdd(&s_rsum[ra], fa);
+                                if (fb) atomicAdd(&s_rsum[rb], fb);
+                            }
                             i0 += 128;
                         } else {  // the last <= 64
                             const u32 ia = i0 + lane;
@@ -263,17 +297,19 @@ __global__ void __launch_bounds__(64) k_query_fast(BriskParams PP, RecSrc src, c
                                 if (pa) {
                                     if (ea == EMPTY_SLOT) pa = false;
                                     else if (qa0 == alo && qa1 == ahi) {
-                                        fa = ea >> 16;
+                                        fa = (ea >> 16) | (POS ? 0x100u : 0u);  // (POS: a present k-mer whose count wrapped to 0 is still found)
                                         pa = false;
                                     } else ha = (ha + 1) & (QF_TABLE - 1);
                                 }
                             }
-                            if (fa) atomicAdd(&s_rsum[ra], fa);
+                            if (POS) {
+                                if (fa) pos_store(kout, kout_n, pos_slot(s_pos[ra], ia - (s_rw[ra * RS + RecGeom<NW>::INFO] & 0x3ffu)), fa, ix.err);
+                            } else if (fa) atomicAdd(&s_rsum[ra], fa);
                             i0 += 64;
                         }
                     }
                     wave_sync();
-                    if (lane < nrec) {
+                    if (!POS && lane < nrec) {
                         const u32 sum = s_rsum[lane];
                         if (sum) {
                             u32 tag;
@@ -299,9 +335,13 @@ __global__ void __launch_bounds__(64) k_query_fast(BriskParams PP, RecSrc src, c
 #define HQ_LIST_CAP 65536u   // listed partitions per batch (the rest stay with the wave kernels)
 #define HQ_ENT 2048u
 #define HQ_TAB 4096u
+// POS: per-position mode, as in k_query
+template <bool POS = false>
 __global__ void __launch_bounds__(HG_THREADS) k_query_huge(BriskParams P, RecSrc src, const u32* __restrict__ tags_binned, const u32* __restrict__ tags,
                                                            const PartDesc* __restrict__ desc, const u32* __restrict__ huge_list, const u32* __restrict__ n_huge, IndexDev ix,
-                                                           unsigned long long* __restrict__ per_read_sum) {
+                                                           unsigned long long* __restrict__ per_read_sum, const u64* __restrict__ anchors = nullptr,
+                                                           uint16_t* __restrict__ kout = nullptr, u64 kout_n = 0) {
+    __shared__ u64 s_pos[POS ? HG_THREADS : 1];
     __shared__ u64 s_ekey[2 * HQ_ENT];
     __shared__ u32 s_tab[HQ_TAB];
     __shared__ u32 s_pref[HG_THREADS + 1];
@@ -327,7 +367,13 @@ __global__ void __launch_bounds__(HG_THREADS) k_query_huge(BriskParams P, RecSrc
             }
             for (u32 rc = 0; rc < d.n_rec; rc += HG_THREADS) {  // the partition's records, one per lane; their instances spread over the lanes
                 const u32 avail = min(d.n_rec - rc, HG_THREADS);
-                const u32 my_n = tid < avail ? hdr_n(huge_rec(P, src, d, rc + tid)[P.nw]) : 0;
+                const u64 my_hdr = tid < avail ? huge_rec(P, src, d, rc + tid)[P.nw] : 0;
+                const u32 my_n = tid < avail ? hdr_n(my_hdr) : 0;
+                if (POS && tid < avail) {
+                    const u32 i = rc + tid;
+                    const u32 tag = !src.bin_cap ? tags[d.r_begin + i] : i < src.bin_cap ? tags_binned[(u64)d.part * src.bin_cap + i] : tags[d.r_begin + i - src.bin_cap];
+                    s_pos[tid] = pos_slot0(P, anchors[tag], hdr_idx0(my_hdr));
+                }
                 u32 ninst;
                 const u32 x = block_incl_scan(my_n, s_wsum, &ninst);
                 s_pref[tid + 1] = x;
@@ -352,14 +398,15 @@ __global__ void __launch_bounds__(HG_THREADS) k_query_huge(BriskParams P, RecSrc
                         if (v == EMPTY_SLOT) break;
                         const u32 e = v & 0xffffu;
                         if (s_ekey[2 * e] == key.lo && s_ekey[2 * e + 1] == key.hi) {
-                            if (v >> 16) atomicAdd(&s_rsum[lo], v >> 16);
+                            if (POS) pos_store(kout, kout_n, pos_slot(s_pos[lo], j), 0x100u | (v >> 16), ix.err);
+                            else if (v >> 16) atomicAdd(&s_rsum[lo], v >> 16);
                             break;
                         }
                         h = (h + 1) & (HQ_TAB - 1);
                     }
                 }
                 __syncthreads();
-                if (tid < avail && s_rsum[tid]) {
+                if (!POS && tid < avail && s_rsum[tid]) {
                     const u32 i = rc + tid;
                     u32 tag;
                     if (!src.bin_cap) tag = tags[d.r_begin + i];

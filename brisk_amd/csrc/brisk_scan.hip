@@ -229,7 +229,9 @@ template <> __device__ __forceinline__ u128x x_load<u128x>(const u32* __restrict
 // [p0, p0+n), vector reversed if `rev` (Kmers.cpp:554-556,597-599); idx_end is
 // the minimizer_idx of the LAST element of the returned vector.  `slot`: the first of superkmer_pieces() consecutive
 // slots (classic output); binned output takes its slots from the partitions' histogram counters.
-template <bool CLS, class T>  // CLS false: the caller knows there are no minimizer_idx classes (m >= 12); T: W4 or u128x
+template <bool CLS, class T, bool POS = false>  // CLS false: the caller knows there are no minimizer_idx classes (m >= 12); T: W4 or u128x
+// POS (per-position mode): `ret` is the record's slot anchor (pos_anchor); binned records store it beside their tag, and the tag
+// is then the record's own index in the binned layout (the anchor travels with the index, the tag with the record)
 __device__ __forceinline__ void emit_record_wide(const BriskParams& P, const u32* __restrict__ packed, u64 q0, u32 p0, u32 n, bool rev,
                                                  u32 idx_end, const ScanOut& out, u32 tag, u64 ret, unsigned long long slot) {
     const u32 L = P.k + n - 1;
@@ -280,7 +282,11 @@ __device__ __forceinline__ void emit_record_wide(const BriskParams& P, const u32
 #endif
             if (rank < out.bin_cap) {
                 r = out.bins + ((u64)part * out.bin_cap + rank) * P.stride;
-                if (out.tag) out.tag[(u64)part * out.bin_cap + rank] = tag;  // query mode: the records' reads, laid out like the records
+                if (POS) {
+                    const u64 ti = (u64)part * out.bin_cap + rank;
+                    out.tag[ti] = (u32)ti;
+                    out.ret[ti] = ret;
+                } else if (out.tag) out.tag[(u64)part * out.bin_cap + rank] = tag;  // query mode: the records' reads, laid out like the records
             } else {
                 const u32 reg = part & (OVF_REGIONS - 1);
                 const u32 at = atomicAdd(&out.ovf_cnt[reg], 1u);
@@ -290,7 +296,11 @@ __device__ __forceinline__ void emit_record_wide(const BriskParams& P, const u32
                 }
                 const u64 o = (u64)reg * out.ovf_region_cap + at;
                 r = out.ovf + o * P.stride;
-                if (out.tag) out.tag[((u64)out.bin_cap << P.part_bits) + o] = tag;
+                if (POS) {
+                    const u64 ti = ((u64)out.bin_cap << P.part_bits) + o;
+                    out.tag[ti] = (u32)ti;
+                    out.ret[ti] = ret;
+                } else if (out.tag) out.tag[((u64)out.bin_cap << P.part_bits) + o] = tag;
             }
         } else {
             r = out.rec + slot * P.stride;
@@ -317,7 +327,7 @@ __device__ __forceinline__ void emit_record_wide(const BriskParams& P, const u32
 #ifndef EMIT_SMALL
 #define EMIT_SMALL 1   // 0: every span through the 256-bit path (A/B)
 #endif
-template <bool CLS>
+template <bool CLS, bool POS = false>
 __device__ void emit_record_at(const BriskParams& P, const u32* __restrict__ packed, u64 q0, u32 p0, u32 n, bool rev,
                                u32 idx_end, const ScanOut& out, u32 tag, u64 ret, unsigned long long slot) {
     if (!out.bins && slot + superkmer_pieces<CLS>(P, n, idx_end) > out.cap) {
@@ -325,8 +335,8 @@ __device__ void emit_record_at(const BriskParams& P, const u32* __restrict__ pac
         return;
     }
     // (a vector has at most k - m + 1 k-mers: its span at most 2k - m nts.  Wave-uniform; folds where k and m are constants)
-    if (EMIT_SMALL && 2 * P.k - P.m <= 64) emit_record_wide<CLS, u128x>(P, packed, q0, p0, n, rev, idx_end, out, tag, ret, slot);
-    else emit_record_wide<CLS, W4>(P, packed, q0, p0, n, rev, idx_end, out, tag, ret, slot);
+    if (EMIT_SMALL && 2 * P.k - P.m <= 64) emit_record_wide<CLS, u128x, POS>(P, packed, q0, p0, n, rev, idx_end, out, tag, ret, slot);
+    else emit_record_wide<CLS, W4, POS>(P, packed, q0, p0, n, rev, idx_end, out, tag, ret, slot);
 }
 __device__ void emit_record(const BriskParams& P, const u32* __restrict__ packed, u64 q0, u32 p0, u32 n, bool rev,
                             u32 idx_end, const ScanOut& out, u32 tag, u64 ret = 0) {
@@ -582,6 +592,10 @@ struct ChunkCtl {
     ChunkState* spec;      // [n_chunks]   state a speculative chunk reached at its emit_from
     ChunkState* truth;     // [n_chunks+1] state the previous chunk had at the same step; seed of a seeded chunk
     u32 long_limit;        // whole-read launch: skip reads with more k-mers than this (0: none)
+    // per-position mode (k_scan2 MODE 3 / 4, brisk_hip_get_kmers): slot_base[tag] = the slot of the tag's read's first k-mer minus
+    // the stream index of that read's first nt (mod 2^64), so that slot_base[tag] + a stream index is the slot of the k-mer there.
+    // (Here rather than in ScanOut: the other modes' kernel arguments keep their offsets.)
+    const u64* slot_base;
 };
 #define CHUNK_EXACT 1u      // chunk status bits
 #define CHUNK_RERUN 2u      // its speculative records are void, a seeded scan replaced them
@@ -723,6 +737,95 @@ __global__ void __launch_bounds__(256) k_filter_records(BriskParams P, const u64
     for (u32 j = 0; j < P.stride; j++) out[slot * P.stride + j] = rec[i * P.stride + j];
 }
 
+// ---- per-position mode (brisk_hip_get_kmers): where every record's k-mers go in the output ----------------------------------
+// Slot bases of a batch: read r owns max(0, len_r - k + 1) slots from base_r = the sum over the reads before it.  slot_base[r] =
+// base_r - starts[r] (mod 2^64): the scan adds a stream index to it (ScanOut::slot_base).  64-bit throughout (50 M reads of 150 bp at
+// k = 63 are 4.4 G slots), hence these siblings of k_psum_* (which count records per partition in 32 bits).
+#define SLOT_ITEMS 16
+__device__ __forceinline__ u64 read_slots(const u64* __restrict__ starts, u64 r, u32 k) {
+    const u64 len = starts[r + 1] - starts[r];
+    return len >= k ? len - k + 1 : 0;
+}
+__global__ void __launch_bounds__(256) k_slot_block(const u64* __restrict__ starts, u64 n_reads, u32 k, u64* __restrict__ block_sums) {
+    __shared__ u64 s[4];
+    const u64 base = (u64)blockIdx.x * 256 * SLOT_ITEMS;
+    u64 acc = 0;
+    for (int i = 0; i < SLOT_ITEMS; i++) {
+        const u64 r = base + (u64)i * 256 + threadIdx.x;
+        if (r < n_reads) acc += read_slots(starts, r, k);
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+}
+// single block: in-place exclusive scan of block_sums[nb]; block_sums[nb] = the total
+__global__ void __launch_bounds__(1024) k_slot_top(u64* __restrict__ block_sums, u32 nb) {
+    __shared__ u64 s_wave[16];
+    __shared__ u64 s_carry;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (u32 base = 0; base < nb; base += 1024) {
+        const u32 i = base + threadIdx.x;
+        const u64 v = i < nb ? block_sums[i] : 0;
+        u64 x = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            const u64 y = __shfl_up(x, o, 64);
+            if ((int)(threadIdx.x & 63) >= o) x += y;
+        }
+        if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = x;
+        __syncthreads();
+        u64 woff = 0;
+        for (u32 j = 0; j < (threadIdx.x >> 6); j++) woff += s_wave[j];
+        const u64 carry = s_carry;
+        if (i < nb) block_sums[i] = carry + woff + x - v;
+        __syncthreads();
+        if (threadIdx.x == 1023) s_carry = carry + woff + x;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_sums[nb] = s_carry;
+}
+__global__ void __launch_bounds__(256) k_slot_apply(const u64* __restrict__ starts, u64 n_reads, u32 k, const u64* __restrict__ block_sums,
+                                                    u64* __restrict__ slot_base) {
+    __shared__ u64 s_wave[4];
+    const u64 base = (u64)blockIdx.x * 256 * SLOT_ITEMS + (u64)threadIdx.x * SLOT_ITEMS;
+    u64 tsum = 0;
+    for (int i = 0; i < SLOT_ITEMS; i++)
+        if (base + i < n_reads) tsum += read_slots(starts, base + i, k);
+    u64 x = tsum;
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 y = __shfl_up(x, o, 64);
+        if ((int)(threadIdx.x & 63) >= o) x += y;
+    }
+    if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = x;
+    __syncthreads();
+    u64 woff = 0;
+    for (u32 j = 0; j < (threadIdx.x >> 6); j++) woff += s_wave[j];
+    u64 run = block_sums[blockIdx.x] + woff + x - tsum;
+    for (int i = 0; i < SLOT_ITEMS; i++) {
+        const u64 r = base + i;
+        if (r >= n_reads) break;
+        slot_base[r] = run - starts[r];
+        run += read_slots(starts, r, k);
+    }
+}
+// a chunk's records carry its chunk slot as their tag: the slot base of its sequence, per chunk
+__global__ void __launch_bounds__(256) k_chunk_slot_base(const VRead* __restrict__ vreads, u32 n_chunks, const u64* __restrict__ slot_base, u64* __restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_chunks) out[i] = slot_base[vreads[i].read];
+}
+// keep the records (and their anchors) of the chunks that were not re-scanned: [first, n_spec_end) speculative, [n_spec_end, n_rec) seeded
+__global__ void __launch_bounds__(256) k_pos_filter(BriskParams P, const u64* __restrict__ rec, const u64* __restrict__ anchor, const u32* __restrict__ tags, u64 first,
+                                                    u64 n_spec_end, u64 n_rec, const u32* __restrict__ status, u64* __restrict__ out, u64* __restrict__ anchor_out,
+                                                    unsigned long long* __restrict__ n_out) {
+    const u64 i = first + (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rec) return;
+    if (i < n_spec_end && (status[tags[i]] & CHUNK_RERUN)) return;
+    const unsigned long long o = atomicAdd(n_out, 1ull);
+    for (u32 j = 0; j < P.stride; j++) out[o * P.stride + j] = rec[i * P.stride + j];
+    anchor_out[o] = anchor[i];
+}
+
 // closed form of get_minimizer's fold (Kmers.cpp:377-405) given the first and last window
 // holding the minimum key, their `reversed` flags and K-m
 __device__ __forceinline__ void resolve_ties(u32 first, u32 last, bool rev_first, bool rev_last, u32 Km, bool canon_if_needed_known, bool canon,
@@ -742,15 +845,25 @@ __device__ __forceinline__ void resolve_ties(u32 first, u32 last, bool rev_first
     }
 }
 
+// Slot anchor of a vector (per-position mode): where its minimizer starts, as a slot number, | reversed << 63.  A forward k-mer
+// holds its minimizer at suffix offset minimizer_idx, so it starts at a + minimizer_idx - w; a k-mer whose minimizer is on the
+// reverse strand is stored reverse-complemented and starts at a - minimizer_idx (pos_slot0 in brisk_readout.hip).  q: stream
+// index of the vector's first k-mer (the one that comes first along the read), n k-mers, idx_end as in emit_record_wide.
+__device__ __forceinline__ u64 pos_anchor(const BriskParams& P, u64 slot_base, u64 q, u32 n, bool rev, u32 idx_end) {
+    const u64 g = rev ? q + idx_end : q + P.w - idx_end + n - 1;
+    return (slot_base + g) | (rev ? 1ull << 63 : 0ull);
+}
+
 // Emit queue entry (one u64 per closed super-k-mer): low word = the step (k-mer index in the lane's read) of its first
 // k-mer; high word = n | idx_end << 8 | reversed << 16 | (returned minimizer == 0) << 17 | lane << 18.  The lane's read
 // (stream index of its first nt, and its tag) is looked up in the wave's s_q0 / s_tag when the record is built.
-template <bool CLS>
+template <bool CLS, bool POS = false>
 __device__ __forceinline__ void emit_queued(const BriskParams& P, const u32* __restrict__ packed, const ScanOut& out, u64 ent, const u64* s_q0, const u32* s_tag,
-                                            unsigned long long slot) {
+                                            unsigned long long slot, const u64* slot_base) {
     const u32 mi = (u32)(ent >> 32), src = (mi >> 18) & 63u;
     const u64 q_start = s_q0[src] + (u32)ent;
-    emit_record_at<CLS>(P, packed, q_start, 0, mi & 0xff, (mi >> 16) & 1, (mi >> 8) & 0xff, out, s_tag[src], q_start | ((u64)((mi >> 17) & 1) << 63), slot);
+    const u64 ret = POS ? pos_anchor(P, slot_base[s_tag[src]], q_start, mi & 0xff, (mi >> 16) & 1, (mi >> 8) & 0xff) : q_start | ((u64)((mi >> 17) & 1) << 63);
+    emit_record_at<CLS, POS>(P, packed, q_start, 0, mi & 0xff, (mi >> 16) & 1, (mi >> 8) & 0xff, out, s_tag[src], ret, slot);
 }
 
 // records the wave's queued super-k-mers become
@@ -766,12 +879,12 @@ __device__ __forceinline__ u32 queue_records(const BriskParams& P, const u64* q_
     return mine;
 }
 // the queue's records into slots [base, base + queue_records())
-template <bool CLS>
+template <bool CLS, bool POS = false>  // slot_base: ChunkCtl::slot_base (POS only)
 __device__ __forceinline__ void emit_queue(const BriskParams& P, const u32* __restrict__ packed, const ScanOut& out, const u64* q_ent, const u64* s_q0, const u32* s_tag,
-                                           u32 qcount, unsigned long long base) {
+                                           u32 qcount, unsigned long long base, const u64* slot_base = nullptr) {
     const u32 lane = threadIdx.x & 63;
     if (!(CLS ? P.cls_bits : 0u)) {
-        for (u32 e = lane; e < qcount; e += 64) emit_queued<CLS>(P, packed, out, q_ent[e], s_q0, s_tag, base + e);
+        for (u32 e = lane; e < qcount; e += 64) emit_queued<CLS, POS>(P, packed, out, q_ent[e], s_q0, s_tag, base + e, slot_base);
         return;
     }
     for (u32 e0 = 0; e0 < qcount; e0 += 64) {  // wave-uniform: the slots of 64 entries from an inclusive scan of their piece counts
@@ -788,20 +901,20 @@ __device__ __forceinline__ void emit_queue(const BriskParams& P, const u32* __re
             const u32 y = __shfl_up(incl, o, 64);
             if ((int)lane >= o) incl += y;
         }
-        if (e < qcount) emit_queued<CLS>(P, packed, out, ent, s_q0, s_tag, base + incl - np);
+        if (e < qcount) emit_queued<CLS, POS>(P, packed, out, ent, s_q0, s_tag, base + incl - np, slot_base);
         base += (u32)__shfl(incl, 63, 64);
     }
 }
 
 // what is left in the waves' queues when their reads end: one slot reservation for the whole block
-template <bool CLS>
+template <bool CLS, bool POS = false>
 __device__ __forceinline__ void scan_final_flush(const BriskParams& P, const u32* __restrict__ packed, const ScanOut& out, const u64* q_ent, const u64* s_q0,
-                                                 const u32* s_tag, u32 qcount, u32* s_wcnt, unsigned long long* s_wbase) {
+                                                 const u32* s_tag, u32 qcount, u32* s_wcnt, unsigned long long* s_wbase, const u64* slot_base = nullptr) {
     const u32 lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const u32 n_mine = queue_records<CLS>(P, q_ent, qcount);
     if (out.bins) {  // binned records need no slots: no reservation, no barrier
         if (lane == 0 && n_mine) atomicAdd(out.n_rec, (unsigned long long)n_mine);
-        emit_queue<CLS>(P, packed, out, q_ent, s_q0, s_tag, qcount, 0);
+        emit_queue<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, qcount, 0, slot_base);
         return;
     }
     if (lane == 0) s_wcnt[wid] = n_mine;
@@ -814,7 +927,7 @@ __device__ __forceinline__ void scan_final_flush(const BriskParams& P, const u32
     __syncthreads();
     unsigned long long base = *s_wbase;
     for (u32 i = 0; i < wid; i++) base += s_wcnt[i];
-    emit_queue<CLS>(P, packed, out, q_ent, s_q0, s_tag, qcount, base);
+    emit_queue<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, qcount, base, slot_base);
 }
 
 // minimum of x over the lane's 16-lane row, in every lane of the row (DPP row rotations: one instruction per step)
@@ -894,7 +1007,8 @@ __device__ unsigned long long g_scan_cnt[8];  // [0] wave-steps [1] expiries [2]
 #define SCNT(i, v)
 #endif
 
-// MODE 0: reads, insert; 1: reads, query (stops a read at a returned minimizer of 0); 2: virtual reads (chunks of long sequences)
+// MODE 0: reads, insert; 1: reads, query (stops a read at a returned minimizer of 0); 2: virtual reads (chunks of long sequences);
+// 3 / 4: reads / virtual reads in per-position mode (brisk_hip_get_kmers): the insert's records, each with its slot anchor in out.ret
 // KK, MM: k and m as compile-time constants for the common parameter sets (0: from P) -- folds the shifts and masks and,
 // above all, frees scalar registers: the generic kernel spills 70+ of them into vector lanes and pays a v_readlane per use
 // Waves per SIMD the kernel is compiled for: six (three 8-wave blocks per CU, 80 registers) where k and m are compile-time
@@ -907,7 +1021,7 @@ __host__ __device__ constexpr int scan_waves_per_eu(int KK, int MM) { return KK 
 template <int NCH, int MODE, int KK, int MM>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_waves_per_eu(KK, MM), 8))) k_scan2(BriskParams P, ScanCfg cfg, const u32* __restrict__ packed, const u64* __restrict__ starts,
                                                 u64 n_reads, const double* __restrict__ g_tabs, ScanOut out, ChunkCtl cc) {
-    constexpr bool VR = MODE == 2, query_mode = MODE == 1;
+    constexpr bool VR = MODE == 2 || MODE == 4, query_mode = MODE == 1, POS = MODE >= 3;
     constexpr bool CLS = MM < 12;  // minimizer_idx classes in the routing id exist only where 2m < 24 (brisk_hip_create)
     extern __shared__ double smem_d[];
     const double* s_coef = smem_d;                        // 128
@@ -965,7 +1079,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
         max_nk = y > max_nk ? y : max_nk;
     }
     if (max_nk == 0) {  // nothing to scan in this wave; it still takes part in the block's final reservation
-        scan_final_flush<CLS>(P, packed, out, q_ent, s_q0, s_tag, 0, s_wcnt, s_wbase);
+        scan_final_flush<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, 0, s_wcnt, s_wbase, cc.slot_base);
         return;
     }
     const u64 KEY0 = order_key_fast<NCH, MM>(0, m, M, cfg, s_tabs, s_coef);
@@ -1282,7 +1396,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
                 if (lane == 0) base = atomicAdd(out.n_rec, (unsigned long long)n_out);
                 base = read_lane_u64(base, 0);
             }
-            emit_queue<CLS>(P, packed, out, q_ent, s_q0, s_tag, qcount, base);
+            emit_queue<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, qcount, base, cc.slot_base);
 #endif
             qcount = 0;
         }
@@ -1308,5 +1422,5 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
 #ifdef SCAN_ATTR_NOEMIT
     qcount = 0;
 #endif
-    scan_final_flush<CLS>(P, packed, out, q_ent, s_q0, s_tag, qcount, s_wcnt, s_wbase);
+    scan_final_flush<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, qcount, s_wcnt, s_wbase, cc.slot_base);
 }

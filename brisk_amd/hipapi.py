@@ -101,7 +101,7 @@ SYMBOLS = [
     "brisk_hip_abi_version", "brisk_hip_create", "brisk_hip_destroy", "brisk_hip_clear", "brisk_hip_last_error", "brisk_hip_sync",
     "brisk_hip_get_layout", "brisk_hip_insert_reads", "brisk_hip_insert_packed", "brisk_hip_get_reads", "brisk_hip_lookup",
     "brisk_hip_enumerate", "brisk_hip_stats", "brisk_hip_memory_info", "brisk_hip_insert_slack", "brisk_hip_reallocate", "brisk_hip_checksum", "brisk_hip_scan_packed", "brisk_hip_scan_bound", "brisk_hip_route_records",
-    "brisk_hip_get_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
+    "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
     "brisk_hip_enumerate_ids", "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
 ]
@@ -131,6 +131,9 @@ def load() -> C.CDLL:
     L.brisk_hip_get_packed.argtypes = [vp, vp, vp, u64, vp]
     L.brisk_hip_get_reads.argtypes = [vp, _u8p, _u64p, u64, _u64p]
     L.brisk_hip_lookup.argtypes = [vp, _u64p, _u64p, _u8p, u64, _u8p, _u8p]
+    _u16p = np.ctypeslib.ndpointer(dtype=np.uint16, flags="C_CONTIGUOUS")
+    L.brisk_hip_get_kmers.argtypes = [vp, _u8p, _u64p, u64, _u16p, u64]
+    L.brisk_hip_get_kmers_packed.argtypes = [vp, vp, vp, u64, vp]
     L.brisk_hip_enumerate.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64)]
     L.brisk_hip_stats.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.brisk_hip_checksum.argtypes = [vp, _u64p]
@@ -173,6 +176,17 @@ def _pack_reads(seqs) -> Tuple[np.ndarray, np.ndarray]:
         offs[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
     flat = np.frombuffer(b"".join(bs), dtype=np.uint8).copy() if bs else np.zeros(0, np.uint8)
     return np.ascontiguousarray(flat), offs
+
+
+def kmer_slots(offsets, k: int) -> np.ndarray:
+    """Slot bases of brisk_hip_get_kmers: read r of the read table `offsets` (n_reads + 1 ascending nucleotide offsets) owns
+    max(0, len_r - k + 1) slots from base[r]; base[n_reads] is the total, what `out` must hold."""
+    offs = np.asarray(offsets, dtype=np.uint64)
+    lens = (offs[1:] - offs[:-1]).astype(np.int64)
+    base = np.zeros(len(offs), dtype=np.uint64)
+    if len(lens):
+        base[1:] = np.cumsum(np.maximum(lens - (k - 1), 0), dtype=np.uint64)
+    return base
 
 
 _live = weakref.WeakSet()
@@ -252,6 +266,19 @@ class BriskHip:
         self._chk(self.L.brisk_hip_get_reads(self.h, flat, offs, len(offs) - 1, out))
         return out
 
+    def get_kmers(self, seqs: Sequence) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The count at every k-mer position (brisk_hip_get_kmers): counts uint8[n_slots] (mod 256), found bool[n_slots],
+        base uint64[n_reads + 1] -- the k-mer at nucleotide i of read r is slot base[r] + i."""
+        flat, offs = _pack_reads(seqs)
+        base = kmer_slots(offs, self.k)
+        total = int(base[-1])
+        out = np.zeros(max(total, 1), np.uint16)
+        if len(flat) == 0:
+            flat = np.zeros(1, np.uint8)
+        self._chk(self.L.brisk_hip_get_kmers(self.h, flat, offs, len(offs) - 1, out, total))
+        out = out[:total]
+        return (out & 0xff).astype(np.uint8), (out & 0x100) != 0, base
+
     def lookup(self, lo, hi, idx) -> Tuple[np.ndarray, np.ndarray]:
         lo = np.ascontiguousarray(lo, np.uint64)
         hi = np.ascontiguousarray(hi, np.uint64)
@@ -325,6 +352,10 @@ class BriskHip:
     def get_packed(self, d_packed: int, d_starts: int, n_reads: int, d_sums: int):
         """per-read sums of counts (query_sequence), reads and sums on the device"""
         self._chk(self.L.brisk_hip_get_packed(self.h, d_packed, d_starts, n_reads, d_sums))
+
+    def get_kmers_packed(self, d_packed: int, d_starts: int, n_reads: int, d_out: int):
+        """per-k-mer answers (brisk_hip_get_kmers), reads and uint16 slots on the device (d_out sized by kmer_slots)"""
+        self._chk(self.L.brisk_hip_get_kmers_packed(self.h, d_packed, d_starts, n_reads, d_out))
 
     def scan_bound(self, d_starts: int, n_reads: int) -> int:
         out = C.c_uint64()

@@ -42,6 +42,10 @@
  *                               query_sequence (apps/counter.cpp:281-310) over
  *                               Brisk::get_superkmer (brisk/Brisk.hpp:102-118) /
  *                               Brisk::get_sequence (brisk/Brisk.hpp:28); _packed: reads and sums on the device
+ *   brisk_hip_get_kmers / brisk_hip_get_kmers_packed
+ *                               Brisk::get_sequence (brisk/Brisk.hpp:28: one DATA* per k-mer of the sequence;
+ *                               declared, never defined) as Brisk::get_superkmer (brisk/Brisk.hpp:102-118) over
+ *                               every vector SuperKmerEnumerator yields; _packed: reads and answers on the device
  *   brisk_hip_lookup            Brisk::get (brisk/Brisk.hpp:64-69)
  *   brisk_hip_enumerate         Brisk::next / restart_kmer_enumeration
  *                               (brisk/Brisk.hpp:166-179, brisk/DenseMenuYo.hpp:476-521)
@@ -179,6 +183,23 @@ int brisk_hip_get_reads(brisk_hip_index *h, const char *bases, const uint64_t *o
 /* the same with reads and sums resident on the device (layout of brisk_hip_insert_packed; d_per_read_sum[n_reads]) */
 int brisk_hip_get_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
                          uint64_t *d_per_read_sum);
+
+/* Per-k-mer get: the count at every k-mer position of every read.  Reads as for brisk_hip_get_reads (clean sequences; a read
+ * shorter than k contributes nothing).  Read r owns max(0, len_r - k + 1) slots, starting at base_r = the sum of the earlier
+ * reads' slots (64-bit: 50 M reads at k = 63 are 4.4 G slots); slot base_r + i is the k-mer that starts at nucleotide i of read
+ * r.  A slot holds 0 when the k-mer is absent and 0x100 | count when it is present (the count is kept mod 256, so a present
+ * k-mer can have count 0: the 0x100 bit says it is there).  A k-mer is looked up under the (kmer_s, minimizer_idx) that
+ * SuperKmerEnumerator gives it while scanning the WHOLE read -- the identity brisk_hip_insert_reads stored; minimizer ties make
+ * it depend on the context, so it is not always the identity of the k-mer enumerated on its own.  Every slot of every read is
+ * answered: the stop of brisk_hip_get_reads at a returned minimizer of 0 (counter.cpp:304-306) belongs to that per-read sum,
+ * not to get_superkmer.  Pending deferred inserts are completed first.  The answer does not depend on max_batch_reads, on how
+ * the call is batched or on which kernels run.  EINVAL on a sharded index (n_owners > 1) and on an entry-id index. */
+/* HOST reads (layout of brisk_hip_get_reads); out[cap] HOST.  BRISK_HIP_ECAPACITY, nothing written, if cap < total slots. */
+int brisk_hip_get_kmers(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
+                        uint16_t *out, uint64_t cap);
+/* DEVICE reads (layout of brisk_hip_insert_packed); d_out DEVICE, sized to the total slots. */
+int brisk_hip_get_kmers_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                               uint16_t *d_out);
 
 /* point lookups of UNHASHED (kmer_s, minimizer_idx) pairs, as Brisk::get takes them.
  * HOST arrays; out_found[i] in {0,1}; out_data[i] valid when found. */
