@@ -298,9 +298,11 @@ struct LaneInst {
     u32 hh[NIMAX];
     u32 won;
 };
-template <u32 NI, u32 NW, u32 KB, u32 SHIFT, u32 NIMAX>
-__device__ __forceinline__ void expand_and_dedupe_words(u32 lane, u32 ninst, u32 tsize, const u32* s_rw, const uint8_t* s_irec, const u32* s_rmult,
-                                                        u64* s_key, u32* s_tab, u32* dbg_rounds, LaneInst<NIMAX>& li) {
+// s_imult: every instance slot's multiplicity, mod 256 (the chunk's records folded: section 4 finding 15)
+// (FOLD false: s_rmult, per record)
+template <u32 NI, u32 NW, u32 KB, u32 SHIFT, u32 NIMAX, bool FOLD>
+__device__ __forceinline__ void expand_and_dedupe_words(u32 lane, u32 ninst, u32 tsize, const u32* s_rw, const uint8_t* s_irec, const uint8_t* s_imult,
+                                                        const u32* s_rmult, u64* s_key, u32* s_tab, u32* dbg_rounds, LaneInst<NIMAX>& li) {
     constexpr u32 RS = RecGeom<NW>::RS, INFO = RecGeom<NW>::INFO, KBITS = 2 * KB + 6;
     static_assert(KBITS + SHIFT <= 128 && SHIFT <= 6, "entry key: [routing id low bits | compacted k-mer | idx']");
     static_assert(NI <= NIMAX, "instances per lane");
@@ -345,7 +347,8 @@ __device__ __forceinline__ void expand_and_dedupe_words(u32 lane, u32 ninst, u32
         klo[it] = lo;
         khi[it] = hi;
         hh[it] = hash_key32(mk128(lo, hi)) & (tsize - 1);
-        mult[it] = (s_rmult[rix[it]] & 0xffu) << WI_CNT_SHIFT;  // counts wrap at 256: so may the multiplicities
+        // counts wrap at 256: so may the multiplicities
+        mult[it] = FOLD ? (u32)s_imult[i < ninst ? i : 0] << WI_CNT_SHIFT : (s_rmult[rix[it]] & 0xffu) << WI_CNT_SHIFT;
         if (i < ninst) {
             s_key[2 * i] = lo;
             s_key[2 * i + 1] = hi;
@@ -429,6 +432,80 @@ __device__ __forceinline__ bool dedupe_records(u32 stride, const RecRegs& rr, u3
     return dup;
 }
 
+// ---- Containment fold of a chunk's records (insert_body's FOLD bodies, DESIGN.md section 4 finding 15).  Record B is contained
+// in record A when their routing ids are equal, A's idx' range holds B's and B's compacted string is the matching part of
+// A's: then every key of B is the key of A with the same idx', bit for bit, whatever the data.  A contained record is not
+// expanded; its k-mers' multiplicity is added over the range of its leader's instance slots.  The strings are compared in a
+// frame common to all records: the k-mer of idx' t starts at nucleotide E - 1 - t (E = suff_reduc + k - m + 1 bounds every
+// record's idx0' + n), so record R's string sits shifted left by 2(E - idx0'_R - n_R) bits, and "B in A" is
+// (U_A & M_B) == U_B with M_B the ones over B's nucleotides -- no shift per pair.  The frame is 2k - m - b nucleotides wide:
+// it fits the record's words.
+#ifndef WI_FOLD_TRIPS
+#define WI_FOLD_TRIPS 16u   // heads per chunk at most (a wave-wide round each); records still open after them stay unfolded
+#endif
+struct FoldFrame {
+    W4 u, m;    // the record's string in the common frame, and the ones over its nucleotides (NW words used)
+    u32 rid;    // routing id
+    u32 rng;    // idx0' | (idx0' + n) << 8
+    u32 s;      // (n << 6) | (63 - lane): the order heads are taken in (0: the record takes no part)
+};
+template <u32 NW, u32 KB>
+__device__ __forceinline__ FoldFrame fold_frame(const RecRegs& rr, u64 hdr, u32 n, bool valid, u32 frame_end, u32 lane) {
+    FoldFrame f;
+    const u32 idx0 = hdr_idx0(hdr), end = idx0 + n, top = frame_end - idx0 + KB - 1;  // nucleotides below the string's top
+    // (a record outside the frame -- none the scan emits -- takes no part: it is expanded on its own)
+    const bool ok = valid && n > 0 && end <= frame_end && top <= 32 * NW;
+    const u32 lo_bits = ok ? 2 * (frame_end - end) : 0, hi_bits = ok ? 2 * top : 0;
+    f.m = w4_andn(w4_mask(hi_bits), w4_mask(lo_bits));
+    f.u = w4_and(w4_shl(W4{rr.w0, NW > 1 ? rr.w1 : 0, NW > 2 ? rr.w2 : 0, NW > 3 ? rr.w3 : 0}, lo_bits), f.m);
+    f.rid = hdr_bucket(hdr);
+    f.rng = idx0 | (end << 8);
+    f.s = ok ? (n << 6) | (63 - lane) : 0;
+    return f;
+}
+__device__ __forceinline__ u64 readlane64(u64 v, u32 a) {
+    return ((u64)(u32)__builtin_amdgcn_readlane((int)(v >> 32), (int)a) << 32) | (u32)__builtin_amdgcn_readlane((int)v, (int)a);
+}
+// Folds the records of lanes < nrec.  Heads are taken in decreasing (n, -lane) among the records still open, one wave-wide
+// round each: the head is maximal (a record containing it would be larger, and open: what contains a folded record contains
+// its head too), and every open record it contains folds into it.  Returns whether this lane's record folded; *lead: the
+// lane of its head (its own lane otherwise), *off: its idx0' minus the head's.  Identical records fold into the lowest lane
+// of them, so no separate record-level de-duplication is needed.
+template <u32 NW>
+__device__ __forceinline__ bool fold_records(const FoldFrame& f, u32 nrec, u32 lane, u32* lead, u32* off, u32* trips) {
+    u32 sv = lane < nrec ? f.s : 0;
+    bool folded = false;
+    *lead = lane;
+    *off = 0;
+    for (u32 t = 0; t < WI_FOLD_TRIPS; t++) {
+        const u32 smax = (u32)__builtin_amdgcn_readlane((int)wave_incl_max_scan(sv), 63);
+        if (smax == 0) break;
+        *trips += 1;
+        const u32 a = 63 - (smax & 63);
+        const u32 rid_a = (u32)__builtin_amdgcn_readlane((int)f.rid, (int)a), rng_a = (u32)__builtin_amdgcn_readlane((int)f.rng, (int)a);
+        const u32 i0 = f.rng & 0xffu, e = f.rng >> 8, i0a = rng_a & 0xffu, ea = rng_a >> 8;
+#ifdef BRISK_NO_RECORD_FOLD  // A/B: identical records only (what the record-level de-duplication collapsed)
+        bool in = sv != 0 && rid_a == f.rid && i0a == i0 && ea == e;
+#else
+        bool in = sv != 0 && rid_a == f.rid && i0a <= i0 && e <= ea;
+#endif
+        bool same = (readlane64(f.u.w0, a) & f.m.w0) == f.u.w0;
+        if (NW > 1) same = same & ((readlane64(f.u.w1, a) & f.m.w1) == f.u.w1);
+        if (NW > 2) same = same & ((readlane64(f.u.w2, a) & f.m.w2) == f.u.w2);
+        if (NW > 3) same = same & ((readlane64(f.u.w3, a) & f.m.w3) == f.u.w3);
+        in = in && same;
+        if (in) {  // (the head itself closes here, unfolded)
+            sv = 0;
+            if (lane != a) {
+                folded = true;
+                *lead = a;
+                *off = i0 - i0a;
+            }
+        }
+    }
+    return folded;
+}
+
 // MAXI: k-mer instances per chunk.  256 (10 KB of LDS, 128 registers: 4 waves per SIMD) for the usual partitions of a
 // few hundred instances; 512 (2 waves per SIMD) when partitions are big -- few distinct minimizers, as with m <= 11 --
 // and the passes over a partition's entries saved by half as many chunks outweigh the occupancy.
@@ -450,6 +527,9 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
     }
     constexpr u32 TABLE = 2 * MAXI, TS = TABLE / 64, NI = MAXI / 64;
     constexpr u32 KW = NW ? (2 * KB + 6 + SHIFT <= 64 ? 1u : 2u) : 0u;  // words of a stored key (0: ix.key_words)
+    // The containment fold (fold_records) where it measured faster: k63 (three record words) in chunks of 256 instances.
+    // At k31 (k31 m15 b14, k31 m11 b11 in the 512-instance body) its rounds cost more than the instances they save.
+    constexpr bool FOLD = NW >= 3 && MAXI == WI_MAX_INST;
     static_assert(MAXI % 256 == 0 && MAXI <= 1024, "chunk size: whole 32-bit words of record marks per lane, 10-bit instance index");
     // LDS of one wave, one buffer cut into regions.  k_insert's throughput follows the number of resident waves almost
     // linearly (4096 -> 30.8 ms, 3072 -> 38.3, 2048 -> 54.2, 1024 -> 103.6 per 50 M reads: every wave is a serial chain of
@@ -470,6 +550,7 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
     constexpr u32 LDS_BYTES = NW ? OFF_PREF : OFF_PREF + 4 * (WI_MAX_REC + 1) + 4;
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[LDS_BYTES];
     u64* s_key = (u64*)s_mem;
+    u32* s_idiff = (u32*)s_mem;  // FOLD: [MAXI] the instances' multiplicity steps, over the first quarter of s_key (instance map)
     u64* s_rec = (u64*)(s_mem + OFF_REC);
     u32* s_rw = (u32*)s_rec;
     u32* s_tab = (u32*)(s_mem + OFF_TAB);
@@ -477,6 +558,8 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
     u32* s_rtab = (u32*)(s_mem + OFF_RTAB);
     u32* s_rmult = (u32*)(s_mem + OFF_RMULT);
     uint8_t* s_irec = s_mem + OFF_IREC;
+    uint8_t* s_imult = s_mem + OFF_RTAB;  // FOLD: [MAXI] the instances' multiplicities mod 256 (instance map .. expand), over s_rtab
+    static_assert(NW == 0 || MAXI <= 4 * 2 * WI_MAX_REC, "instance multiplicities fit the record table's bytes");
     u32* s_pref = (u32*)(s_mem + (NW ? 0 : OFF_PREF));  // generic body only
 
     const u32 lane = threadIdx.x;
@@ -580,7 +663,7 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                 const u32 avail = min(r_end - rc, (u32)WI_MAX_REC);
                 if (rc != d.r_begin) rr = load_part_recs(P, src, part, d.r_begin, rc, avail, lane);
                 wave_sync();
-                if (lane < avail) {
+                if (!FOLD && lane < avail) {  // (the record-level pass reads them here; the fold works from registers)
                     u64* dst = s_rec + lane * P.stride;
                     dst[0] = rr.w0;
                     dst[1] = rr.w1;
@@ -601,9 +684,22 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                 // it: hence the loop), at the latest to the raw-count prefix, which always fits.
                 const u32 rawfit = (u32)__popcll(__ballot(lane < avail && x0 <= MAXI));  // >= 1; a prefix: x0 is monotone
                 u32 nrec = avail, my_n = 0, x = 0, ninst = 0;
+                // FOLD: records contained in others (identical ones included) fold into them instead (fold_records):
+                // 185 -> ~85 instances per partition at k63 m21 b14 (section 4 finding 15).
+                u32 lead = lane, lead_off = 0, dbg_trips = 0;
+                FoldFrame ff{};
+                // FOLD: the records as 32-bit words of C << 6 (expand_and_dedupe_words) right away, their info words once the
+                // prefix is known: the record registers are dead from here on
+                const u32 info_hi = (raw_n << 10) | (hdr_idx0(my_hdr) << 18) | ((hdr_bucket(my_hdr) & ((1u << SHIFT) - 1)) << 26);
+                if (FOLD) {
+                    ff = fold_frame<NW ? NW : 1, KB>(rr, my_hdr, raw_n, lane < avail, P.suff_reduc + P.w + 1, lane);
+                    if (lane < avail) store_rec_words<NW ? NW : 1>(s_rw + lane * RecGeom<NW ? NW : 1>::RS, rr, 0);
+                }
                 for (int attempt = 0;; attempt++) {
                     CNT(2, 1)
-                    const bool dup = dedupe_records(P.stride, rr, my_mult, nrec, lane, s_rec, s_rtab, s_rmult);
+                    bool dup;
+                    if (FOLD) dup = fold_records<NW ? NW : 1>(ff, nrec, lane, &lead, &lead_off, &dbg_trips);
+                    else dup = dedupe_records(P.stride, rr, my_mult, nrec, lane, s_rec, s_rtab, s_rmult);
                     my_n = (lane < nrec && !dup) ? raw_n : 0;
                     x = wave_incl_scan(my_n, lane);
                     ninst = __shfl(x, 63, 64);
@@ -614,6 +710,11 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                 }
                 PHASE(1)
                 const u32 raw_inst = __shfl(x0, nrec - 1, 64);
+                CNT(9, raw_inst)
+                CNT(10, FOLD ? (u32)__popcll(__ballot(lane < nrec && my_n == 0 && raw_n != 0)) : 0u)
+                CNT(11, dbg_trips)
+                // where this record's k-mers sit on the instance line: its own slots, or its head's from its idx0' on
+                const u32 m_first = FOLD ? (u32)__shfl(x - my_n, lead, 64) + lead_off : 0u;
                 // (a quarter full at most in instances, less in distinct keys: probe rounds are wave-wide -- every round costs all 64 lanes
                 // whoever is still probing -- so a sparser table is worth its clearing: 25.8 -> 25.0 ms per 50 M reads against half full.
                 // Skipping, by a scalar branch, the instance slots nobody is pending in lost: 28.7 ms -- seven more spilled registers)
@@ -630,17 +731,42 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                 {
                     // instance -> record: each record marks its first instance, a running maximum spreads the marks
                     // (records lie in lane order).  Every lane owns MAXI/64 consecutive instances here.
+                    // FOLD, in the same rounds: every instance's multiplicity.  Each record adds its own
+                    // at the start of its range and takes it off at the end; a prefix sum over the slots (the lane's NI,
+                    // then the wave) adds up the records over every slot.  u32, wrapping: only the low 8 bits count.
                     u32* irec32 = (u32*)s_irec;
 #pragma unroll
                     for (u32 q = 0; q < MAXI / 256; q++) irec32[q * 64 + lane] = 0;
+                    if (FOLD) {
+#pragma unroll
+                        for (u32 q = 0; q < NI; q++) s_idiff[lane * NI + q] = 0;
+                    }
                     wave_sync();
                     if (my_n) s_irec[x - my_n] = (uint8_t)(lane + 1);
+                    if (FOLD && lane < nrec) {
+                        atomicAdd(&s_idiff[m_first], my_mult);
+                        if (m_first + raw_n < ninst) atomicAdd(&s_idiff[m_first + raw_n], 0u - my_mult);
+                    }
                     wave_sync();
                     u32 wv[MAXI / 256], run = 0;
 #pragma unroll
                     for (u32 q = 0; q < MAXI / 256; q++) {
                         wv[q] = irec32[lane * (MAXI / 256) + q];
                         run = op_max_u32(run, op_max_u32(op_max_u32(wv[q] & 0xff, (wv[q] >> 8) & 0xff), op_max_u32((wv[q] >> 16) & 0xff, wv[q] >> 24)));
+                    }
+                    if (FOLD) {
+                        u32 mv[NI], tot = 0;
+#pragma unroll
+                        for (u32 q = 0; q < NI; q++) {
+                            tot += s_idiff[lane * NI + q];
+                            mv[q] = tot;
+                        }
+                        const u32 before = wave_incl_scan(tot, lane) - tot;
+                        u32* mult32 = (u32*)s_imult;
+#pragma unroll
+                        for (u32 q = 0; q < NI / 4; q++)
+                            mult32[lane * (NI / 4) + q] = ((mv[4 * q] + before) & 0xff) | (((mv[4 * q + 1] + before) & 0xff) << 8) |
+                                                          (((mv[4 * q + 2] + before) & 0xff) << 16) | ((mv[4 * q + 3] + before) << 24);
                     }
                     u32 carry = wave_prev_lane(wave_incl_max_scan(run));  // the last mark before this lane's instances
 #pragma unroll
@@ -662,18 +788,15 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                 CNT(4, ninst)
                 CNT(5, nrec)
                 if (NW) {
-                    // the records once more, as 32-bit words of C << 6 with their packed info (the u64 copy was for the
-                    // record-level pass above; its last reader is behind the wave_sync before the instance map)
-                    if (lane < nrec) {
-                        const u32 info = (x - my_n) | (raw_n << 10) | (hdr_idx0(my_hdr) << 18) | ((hdr_bucket(my_hdr) & ((1u << SHIFT) - 1)) << 26);
-                        store_rec_words<NW ? NW : 1>(s_rw + lane * RecGeom<NW ? NW : 1>::RS, rr, info);
-                    }
+                    // the records' info words: [first instance | n | idx0' | routing id low bits]
+                    if (FOLD && lane < nrec) s_rw[lane * RecGeom<NW ? NW : 1>::RS + RecGeom<NW ? NW : 1>::INFO] = (x - my_n) | info_hi;
+                    if (!FOLD && lane < nrec) store_rec_words<NW ? NW : 1>(s_rw + lane * RecGeom<NW ? NW : 1>::RS, rr, (x - my_n) | info_hi);
                     wave_sync();
-                    if (ninst <= 64) expand_and_dedupe_words<1, NW ? NW : 1, KB, SHIFT, NI>(lane, ninst, tsize, s_rw, s_irec, s_rmult, s_key, s_tab, &dbg_r, li);
-                    else if (ninst <= 128) expand_and_dedupe_words<2, NW ? NW : 1, KB, SHIFT, NI>(lane, ninst, tsize, s_rw, s_irec, s_rmult, s_key, s_tab, &dbg_r, li);
-                    else if (ninst <= 192) expand_and_dedupe_words<3, NW ? NW : 1, KB, SHIFT, NI>(lane, ninst, tsize, s_rw, s_irec, s_rmult, s_key, s_tab, &dbg_r, li);
-                    else if (NI <= 4 || ninst <= 256) expand_and_dedupe_words<4, NW ? NW : 1, KB, SHIFT, NI>(lane, ninst, tsize, s_rw, s_irec, s_rmult, s_key, s_tab, &dbg_r, li);
-                    else expand_and_dedupe_words<NI, NW ? NW : 1, KB, SHIFT, NI>(lane, ninst, tsize, s_rw, s_irec, s_rmult, s_key, s_tab, &dbg_r, li);
+                    if (ninst <= 64) expand_and_dedupe_words<1, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    else if (ninst <= 128) expand_and_dedupe_words<2, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    else if (ninst <= 192) expand_and_dedupe_words<3, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    else if (NI <= 4 || ninst <= 256) expand_and_dedupe_words<4, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    else expand_and_dedupe_words<NI, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
                 } else {
                     if (ninst <= 128) expand_and_dedupe<2, 0>(P, lane, ninst, tsize, s_rec, s_pref, s_irec, s_rmult, s_key, s_tab);
                     else if (NI <= 4 || ninst <= 256) expand_and_dedupe<4, 0>(P, lane, ninst, tsize, s_rec, s_pref, s_irec, s_rmult, s_key, s_tab);

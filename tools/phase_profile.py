@@ -40,13 +40,14 @@ for rep in range(2):
     ix.sync()
     prof = ix.profile_read()
     L.brisk_hip_debug_phases(buf, 0)
-names = ["0 loop/desc/wait", "1 rec store+scan+rec dedupe", "2 pref/table init/inst map", "3 expand+CAS dedupe", "4 -", "5 stream existing",
+names = ["0 loop/desc/wait", "1 rec store+scan+fold/dedupe", "2 pref/table init/inst map", "3 expand+CAS dedupe", "4 -", "5 stream existing",
          "6 compact new", "7 alloc/move", "8 append", "9 epilogue", "10 tail"]
 tot = sum(buf[i] for i in range(11)) or 1
 print("k_insert ms:", {n: round(v["ms"], 3) for n, v in prof.items() if v["launches"]})
 for i, n in enumerate(names):
     print(f"{n:32s} {buf[i]:16d} {100.0 * buf[i] / tot:6.2f} %")
-cn = ["partitions", "chunks", "record-dedupe attempts", "expand its (x64 lanes)", "instances", "records", "append passes", "new entries", "CAS rounds x its"]
+cn = ["partitions", "chunks", "record-dedupe attempts", "expand its (x64 lanes)", "instances", "records", "append passes", "new entries", "CAS rounds x its",
+      "instances before the fold", "records folded", "fold rounds (heads)"]
 for i, n in enumerate(cn):
     print(f"{n:28s} {buf[16 + i]:14d}  per partition {buf[16 + i] / max(buf[16], 1):8.3f}")
 L.brisk_hip_debug_scan_counts(sbuf, 0)
