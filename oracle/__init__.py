@@ -258,6 +258,18 @@ class Oracle(_Lib):
         L = self.lib
         L.bo_index_insert_reads.restype = C.c_int
         L.bo_index_insert_reads.argtypes = [C.c_void_p, u8p, u64p, C.c_uint64]
+        L.bo_index_insert_reads_mt.restype = C.c_int
+        L.bo_index_insert_reads_mt.argtypes = [C.c_void_p, u8p, u64p, C.c_uint64, C.c_int]
+        L.bo_index_query_reads_mt.restype = C.c_int
+        L.bo_index_query_reads_mt.argtypes = [C.c_void_p, u8p, u64p, C.c_uint64, u64p, C.c_int]
+        L.bo_index_digest.restype = None
+        L.bo_index_digest.argtypes = [C.c_void_p, u64p]
+        L.bo_digest_entries.restype = None
+        L.bo_digest_entries.argtypes = [u64p, u64p, u8p, u8p, C.c_uint64, u64p]
+        L.bo_index_set_bucket_range.restype = C.c_int
+        L.bo_index_set_bucket_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+        L.bo_bucket_ids.restype = None
+        L.bo_bucket_ids.argtypes = [C.c_void_p, u64p, u64p, u8p, C.c_uint64, u32p, C.c_int]
         L.bo_class.restype = C.c_uint
         L.bo_class.argtypes = [C.c_uint64, C.c_uint, f64p]
         L.bo_key.restype = C.c_uint64
@@ -272,7 +284,52 @@ class Oracle(_Lib):
         L.bo_synth_reads.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, C.c_uint64, C.c_uint64, u8p]
 
     def index_insert_reads(self, h, flat, offs, threads: int = 1) -> None:
-        self.lib.bo_index_insert_reads(h, flat, offs, len(offs) - 1)
+        """threads == 1: the single-threaded insert; more: bo_index_insert_reads_mt, which builds the identical index."""
+        if threads > 1:
+            rc = self.lib.bo_index_insert_reads_mt(h, flat, offs, len(offs) - 1, threads)
+        else:
+            rc = self.lib.bo_index_insert_reads(h, flat, offs, len(offs) - 1)
+        assert rc == 0, rc
+
+    def index_insert_reads_mt(self, h, flat, offs, threads: int) -> None:
+        """The threaded code path whatever `threads` is (1 included)."""
+        assert self.lib.bo_index_insert_reads_mt(h, flat, offs, len(offs) - 1, threads) == 0
+
+    def index_query_reads(self, h, flat: np.ndarray, offs: np.ndarray, threads: int = 1) -> np.ndarray:
+        if threads <= 1:
+            return super().index_query_reads(h, flat, offs)
+        out = np.zeros(len(offs) - 1, np.uint64)
+        self.lib.bo_index_query_reads_mt(h, flat, offs, len(offs) - 1, out, threads)
+        return out
+
+    def index_digest(self, h) -> tuple:
+        """(entries, sum of counts, digest) of the index, as oracle.digest and brisk_hip_checksum define it."""
+        out = np.zeros(3, np.uint64)
+        self.lib.bo_index_digest(h, out)
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def digest_entries(self, lo, hi, idx, cnt) -> tuple:
+        """The same digest over entry arrays (BriskHip.enumerate(), index_dump)."""
+        lo, hi = np.ascontiguousarray(lo, np.uint64), np.ascontiguousarray(hi, np.uint64)
+        idx, cnt = np.ascontiguousarray(idx, np.uint8), np.ascontiguousarray(cnt, np.uint8)
+        assert len(lo) == len(hi) == len(idx) == len(cnt)
+        out = np.zeros(3, np.uint64)
+        self.lib.bo_digest_entries(lo, hi, idx, cnt, len(lo), out)
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def index_set_bucket_range(self, h, first: int, last: int) -> None:
+        """From now on insert skips every k-mer whose bucket id lies outside [first, last)."""
+        if self.lib.bo_index_set_bucket_range(h, first, last):
+            raise ValueError(f"bucket range [{first}, {last})")
+
+    def bucket_ids(self, h, lo, hi, idx, threads: int = 1) -> np.ndarray:
+        """Bucket id of unhashed entries (the geometry is the index's)."""
+        lo, hi = np.ascontiguousarray(lo, np.uint64), np.ascontiguousarray(hi, np.uint64)
+        idx = np.ascontiguousarray(idx, np.uint8)
+        assert len(lo) == len(hi) == len(idx)
+        out = np.zeros(len(lo), np.uint32)
+        self.lib.bo_bucket_ids(h, lo, hi, idx, len(lo), out, threads)
+        return out
 
     def class_many(self, xs: Iterable[int], m: int) -> np.ndarray:
         coef = self.coef_table(m)

@@ -276,6 +276,7 @@ def test_randomised_parity_soak(B):
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fuzz_parity.py")
     p = subprocess.run([sys.executable, worker, "25", "7"], capture_output=True, text=True, timeout=600)
     last = p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
+    print("randomised parity soak:", last.split()[1] if last.startswith("done") else "?", "cases")
     assert p.returncode == 0 and last.startswith("done") and int(last.split()[1]) >= 20, (p.stdout[-2000:], p.stderr[-3000:])
 
 
