@@ -5,7 +5,10 @@
 //   brisk_count --mixed  FASTA k m b              BASELINE config #5's protocol (apps/counter.cpp:197-227,314-346): one thread streams the
 //                                                 file into brisk_hip_insert_reads while a second thread issues brisk_hip_get_reads on
 //                                                 the first reads of batches that are already in; prints what every get saw
-// Prints nb_kmers / nb_buckets / sum of counts; optionally dumps "KMER idx count" lines (dump.txt, "-" for none) and
+// --bulk only, anywhere on the command line (taken out before the positional arguments are read):
+//   --histo FILE     the count spectrum (brisk_hip_count_spectrum): 256 lines "count<TAB>entries", empty bins included
+//   --min-count N / --max-count N   the dump and the KFF file hold only the entries with N <= count (<= N): brisk_hip_enumerate_range
+// Prints nb_kmers / nb_buckets / sum of counts (of the entries dumped); optionally dumps "KMER idx count" lines (dump.txt, "-" for none) and
 // writes the index as a KFF file (a 7th argument: BriskWriter in --facade mode, brisk_write_kff in --bulk mode).
 #include <algorithm>
 #include <cstdio>
@@ -117,9 +120,47 @@ static int run_mixed(const char* path, uint8_t k, uint8_t m, uint8_t b, const do
     return failed ? 1 : 0;
 }
 
-int main(int argc, char** argv) {
+int main(int argc_in, char** argv_in) {
+    // named options first: what is left is the positional command line as it always was
+    std::vector<char*> args;
+    const char* histo = nullptr;
+    long min_count = 0, max_count = 255;
+    bool have_range = false;
+    for (int i = 0; i < argc_in; i++) {
+        const bool named = i > 0 && (!strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count"));
+        if (!named) {
+            args.push_back(argv_in[i]);
+            continue;
+        }
+        if (i + 1 >= argc_in) {
+            std::cerr << argv_in[i] << " needs a value" << std::endl;
+            return 2;
+        }
+        const char* opt = argv_in[i++];
+        if (!strcmp(opt, "--histo")) histo = argv_in[i];
+        else {
+            char* end = nullptr;
+            const long v = strtol(argv_in[i], &end, 10);
+            if (end == argv_in[i] || *end || v < 0 || v > 255) {
+                std::cerr << opt << ": a count is 0..255, got " << argv_in[i] << std::endl;
+                return 2;
+            }
+            (!strcmp(opt, "--min-count") ? min_count : max_count) = v;
+            have_range = true;
+        }
+    }
+    const int argc = (int)args.size();
+    char** argv = args.data();
+    if ((histo || have_range) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--histo, --min-count and --max-count work on the device index: --bulk only" << std::endl;
+        return 2;
+    }
+    if (min_count > max_count) {
+        std::cerr << "--min-count " << min_count << " is above --max-count " << max_count << std::endl;
+        return 2;
+    }
     if (argc < 6) {
-        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt]" << std::endl;
+        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--histo FILE] [--min-count N] [--max-count N])" << std::endl;
         return 2;
     }
     const bool bulk = !strcmp(argv[1], "--bulk");
@@ -237,19 +278,29 @@ int main(int argc, char** argv) {
                     std::cout << "}}" << std::endl;
                 }
             }
+            if (histo) {
+                uint64_t spectrum[256];
+                if (brisk_hip_count_spectrum(h, spectrum) != BRISK_HIP_OK) {
+                    std::cerr << "histo: " << brisk_hip_last_error(h) << std::endl;
+                    return 1;
+                }
+                std::ofstream out(histo);
+                for (int c = 0; c < 256; c++) out << c << "\t" << spectrum[c] << "\n";
+            }
             uint64_t cursor = 0, n = 0;
             const uint64_t cap = 1u << 20;
             std::vector<uint64_t> lo(cap), hi(cap);
             std::vector<uint8_t> idx(cap), cnt(cap);
             for (;;) {
-                rc = brisk_hip_enumerate(h, &cursor, lo.data(), hi.data(), idx.data(), cnt.data(), cap, &n);
+                rc = have_range ? brisk_hip_enumerate_range(h, &cursor, lo.data(), hi.data(), idx.data(), cnt.data(), cap, &n, (uint32_t)min_count, (uint32_t)max_count)
+                                : brisk_hip_enumerate(h, &cursor, lo.data(), hi.data(), idx.data(), cnt.data(), cap, &n);
                 if (rc != BRISK_HIP_OK || n == 0) break;
                 for (uint64_t i = 0; i < n; i++) {
                     sum += cnt[i];
                     if (dump) lines.push_back(kmer2str(((kint)hi[i] << 64) | lo[i], k) + " " + std::to_string(idx[i]) + " " + std::to_string(cnt[i]));
                 }
             }
-            if (kff && brisk_write_kff(h, kff) != BRISK_HIP_OK) {
+            if (kff && brisk_write_kff(h, kff, (uint32_t)min_count, (uint32_t)max_count) != BRISK_HIP_OK) {
                 std::cerr << "KFF: " << brisk_hip_last_error(h) << std::endl;
                 return 1;
             }

@@ -112,6 +112,7 @@ struct brisk_hip_index {
     u64 nb_skmers = 0;
     std::vector<u32> h_dir_cnt;  // enumeration snapshot
     bool dir_snapshot_valid = false;
+    u32 snapshot_range = 0;      // what h_dir_cnt counts: 0 every entry, else 0x10000 | min_count << 8 | max_count (brisk_hip_enumerate_range)
     // profiling
     bool profiling = false;
     std::vector<PendingEvent> pending;
@@ -2134,22 +2135,31 @@ BRISK_API int brisk_hip_lookup(brisk_hip_index* h, const uint64_t* kmer_lo, cons
     return BRISK_HIP_OK;
 }
 
+// range: 0 for every entry, else 0x10000 | min_count << 8 | max_count: the entries whose count is in that range only
 static int enumerate_impl(brisk_hip_index* h, uint64_t* cursor, uint64_t* out_lo, uint64_t* out_hi, uint8_t* out_minimizer_idx,
-                          uint8_t* out_data, uint32_t* out_ids, uint64_t cap, uint64_t* n_out) {
+                          uint8_t* out_data, uint32_t* out_ids, uint64_t cap, uint64_t* n_out, uint32_t range = 0) {
     if (!h || !cursor || !n_out || (cap && (!out_lo || !out_hi || !out_minimizer_idx))) return BRISK_HIP_EINVAL;
     if (out_ids && !h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "not an entry-id index");
+    if (range && h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "enumerate_range on an entry-id index: its DATA lives on the host");
+    const u32 r_lo = (range >> 8) & 0xffu, r_hi = range & 0xffu;
     HIPCHK(h, hipSetDevice(h->device));
     std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
     if (int frc = enter(h)) return frc;
     *n_out = 0;
-    if (*cursor == 0 || !h->dir_snapshot_valid) {
+    if (*cursor == 0 || !h->dir_snapshot_valid || h->snapshot_range != range) {
         h->h_dir_cnt.resize(h->n_parts);
         // d_cur32 is per-batch scratch, free between batches
-        hipLaunchKernelGGL(k_dir_counts, dim3(nblocks(h->n_parts, 256)), dim3(256), 0, h->stream, h->ix.dir, h->n_parts, h->d_cur32);
-        if (int lrc = launch_check(h, "k_dir_counts")) return lrc;
+        if (range) {
+            hipLaunchKernelGGL(k_dir_counts_range, dim3((u32)std::min<u64>(nblocks(h->n_parts * 64, 256), 2048)), dim3(256), 0, h->stream, h->ix, (u32)h->n_parts, r_lo, r_hi, h->d_cur32);
+            if (int lrc = launch_check(h, "k_dir_counts_range")) return lrc;
+        } else {
+            hipLaunchKernelGGL(k_dir_counts, dim3(nblocks(h->n_parts, 256)), dim3(256), 0, h->stream, h->ix.dir, h->n_parts, h->d_cur32);
+            if (int lrc = launch_check(h, "k_dir_counts")) return lrc;
+        }
         HIPCHK(h, hipMemcpyAsync(h->h_dir_cnt.data(), h->d_cur32, h->n_parts * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->dir_snapshot_valid = true;
+        h->snapshot_range = range;
     }
     u64 p = *cursor;
     while (p < h->n_parts && h->h_dir_cnt[p] == 0) p++;
@@ -2175,8 +2185,13 @@ static int enumerate_impl(brisk_hip_index* h, uint64_t* cursor, uint64_t* out_lo
     HIPCHK(h, hipMemcpyAsync(d_base, base.data(), np * 8, hipMemcpyHostToDevice, h->stream));
     if (total) {
         ProfScope ps(h, S_ENUM);
-        hipLaunchKernelGGL(k_enumerate, dim3((u32)std::min<u64>(np, 1u << 22)), dim3(64), 0, h->stream, h->P, h->ix, (u32)p, (u32)np, d_base, d_lo, d_hi, d_idx, d_cnt, d_ids);
-        if ((rc = launch_check(h, "k_enumerate"))) return rc;
+        if (range) {
+            hipLaunchKernelGGL(k_enumerate_range, dim3((u32)std::min<u64>(np, 1u << 22)), dim3(64), 0, h->stream, h->P, h->ix, (u32)p, (u32)np, d_base, total, r_lo, r_hi, d_lo, d_hi, d_idx, d_cnt);
+            if ((rc = launch_check(h, "k_enumerate_range"))) return rc;
+        } else {
+            hipLaunchKernelGGL(k_enumerate, dim3((u32)std::min<u64>(np, 1u << 22)), dim3(64), 0, h->stream, h->P, h->ix, (u32)p, (u32)np, d_base, d_lo, d_hi, d_idx, d_cnt, d_ids);
+            if ((rc = launch_check(h, "k_enumerate"))) return rc;
+        }
         HIPCHK(h, hipMemcpyAsync(out_lo, d_lo, total * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(out_hi, d_hi, total * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(out_minimizer_idx, d_idx, total, hipMemcpyDeviceToHost, h->stream));
@@ -2199,6 +2214,67 @@ BRISK_API int brisk_hip_enumerate_ids(brisk_hip_index* h, uint64_t* cursor, uint
                                       uint32_t* out_ids, uint64_t cap, uint64_t* n_out) {
     if (cap && !out_ids) return BRISK_HIP_EINVAL;
     return enumerate_impl(h, cursor, out_lo, out_hi, out_minimizer_idx, nullptr, out_ids, cap, n_out);
+}
+
+BRISK_API int brisk_hip_enumerate_range(brisk_hip_index* h, uint64_t* cursor, uint64_t* out_lo, uint64_t* out_hi, uint8_t* out_minimizer_idx,
+                                        uint8_t* out_data, uint64_t cap, uint64_t* n_out, uint32_t min_count, uint32_t max_count) {
+    if (cap && !out_data) return BRISK_HIP_EINVAL;
+    if (min_count > max_count) return fail(h, BRISK_HIP_EINVAL, "enumerate_range: min_count > max_count");
+    // (counts are bytes: a bound above 255 is 255, a range wholly above it holds nothing)
+    if (min_count > 255) {
+        if (!h || !cursor || !n_out) return BRISK_HIP_EINVAL;
+        if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "enumerate_range on an entry-id index: its DATA lives on the host");
+        *cursor = h->n_parts;
+        *n_out = 0;
+        return BRISK_HIP_OK;
+    }
+    return enumerate_impl(h, cursor, out_lo, out_hi, out_minimizer_idx, out_data, nullptr, cap, n_out, 0x10000u | (min_count << 8) | std::min<uint32_t>(max_count, 255u));
+}
+
+BRISK_API int brisk_hip_count_spectrum(brisk_hip_index* h, uint64_t out[256]) {
+    if (!h || !out) return BRISK_HIP_EINVAL;
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "count_spectrum on an entry-id index: its DATA lives on the host");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    int rc;
+    if ((rc = ensure(h, h->enum_out, 256 * 8))) return rc;  // (enumeration scratch, free between calls)
+    unsigned long long* d_hist = (unsigned long long*)h->enum_out.p;
+    HIPCHK(h, hipMemsetAsync(d_hist, 0, 256 * 8, h->stream));
+    const u64 n_groups = (h->n_parts + 63) / 64;  // a wave takes 64 partitions at a time
+    hipLaunchKernelGGL(k_spectrum, dim3((u32)std::min<u64>(nblocks(n_groups, 4), 2048)), dim3(256), 0, h->stream, h->ix, (u32)h->n_parts, d_hist);
+    if ((rc = launch_check(h, "k_spectrum"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, d_hist, 256 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_prune(brisk_hip_index* h, uint32_t min_count, uint32_t max_count, uint64_t* removed) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (min_count > max_count) return fail(h, BRISK_HIP_EINVAL, "prune: min_count > max_count");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "prune on an entry-id index: its DATA lives on the host");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    if (removed) *removed = 0;
+    // (counts are bytes: a range wholly above 255 keeps nothing -- min 256, max 255 below -- and a bound above 255 is 255)
+    const u32 lo = std::min<u32>(min_count, 256u), hi = std::min<u32>(max_count, 255u);
+    int rc;
+    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 8, h->stream));
+    hipLaunchKernelGGL(k_prune, dim3((u32)std::min<u64>(nblocks(h->n_parts * 64, 256), 2048)), dim3(256), 0, h->stream, h->ix, (u32)h->n_parts, lo, hi, h->d_small);
+    if ((rc = launch_check(h, "k_prune"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 n_removed = h->h_small[0];
+    if (n_removed) {  // the directory changed: the enumeration snapshot is stale, and a bucket may have lost its last entry
+        h->dir_snapshot_valid = false;
+        HIPCHK(h, hipMemsetAsync(h->ix.bucket_bits, 0, ((h->n_buckets + 31) / 32) * 4, h->stream));
+        const u64 threads = h->P.shift ? h->n_parts * 64 : h->n_parts;
+        hipLaunchKernelGGL(k_bucket_bits_rebuild, dim3((u32)std::min<u64>(nblocks(threads, 256), 2048)), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts);
+        if ((rc = launch_check(h, "k_bucket_bits_rebuild"))) return rc;
+    }
+    if (removed) *removed = n_removed;
+    return check_device_flags(h);
 }
 
 BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t* nb_skmers, uint64_t* nb_kmers, uint64_t* memory_bytes,

@@ -666,3 +666,194 @@ __global__ void __launch_bounds__(256) k_set_multiplicity(u64* __restrict__ rec,
     if (i >= n_rec) return;
     rec[i * stride + stride - 1] |= HDR_HAS_MULT | ((u64)cnt[tags[i]] << 48);
 }
+
+// ===========================================================================
+// Abundance: the count spectrum, enumeration restricted to a count range, and prune (no reference counterpart: the
+// reference has Brisk::stats and Brisk::next only).  All three compare the STORED count byte (counts are kept mod 256).
+//
+// k_spectrum: out[c] += entries whose count is c, over the live slices only (the arena also holds abandoned slices).
+// A wave takes 64 consecutive partitions at a time: one coalesced read of their directory lines, a prefix sum of their
+// sizes, and then the wave walks the group's entries as ONE list -- entry i belongs to the partition whose inclusive
+// prefix is the first above i (a six-step search in the wave's 64 prefixes in LDS) -- so every pass has 64 busy lanes
+// whatever the partition sizes are (80 entries a partition at working density: a wave per partition idles 40 % of its lanes on
+// the second pass) and the count loads of a group do not wait for a directory line each.
+// A real spectrum is one or two values almost everywhere, so the 64 lanes of a pass mostly want the same bin: the lanes
+// holding the first lane's value are counted with a ballot and ONE lane adds the popcount, then the same for the first
+// lane left over, until at most SP_DIRECT lanes are left (or SP_ROUNDS rounds have passed: a spectrum that is flat across 64 lanes has few
+// conflicts anyway), which add 1 each.  One 256-bin histogram per block in LDS, one global atomic per non-empty bin per block.
+#define SP_ROUNDS 4
+#define SP_DIRECT 8
+__device__ __forceinline__ void spectrum_add(unsigned long long* s_hist, u32 v, bool valid, u32 lane) {
+    unsigned long long left = __ballot(valid);  // wave-uniform
+#pragma unroll
+    for (int round = 0; round < SP_ROUNDS; round++) {
+        if (__popcll(left) <= SP_DIRECT) break;
+        const u32 first = (u32)__ffsll((long long)left) - 1;
+        const u32 lead = (u32)__builtin_amdgcn_readlane((int)v, (int)first);
+        const unsigned long long same = __ballot(valid && v == lead);
+        if (lane == first) atomicAdd(&s_hist[lead], (unsigned long long)__popcll(same));
+        valid = valid && v != lead;
+        left &= ~same;
+    }
+    if (valid) atomicAdd(&s_hist[v], 1ull);
+}
+__global__ void __launch_bounds__(256) k_spectrum(IndexDev ix, u32 n_parts, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s_hist[256];
+    __shared__ unsigned long long s_base[4][64];
+    __shared__ u32 s_incl[4][64];
+    const uint8_t* __restrict__ counts = ix.counts;
+    const u32 lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    s_hist[threadIdx.x] = 0;
+    __syncthreads();
+    const u32 wave = blockIdx.x * 4 + wib, n_waves = gridDim.x * 4, n_groups = (n_parts + 63) >> 6;
+    for (u32 g = wave; g < n_groups; g += n_waves) {
+        const u32 part = g * 64 + lane;
+        DirEnt de{0, 0, 0};
+        if (part < n_parts) de = ix.dir[part];
+        if (__ballot(de.cnt > (1u << 24))) {  // sizes whose sum might not fit 32 bits: partition by partition
+            for (u32 j = 0; j < 64; j++) {
+                const u32 cnt = (u32)__builtin_amdgcn_readlane((int)de.cnt, (int)j);
+                const unsigned long long off = __shfl(de.off, (int)j, 64);
+                for (u32 e0 = 0; e0 < cnt; e0 += 64) {
+                    const bool valid = cnt - e0 > lane;
+                    spectrum_add(s_hist, valid ? counts[off + e0 + lane] : 0u, valid, lane);
+                }
+            }
+            continue;
+        }
+        const u32 incl = wave_incl_scan(de.cnt, lane);
+        wave_sync();  // the previous group's searches are done
+        s_incl[wib][lane] = incl;
+        s_base[wib][lane] = de.off - (incl - de.cnt);  // entry i of the group is at base + i (mod 2^64)
+        wave_sync();
+        const u32 total = (u32)__builtin_amdgcn_readlane((int)incl, 63);
+        for (u32 i0 = 0; i0 < total; i0 += 64) {
+            const u32 i = i0 + lane;
+            const bool valid = i < total;
+            u32 j = 0;  // the number of prefixes <= i: the partition of entry i (at most 63 for a valid i)
+#pragma unroll
+            for (u32 s = 32; s; s >>= 1)
+                if (s_incl[wib][j + s - 1] <= i) j += s;
+            spectrum_add(s_hist, valid ? counts[s_base[wib][j] + i] : 0u, valid, lane);
+        }
+    }
+    __syncthreads();
+    const unsigned long long mine = s_hist[threadIdx.x];
+    if (mine) atomicAdd(&out[threadIdx.x], mine);
+}
+
+// entries of each partition whose count is in [lo, hi]: what k_dir_counts is to the plain enumeration
+__global__ void __launch_bounds__(256) k_dir_counts_range(IndexDev ix, u32 n_parts, u32 lo, u32 hi, u32* __restrict__ out) {
+    const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6, lane = threadIdx.x & 63;
+    for (u32 part = wave; part < n_parts; part += n_waves) {
+        const DirEnt de = ix.dir[part];
+        u32 n = 0;
+        for (u32 e0 = 0; e0 < de.cnt; e0 += 64) {
+            const u32 c = de.cnt - e0 > lane ? ix.counts[de.off + e0 + lane] : 0x100u;
+            n += (u32)__popcll(__ballot(c >= lo && c <= hi));
+        }
+        if (lane == 0) out[part] = n;
+    }
+}
+
+// k_enumerate with the predicate: the passing entries of a partition, compacted in storage order (chunks of 64 entries: ballot,
+// rank among the passing lanes below); out_base is the exclusive prefix of k_dir_counts_range's counts.  A store beyond the
+// partition's share cannot happen while the index is what the count pass saw (one call holds the handle's lock for both).
+__global__ void __launch_bounds__(64) k_enumerate_range(BriskParams P, IndexDev ix, u32 p_begin, u32 n_parts, const u64* __restrict__ out_base, u64 out_n, u32 lo, u32 hi,
+                                                        u64* __restrict__ out_lo, u64* __restrict__ out_hi, uint8_t* __restrict__ out_idx, uint8_t* __restrict__ out_cnt) {
+    const u32 lane = threadIdx.x;
+    for (u32 pi = blockIdx.x; pi < n_parts; pi += gridDim.x) {
+        const u32 part = p_begin + pi;
+        const DirEnt de = ix.dir[part];
+        u64 ob = out_base[pi];
+        for (u32 e0 = 0; e0 < de.cnt; e0 += 64) {
+            const bool valid = de.cnt - e0 > lane;
+            const u32 cnt = valid ? ix.counts[de.off + e0 + lane] : 0u;
+            const bool pass = valid && cnt >= lo && cnt <= hi;
+            const unsigned long long bal = __ballot(pass);
+            const u64 at = ob + (u32)__popcll(bal & lanes_below(lane));
+            if (pass && at < out_n) {  // (never outside the caller's buffers)
+                const u128x key = load_key(ix, de.off + e0 + lane);
+                u32 idx;
+                u128x hk = entry_hashed_kmer(P, part, key, &idx);
+                const u64 mm = mix2m_inv(shr128(hk, 2 * idx).lo & P.m_mask, P.m_mask);  // unhash_kmer_minimizer (Kmers.cpp:178-187)
+                hk = or128(andn128(hk, shl128(mk128(P.m_mask, 0), 2 * idx)), shl128(mk128(mm, 0), 2 * idx));
+                out_lo[at] = hk.lo;
+                out_hi[at] = hk.hi;
+                out_idx[at] = (uint8_t)idx;
+                out_cnt[at] = (uint8_t)cnt;
+            }
+            ob += (u32)__popcll(bal);
+        }
+    }
+}
+
+// k_prune: removes, in place, the entries whose count is outside [lo, hi].  One wave per partition, chunks of 64 entries:
+// every lane loads its entry's count, the survivors are ranked by a ballot, and a survivor that has a removed entry before
+// it moves down to slot written + rank.  Why this is safe in place:
+//  * inside a chunk, every load is issued for the whole wave before any store: the counts are loaded (by all lanes) before
+//    the ballot that the stores depend on, and the keys of the lanes that move are loaded by one instruction (per key word)
+//    whose results the stores of the same lanes wait for -- a lane stores the registers it loaded.  A survivor that stays
+//    (slot == its own index) neither loads its key nor stores anything, and no mover targets it: a lane that stays has no
+//    removed entry before it, so every later survivor's slot is above its own;
+//  * written never exceeds the chunk's first index, so a chunk's stores go below the first entry of the next chunk, whose
+//    loads they therefore cannot touch; earlier chunks are never read again.
+// A partition with nothing to remove stores nothing at all (prune(0, 255) reads the counts and the directory only).
+// The slice keeps its offset and capacity: the arena is a bump allocator, later inserts fill the freed tail.
+__global__ void __launch_bounds__(256) k_prune(IndexDev ix, u32 n_parts, u32 lo, u32 hi, unsigned long long* __restrict__ removed_out) {
+    const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6, lane = threadIdx.x & 63;
+    unsigned long long removed = 0;  // wave-uniform
+    for (u32 part = wave; part < n_parts; part += n_waves) {
+        const DirEnt de = ix.dir[part];
+        u32 written = 0;
+        for (u32 e0 = 0; e0 < de.cnt; e0 += 64) {
+            const u32 e = e0 + lane;
+            const bool valid = e < de.cnt;
+            const u32 c = valid ? ix.counts[de.off + e] : 0u;
+            const bool keep = valid && c >= lo && c <= hi;
+            const unsigned long long bal = __ballot(keep);
+            const u32 slot = written + (u32)__popcll(bal & lanes_below(lane));  // <= e
+            if (keep && slot != e) {
+                const u128x key = load_key(ix, de.off + e);
+                store_key(ix, de.off + slot, key.lo, key.hi);
+                ix.counts[de.off + slot] = (uint8_t)c;
+            }
+            written += (u32)__popcll(bal);
+        }
+        if (written != de.cnt) {
+            if (lane == 0) ix.dir[part].cnt = written;
+            removed += de.cnt - written;
+        }
+    }
+    if (lane == 0 && removed) atomicAdd(removed_out, removed);
+}
+
+// The bucket occupancy bitmap from the entries, for every geometry (after a prune).  k_bucket_bits serves brisk_hip_stats where a
+// partition spans more than 64 buckets and there ext_bits == 0; with ext_bits > 0 a partition is a slice of ONE bucket and
+// part << shift is a routing id, so the bucket id is the routing id without its ext_bits.  shift == 0: an entry's bucket
+// is its partition's, no key is read (one lane per partition); else one wave per partition reads the key word that holds the
+// routing id's low bits.  A bit that is already set is not set again (same-address atomics serialise device-wide).
+__global__ void __launch_bounds__(256) k_bucket_bits_rebuild(BriskParams P, IndexDev ix, u32 n_parts) {
+    if (P.shift == 0) {
+        const u32 stride = gridDim.x * blockDim.x;
+        for (u32 part = blockIdx.x * blockDim.x + threadIdx.x; part < n_parts; part += stride) {
+            if (!ix.dir[part].cnt) continue;
+            const u32 bucket = part >> P.ext_bits, bit = 1u << (bucket & 31);
+            if (!(ix.bucket_bits[bucket >> 5] & bit)) atomicOr(&ix.bucket_bits[bucket >> 5], bit);
+        }
+        return;
+    }
+    const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6, lane = threadIdx.x & 63;
+    const u32 kbits = 2 * P.kb + 6, low_mask = (1u << P.shift) - 1;
+    for (u32 part = wave; part < n_parts; part += n_waves) {
+        const DirEnt de = ix.dir[part];
+        for (u32 e = lane; e < de.cnt; e += 64) {
+            u32 low;
+            if (ix.key_words == 1) low = (u32)(ix.keys[de.off + e] >> kbits);
+            else if (kbits >= 64) low = (u32)(ix.keys[2 * (de.off + e) + 1] >> (kbits - 64));
+            else low = (u32)shr128(load_key<2>(ix, de.off + e), kbits).lo;
+            const u32 bucket = ((part << P.shift) | (low & low_mask)) >> P.ext_bits, bit = 1u << (bucket & 31);
+            if (!(ix.bucket_bits[bucket >> 5] & bit)) atomicOr(&ix.bucket_bits[bucket >> 5], bit);
+        }
+    }
+}

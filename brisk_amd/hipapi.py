@@ -102,7 +102,7 @@ SYMBOLS = [
     "brisk_hip_get_layout", "brisk_hip_insert_reads", "brisk_hip_insert_packed", "brisk_hip_get_reads", "brisk_hip_lookup",
     "brisk_hip_enumerate", "brisk_hip_stats", "brisk_hip_memory_info", "brisk_hip_insert_slack", "brisk_hip_reallocate", "brisk_hip_checksum", "brisk_hip_scan_packed", "brisk_hip_scan_bound", "brisk_hip_route_records",
     "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
-    "brisk_hip_enumerate_ids", "brisk_hip_profile_enable",
+    "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune", "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
 ]
 
@@ -158,6 +158,9 @@ def load() -> C.CDLL:
     L.brisk_hip_upsert_kmers.argtypes = [vp, _u64p, _u64p, _u8p, u64, _u32p, _u8p]
     L.brisk_hip_find_kmers.argtypes = [vp, _u64p, _u64p, _u8p, u64, _u32p]
     L.brisk_hip_enumerate_ids.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u32p, u64, C.POINTER(u64)]
+    L.brisk_hip_count_spectrum.argtypes = [vp, _u64p]
+    L.brisk_hip_enumerate_range.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64), u32, u32]
+    L.brisk_hip_prune.argtypes = [vp, u32, u32, C.POINTER(u64)]
     L.brisk_hip_debug_order_keys.argtypes = [vp, _u64p, u64, i32, _u64p]
     L.brisk_hip_profile_enable.argtypes = [vp, i32]
     L.brisk_hip_profile_read.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_char_p), C.POINTER(u64), C.POINTER(C.c_double)]
@@ -289,8 +292,10 @@ class BriskHip:
         self._chk(self.L.brisk_hip_lookup(self.h, lo, hi, idx, n, data, found))
         return data[:n], found[:n]
 
-    def enumerate(self, chunk: int = 1 << 20):
-        """All entries: (lo, hi, minimizer_idx, count) arrays, k-mers unhashed."""
+    def enumerate(self, chunk: int = 1 << 20, min_count: int = 0, max_count: int = 255):
+        """All entries: (lo, hi, minimizer_idx, count) arrays, k-mers unhashed.  With bounds other than the defaults: the
+        entries whose count is in [min_count, max_count] only (brisk_hip_enumerate_range), in the same order."""
+        ranged = (min_count, max_count) != (0, 255)
         cur = C.c_uint64(0)
         n = C.c_uint64(0)
         los, his, idxs, cnts = [], [], [], []
@@ -300,7 +305,10 @@ class BriskHip:
             hi = np.zeros(cap, np.uint64)
             idx = np.zeros(cap, np.uint8)
             cnt = np.zeros(cap, np.uint8)
-            rc = self.L.brisk_hip_enumerate(self.h, C.byref(cur), lo, hi, idx, cnt, cap, C.byref(n))
+            if ranged:
+                rc = self.L.brisk_hip_enumerate_range(self.h, C.byref(cur), lo, hi, idx, cnt, cap, C.byref(n), min_count, max_count)
+            else:
+                rc = self.L.brisk_hip_enumerate(self.h, C.byref(cur), lo, hi, idx, cnt, cap, C.byref(n))
             if rc == ECAPACITY:
                 cap *= 4
                 continue
@@ -310,6 +318,18 @@ class BriskHip:
             los.append(lo[: n.value]); his.append(hi[: n.value]); idxs.append(idx[: n.value]); cnts.append(cnt[: n.value])
         cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
         return cat(los, np.uint64), cat(his, np.uint64), cat(idxs, np.uint8), cat(cnts, np.uint8)
+
+    def count_spectrum(self) -> np.ndarray:
+        """uint64[256]: out[c] = entries whose stored count (mod 256) is c"""
+        out = np.zeros(256, np.uint64)
+        self._chk(self.L.brisk_hip_count_spectrum(self.h, out))
+        return out
+
+    def prune(self, min_count: int, max_count: int = 255) -> int:
+        """remove, in place, every entry whose count is outside [min_count, max_count]; returns how many were removed"""
+        v = C.c_uint64()
+        self._chk(self.L.brisk_hip_prune(self.h, min_count, max_count, C.byref(v)))
+        return v.value
 
     def stats(self) -> dict:
         v = [C.c_uint64() for _ in range(5)]

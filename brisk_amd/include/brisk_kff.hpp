@@ -186,8 +186,10 @@ class KffIndexWriter {
 };
 
 #ifdef BRISK_HIP_H
-// A bulk-count index (DATA = the uint8_t counter on the device) straight from the C-ABI: brisk_hip_enumerate in chunks.
-inline int brisk_write_kff(brisk_hip_index* h, const std::string& path) {
+// A bulk-count index (DATA = the uint8_t counter on the device) straight from the C-ABI: brisk_hip_enumerate in chunks;
+// with bounds other than the defaults only the entries whose count is in [min_count, max_count] (brisk_hip_enumerate_range).
+inline int brisk_write_kff(brisk_hip_index* h, const std::string& path, uint32_t min_count = 0, uint32_t max_count = 255) {
+    const bool ranged = min_count != 0 || max_count != 255;
     brisk_hip_layout lay{};
     int rc = brisk_hip_get_layout(h, &lay);
     if (rc != BRISK_HIP_OK) return rc;
@@ -196,7 +198,8 @@ inline int brisk_write_kff(brisk_hip_index* h, const std::string& path) {
     std::vector<uint64_t> lo(cap), hi(cap);
     std::vector<uint8_t> idx(cap), cnt(cap);
     for (;;) {
-        rc = brisk_hip_enumerate(h, &cursor, lo.data(), hi.data(), idx.data(), cnt.data(), cap, &n);
+        rc = ranged ? brisk_hip_enumerate_range(h, &cursor, lo.data(), hi.data(), idx.data(), cnt.data(), cap, &n, min_count, max_count)
+                    : brisk_hip_enumerate(h, &cursor, lo.data(), hi.data(), idx.data(), cnt.data(), cap, &n);
         if (rc == BRISK_HIP_ECAPACITY) {  // one bucket range larger than the buffer
             cap *= 8;
             lo.resize(cap); hi.resize(cap); idx.resize(cap); cnt.resize(cap);

@@ -52,6 +52,10 @@
  *   brisk_hip_stats             Brisk::stats (brisk/Brisk.hpp:194-197,
  *                               brisk/DenseMenuYo.hpp:545-568)
  *   brisk_hip_memory_info / brisk_hip_insert_slack   no reference counterpart (Brisk::stats reports the process' peak RSS): the arena's bookkeeping
+ *   brisk_hip_count_spectrum / brisk_hip_enumerate_range / brisk_hip_prune
+ *                               no reference counterpart (Brisk::stats and Brisk::next are all it has): the abundance
+ *                               spectrum, the entries of a count range, and the index without the entries outside one,
+ *                               each one pass over the arena on the device
  *   brisk_hip_checksum          the next()+get() walk of verif_counts (apps/counter.cpp:90-126), reduced
  *                               to a digest on the device
  *   brisk_hip_scan_packed / brisk_hip_route_records / brisk_hip_insert_records
@@ -243,6 +247,29 @@ int brisk_hip_insert_slack(brisk_hip_index *h, uint64_t *entries);
  * mix(a,b,c,d) = f(a ^ f(b ^ f(c << 8 | d))), f = the splitmix64 finaliser (k-mers unhashed,
  * as Brisk::next yields them).  Digests of bucket-range shards add up to the whole index's. */
 int brisk_hip_checksum(brisk_hip_index *h, uint64_t out[3]);
+
+/* ---- abundance: spectrum, count-range enumeration, prune (no reference counterpart) ---- */
+/* All three compare the STORED count byte: counts are kept mod 256, so an entry whose count wrapped to 0 is an entry with
+ * count 0 (it is in bin 0, a range must include 0 to hold it, prune(1, 255) removes it).  All three complete pending
+ * deferred inserts first, return EINVAL on an entry-id index (its DATA lives with the caller), and on a sharded handle
+ * (n_owners > 1) speak about this owner's partitions only, as brisk_hip_checksum does.  A bound above 255 means 255. */
+/* out[c] = number of entries whose count is c (HOST array).  Sum over c == nb_kmers of brisk_hip_stats; sum of c * out[c] ==
+ * out[1] of brisk_hip_checksum.  Spectra of bucket-range shards add up. */
+int brisk_hip_count_spectrum(brisk_hip_index *h, uint64_t out[256]);
+/* brisk_hip_enumerate restricted to entries with min_count <= count <= max_count: same cursor protocol, same order (ascending
+ * partition, storage order inside one), same outputs.  EINVAL if min_count > max_count.  ECAPACITY only if the PASSING entries
+ * of one partition exceed cap.  A walk keeps its bounds from *cursor = 0 to the end. */
+int brisk_hip_enumerate_range(brisk_hip_index *h, uint64_t *cursor, uint64_t *out_lo, uint64_t *out_hi,
+                              uint8_t *out_minimizer_idx, uint8_t *out_data, uint64_t cap, uint64_t *n_out,
+                              uint32_t min_count, uint32_t max_count);
+/* Removes, in place, every entry whose count is outside [min_count, max_count]; *removed (may be NULL) receives how many.
+ * Afterwards the index is exactly the index that holds the remaining entries: stats (nb_kmers, nb_buckets, largest_bucket),
+ * checksum, enumerate, lookup, every get and every later insert behave so (a removed k-mer that is inserted again starts at
+ * 1).  Storage order of the survivors is kept.  nb_skmers (records received) is left as it is.  The arena is a bump
+ * allocator: a partition's slice keeps its place and capacity, so later inserts fill the room the removed entries left, but
+ * no device memory is returned and memory_bytes / brisk_hip_memory_info do not shrink (brisk_hip_clear, or a new index, do
+ * that).  EINVAL if min_count > max_count. */
+int brisk_hip_prune(brisk_hip_index *h, uint32_t min_count, uint32_t max_count, uint64_t *removed);
 
 /* ---- the path cut at the super-k-mer boundary (multi-GPU) ----------------- */
 /* scan: d_records receives up to cap_records records of record_words u64 each;
