@@ -8,6 +8,10 @@
 // --bulk only, anywhere on the command line (taken out before the positional arguments are read):
 //   --histo FILE     the count spectrum (brisk_hip_count_spectrum): 256 lines "count<TAB>entries", empty bins included
 //   --min-count N / --max-count N   the dump and the KFF file hold only the entries with N <= count (<= N): brisk_hip_enumerate_range
+//   --merge FILE / --subtract FILE / --intersect FILE   each at most once, applied in that order: FILE is counted into a second index with
+//                    the same parameters and combined with the first on the device (brisk_hip_merge / _subtract / _intersect, counts of
+//                    the first kept by --intersect) before --histo, --min-count / --max-count and the dump take effect; one line on stderr
+//                    per operation with the entries added / removed
 // Prints nb_kmers / nb_buckets / sum of counts (of the entries dumped); optionally dumps "KMER idx count" lines (dump.txt, "-" for none) and
 // writes the index as a KFF file (a 7th argument: BriskWriter in --facade mode, brisk_write_kff in --bulk mode).
 #include <algorithm>
@@ -126,8 +130,13 @@ int main(int argc_in, char** argv_in) {
     const char* histo = nullptr;
     long min_count = 0, max_count = 255;
     bool have_range = false;
+    const char* const setop_names[3] = {"--merge", "--subtract", "--intersect"};  // in the order they are applied
+    const char* setop_file[3] = {nullptr, nullptr, nullptr};
     for (int i = 0; i < argc_in; i++) {
-        const bool named = i > 0 && (!strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count"));
+        int setop = -1;
+        for (int q = 0; q < 3; q++)
+            if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
+        const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count"));
         if (!named) {
             args.push_back(argv_in[i]);
             continue;
@@ -138,7 +147,13 @@ int main(int argc_in, char** argv_in) {
         }
         const char* opt = argv_in[i++];
         if (!strcmp(opt, "--histo")) histo = argv_in[i];
-        else {
+        else if (setop >= 0) {
+            if (setop_file[setop]) {
+                std::cerr << opt << " may be given once" << std::endl;
+                return 2;
+            }
+            setop_file[setop] = argv_in[i];
+        } else {
             char* end = nullptr;
             const long v = strtol(argv_in[i], &end, 10);
             if (end == argv_in[i] || *end || v < 0 || v > 255) {
@@ -151,8 +166,9 @@ int main(int argc_in, char** argv_in) {
     }
     const int argc = (int)args.size();
     char** argv = args.data();
-    if ((histo || have_range) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--histo, --min-count and --max-count work on the device index: --bulk only" << std::endl;
+    const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
+    if ((histo || have_range || have_setop) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--histo, --min-count, --max-count, --merge, --subtract and --intersect work on the device index: --bulk only" << std::endl;
         return 2;
     }
     if (min_count > max_count) {
@@ -160,7 +176,7 @@ int main(int argc_in, char** argv_in) {
         return 2;
     }
     if (argc < 6) {
-        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--histo FILE] [--min-count N] [--max-count N])" << std::endl;
+        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] [--subtract FILE] [--intersect FILE])" << std::endl;
         return 2;
     }
     const bool bulk = !strcmp(argv[1], "--bulk");
@@ -277,6 +293,31 @@ int main(int argc_in, char** argv_in) {
                         }
                     std::cout << "}}" << std::endl;
                 }
+            }
+            for (int q = 0; q < 3; q++) {  // --merge, --subtract, --intersect: FILE counted into a second index, then combined on the device
+                if (!setop_file[q]) continue;
+                brisk_hip_index* other = nullptr;
+                rc = brisk_hip_create(&other, k, m, b, 1, params.dede->coef(), &o);
+                if (rc != BRISK_HIP_OK) {
+                    std::cerr << setop_names[q] << ": brisk_hip_create failed: " << rc << std::endl;
+                    return 1;
+                }
+                FastaBatcher batches(setop_file[q], batch_bases);
+                FastaBatch bt;
+                while (batches.next(bt))
+                    if ((rc = brisk_hip_insert_reads(other, bt.flat.data(), bt.offs.data(), bt.size())) != BRISK_HIP_OK) {
+                        std::cerr << setop_names[q] << ": " << brisk_hip_last_error(other) << std::endl;
+                        return 1;
+                    }
+                uint64_t changed = 0;
+                rc = q == 0 ? brisk_hip_merge(h, other, &changed) : q == 1 ? brisk_hip_subtract(h, other, &changed) : brisk_hip_intersect(h, other, BRISK_HIP_COUNT_LEFT, &changed);
+                if (rc != BRISK_HIP_OK) {
+                    std::cerr << setop_names[q] << ": " << brisk_hip_last_error(h) << std::endl;
+                    return 1;
+                }
+                std::cerr << (setop_names[q] + 2) << " " << setop_file[q] << ": " << changed << (q == 0 ? " entries added" : " entries removed") << std::endl;
+                brisk_hip_destroy(other);
+                brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
             }
             if (histo) {
                 uint64_t spectrum[256];

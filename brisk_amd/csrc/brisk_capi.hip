@@ -2393,6 +2393,179 @@ BRISK_API int brisk_hip_reallocate(brisk_hip_index* from, brisk_hip_index* to) {
     return check_device_flags(h);
 }
 
+// ---- set operations (no reference counterpart): two indexes of one geometry combined partition by partition (brisk_setops.hip) ----
+namespace {
+// what both handles of a set operation must agree in; the message names the first field that differs
+int setop_compatible(brisk_hip_index* h, const brisk_hip_index* a, const brisk_hip_index* b, const char* op) {
+    const std::string who = std::string(op) + ": ";
+    if (a->entry_ids || b->entry_ids) return fail(h, BRISK_HIP_EINVAL, who + "entry-id index (its DATA lives on the host)");
+    if (a->P.n_owners > 1 || b->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, who + "sharded index (n_owners > 1)");
+    const char* field = nullptr;
+    if (a->P.k != b->P.k) field = "k";
+    else if (a->P.m != b->P.m) field = "m";
+    else if (a->P.b != b->P.b) field = "b";
+    else if (a->P.part_bits != b->P.part_bits) field = "part_bits";
+    else if (a->P.ext_bits != b->P.ext_bits) field = "ext_bits";
+    else if (a->P.cls_bits != b->P.cls_bits) field = "cls_bits";
+    else if (a->P.cls_width != b->P.cls_width) field = "cls_width";
+    else if (a->ix.key_words != b->ix.key_words) field = "key width";
+    else if (a->device != b->device) field = "device";
+    if (field) return fail(h, BRISK_HIP_EINVAL, who + "the two indexes differ in " + field);
+    return BRISK_HIP_OK;
+}
+// the checks and the preparation the four calls share.  On success both locks are held (the caller adopts them), pending inserts
+// of both handles are in, and src's stream is idle, so dst's stream may read src's arena.
+int setop_enter(brisk_hip_index* dst, brisk_hip_index* src, const char* op) {
+    std::lock(dst->call_mu, src->call_mu);  // both or neither, as brisk_hip_reallocate
+    int rc = setop_compatible(dst, dst, src, op);
+    if (!rc) {
+        hipError_t e = hipSetDevice(dst->device);
+        if (e != hipSuccess) rc = fail(dst, BRISK_HIP_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    }
+    if (!rc && (rc = enter(src))) fail(dst, rc, std::string(op) + ": " + src->err);
+    if (!rc) rc = enter(dst);
+    if (!rc) {
+        hipError_t e = hipStreamSynchronize(src->stream);
+        if (e != hipSuccess) rc = fail(dst, BRISK_HIP_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        dst->call_mu.unlock();
+        src->call_mu.unlock();
+    }
+    return rc;
+}
+int launch_join(brisk_hip_index* h, brisk_hip_index* src, u32 op, u32 rule, unsigned long long* d_out) {
+    // persistent waves: a few per SIMD of every CU; fewer partitions than that take a wave each
+    const dim3 grid((u32)std::min<u64>(h->n_parts, 16384)), block(64);
+#define LAUNCH_JOIN(OP)                                                                                                                            \
+    {                                                                                                                                              \
+        if (h->ix.key_words == 1) hipLaunchKernelGGL((k_join<OP, 1>), grid, block, 0, h->stream, h->ix, src->ix, (u32)h->n_parts, rule, d_out);  \
+        else hipLaunchKernelGGL((k_join<OP, 2>), grid, block, 0, h->stream, h->ix, src->ix, (u32)h->n_parts, rule, d_out);                       \
+    }
+    if (op == JOIN_INTERSECT) LAUNCH_JOIN(JOIN_INTERSECT)
+    else if (op == JOIN_SUBTRACT) LAUNCH_JOIN(JOIN_SUBTRACT)
+    else LAUNCH_JOIN(JOIN_COMPARE)
+#undef LAUNCH_JOIN
+    return launch_check(h, "k_join");
+}
+// intersect / subtract: the join, then what brisk_hip_prune does after a removal
+int join_remove(brisk_hip_index* h, brisk_hip_index* src, u32 op, u32 rule, uint64_t* removed) {
+    int rc;
+    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 8, h->stream));
+    if ((rc = launch_join(h, src, op, rule, h->d_small))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 n_removed = h->h_small[0];
+    if (n_removed) {  // the directory changed: the enumeration snapshot is stale, and a bucket may have lost its last entry
+        h->dir_snapshot_valid = false;
+        HIPCHK(h, hipMemsetAsync(h->ix.bucket_bits, 0, ((h->n_buckets + 31) / 32) * 4, h->stream));
+        const u64 threads = h->P.shift ? h->n_parts * 64 : h->n_parts;
+        hipLaunchKernelGGL(k_bucket_bits_rebuild, dim3((u32)std::min<u64>(nblocks(threads, 256), 2048)), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts);
+        if ((rc = launch_check(h, "k_bucket_bits_rebuild"))) return rc;
+    }
+    if (removed) *removed = n_removed;
+    return check_device_flags(h);
+}
+// nb_kmers: the directory reduction of brisk_hip_stats
+int dir_entries(brisk_hip_index* h, u64* out) {
+    HIPCHK(h, hipMemsetAsync(h->ix.stats, 0, 24, h->stream));
+    hipLaunchKernelGGL(k_stats, dim3(1024), dim3(256), 0, h->stream, h->ix.dir, h->n_parts, h->ix.bucket_bits, (u64)0, h->ix.stats);
+    if (int lrc = launch_check(h, "k_stats")) return lrc;
+    unsigned long long n = 0;
+    HIPCHK(h, hipMemcpyAsync(&n, h->ix.stats, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *out = n;
+    return BRISK_HIP_OK;
+}
+}  // namespace
+
+BRISK_API int brisk_hip_intersect(brisk_hip_index* dst, brisk_hip_index* src, uint32_t count_rule, uint64_t* removed) {
+    if (!dst || !src || dst == src) return fail(dst, BRISK_HIP_EINVAL, "intersect: two different handles are needed");
+    if (count_rule > BRISK_HIP_COUNT_SUM) return fail(dst, BRISK_HIP_EINVAL, "intersect: unknown count_rule");
+    if (int rc = setop_enter(dst, src, "intersect")) return rc;
+    std::lock_guard<std::recursive_mutex> lock_dst(dst->call_mu, std::adopt_lock), lock_src(src->call_mu, std::adopt_lock);
+    if (removed) *removed = 0;
+    return join_remove(dst, src, JOIN_INTERSECT, count_rule, removed);
+}
+
+BRISK_API int brisk_hip_subtract(brisk_hip_index* dst, brisk_hip_index* src, uint64_t* removed) {
+    if (!dst || !src || dst == src) return fail(dst, BRISK_HIP_EINVAL, "subtract: two different handles are needed");
+    if (int rc = setop_enter(dst, src, "subtract")) return rc;
+    std::lock_guard<std::recursive_mutex> lock_dst(dst->call_mu, std::adopt_lock), lock_src(src->call_mu, std::adopt_lock);
+    if (removed) *removed = 0;
+    return join_remove(dst, src, JOIN_SUBTRACT, 0, removed);
+}
+
+BRISK_API int brisk_hip_compare(brisk_hip_index* a, brisk_hip_index* b, uint64_t out[6]) {
+    if (!a || !b || a == b) return fail(a, BRISK_HIP_EINVAL, "compare: two different handles are needed");
+    if (!out) return fail(a, BRISK_HIP_EINVAL, "compare: out is null");
+    if (int rc = setop_enter(a, b, "compare")) return rc;
+    std::lock_guard<std::recursive_mutex> lock_a(a->call_mu, std::adopt_lock), lock_b(b->call_mu, std::adopt_lock);
+    brisk_hip_index* h = a;
+    int rc;
+    if ((rc = ensure(h, h->enum_out, 6 * 8))) return rc;  // (enumeration scratch, free between calls)
+    unsigned long long* d_out = (unsigned long long*)h->enum_out.p;
+    HIPCHK(h, hipMemsetAsync(d_out, 0, 6 * 8, h->stream));
+    if ((rc = launch_join(h, b, JOIN_COMPARE, 0, d_out))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, d_out, 6 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// merge: src's entries as one-k-mer records with their counts as multiplicities (k_entries_to_records), through dst's insert in
+// rounds of whole partitions of at most 2^24 entries, as brisk_hip_reallocate does.  The records leave the kernel in partition
+// order and src's directory counts are their histogram (k_dir_to_hist writes it where k_part_hist would have counted it), so
+// the insert is told that it has one; it still runs its own prefix and k_scatter, which here copies every record to the place
+// it already has (insert_records_impl has no entry for records that are in partition order, and is not changed for one).
+BRISK_API int brisk_hip_merge(brisk_hip_index* dst, brisk_hip_index* src, uint64_t* added) {
+    if (!dst || !src || dst == src) return fail(dst, BRISK_HIP_EINVAL, "merge: two different handles are needed");
+    if (int rc = setop_enter(dst, src, "merge")) return rc;
+    std::lock_guard<std::recursive_mutex> lock_dst(dst->call_mu, std::adopt_lock), lock_src(src->call_mu, std::adopt_lock);
+    brisk_hip_index* h = dst;
+    if (added) *added = 0;
+    int rc;
+    u64 before = 0, after = 0;
+    if ((rc = dir_entries(h, &before))) return rc;
+    const u64 skmers_before = h->nb_skmers;
+    // src's partition sizes (its own scratch; its stream is idle and its lock is held)
+    std::vector<u32> cnt(src->n_parts);
+    hipLaunchKernelGGL(k_dir_counts, dim3(nblocks(src->n_parts, 256)), dim3(256), 0, h->stream, src->ix.dir, src->n_parts, src->d_cur32);
+    if ((rc = launch_check(h, "k_dir_counts"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(cnt.data(), src->d_cur32, src->n_parts * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 round_cap = 1ull << 24;  // entries per round
+    std::vector<u64> base;
+    for (u64 p = 0; p < src->n_parts;) {
+        while (p < src->n_parts && cnt[p] == 0) p++;
+        if (p >= src->n_parts) break;
+        base.clear();
+        u64 total = 0, q = p;
+        while (q < src->n_parts && (total == 0 || total + cnt[q] <= round_cap)) {
+            base.push_back(total);
+            total += cnt[q];
+            q++;
+        }
+        const u64 np = q - p;
+        if (total >= (1ull << 32)) return fail(h, BRISK_HIP_EUNSUPPORTED, "merge: a partition of 2^32 entries or more");
+        if ((rc = ensure(h, h->enum_out, np * 8))) return rc;
+        if ((rc = ensure(h, h->staging, total * h->P.stride * 8))) return rc;
+        u64* d_base = (u64*)h->enum_out.p;
+        HIPCHK(h, hipMemcpyAsync(d_base, base.data(), np * 8, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_entries_to_records, dim3((u32)std::min<u64>(np, 1u << 20)), dim3(64), 0, h->stream, h->P, src->ix, (u32)p, (u32)np, d_base, total, (u64*)h->staging.p);
+        if ((rc = launch_check(h, "k_entries_to_records"))) return rc;
+        HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
+        hipLaunchKernelGGL(k_dir_to_hist, dim3(nblocks(np, 256)), dim3(256), 0, h->stream, src->ix.dir, (u32)p, (u32)np, h->d_hist);
+        if ((rc = launch_check(h, "k_dir_to_hist"))) return rc;
+        if ((rc = insert_records_impl(h, (const u64*)h->staging.p, total, true))) return rc;
+        p = q;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->nb_skmers = skmers_before + src->nb_skmers;  // (the insert counted one record per entry of src)
+    if ((rc = dir_entries(h, &after))) return rc;
+    if (added) *added = after - before;
+    return check_device_flags(h);
+}
+
 BRISK_API int brisk_hip_memory_info(brisk_hip_index* h, uint64_t out[4]) {
     if (!h || !out) return BRISK_HIP_EINVAL;
     std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);

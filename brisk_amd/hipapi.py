@@ -34,7 +34,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU). In-tree output."""
     out = library_path()
     srcs = [os.path.join(HERE, "csrc", f) for f in ("brisk_capi.hip", "brisk_kernels.hip", "brisk_scan.hip", "brisk_partition.hip", "brisk_insert.hip",
-                                                    "brisk_readout.hip", "brisk_device.h")]
+                                                    "brisk_readout.hip", "brisk_setops.hip", "brisk_device.h")]
     srcs.append(os.path.join(ROOT, "include", "brisk_hip.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
@@ -102,7 +102,8 @@ SYMBOLS = [
     "brisk_hip_get_layout", "brisk_hip_insert_reads", "brisk_hip_insert_packed", "brisk_hip_get_reads", "brisk_hip_lookup",
     "brisk_hip_enumerate", "brisk_hip_stats", "brisk_hip_memory_info", "brisk_hip_insert_slack", "brisk_hip_reallocate", "brisk_hip_checksum", "brisk_hip_scan_packed", "brisk_hip_scan_bound", "brisk_hip_route_records",
     "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
-    "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune", "brisk_hip_profile_enable",
+    "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune",
+    "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
 ]
 
@@ -161,6 +162,10 @@ def load() -> C.CDLL:
     L.brisk_hip_count_spectrum.argtypes = [vp, _u64p]
     L.brisk_hip_enumerate_range.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64), u32, u32]
     L.brisk_hip_prune.argtypes = [vp, u32, u32, C.POINTER(u64)]
+    L.brisk_hip_merge.argtypes = [vp, vp, C.POINTER(u64)]
+    L.brisk_hip_intersect.argtypes = [vp, vp, u32, C.POINTER(u64)]
+    L.brisk_hip_subtract.argtypes = [vp, vp, C.POINTER(u64)]
+    L.brisk_hip_compare.argtypes = [vp, vp, _u64p]
     L.brisk_hip_debug_order_keys.argtypes = [vp, _u64p, u64, i32, _u64p]
     L.brisk_hip_profile_enable.argtypes = [vp, i32]
     L.brisk_hip_profile_read.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_char_p), C.POINTER(u64), C.POINTER(C.c_double)]
@@ -330,6 +335,36 @@ class BriskHip:
         v = C.c_uint64()
         self._chk(self.L.brisk_hip_prune(self.h, min_count, max_count, C.byref(v)))
         return v.value
+
+    # ---- set operations (brisk_hip_merge / intersect / subtract / compare): `other` has the same geometry and is left as it is
+    COUNT_RULES = {"left": 0, "min": 1, "max": 2, "sum": 3}
+
+    def merge(self, other: "BriskHip") -> int:
+        """self := self UNION other, counts of shared entries added mod 256; returns the entries new to self"""
+        v = C.c_uint64()
+        self._chk(self.L.brisk_hip_merge(self.h, other.h, C.byref(v)))
+        return v.value
+
+    def intersect(self, other: "BriskHip", count: str = "left") -> int:
+        """keep the entries that are also in `other`; their count is self's ("left"), the "min", the "max" or the "sum"
+        (mod 256) of the two; returns how many entries were removed"""
+        if count not in self.COUNT_RULES:
+            raise ValueError(f"count must be one of {sorted(self.COUNT_RULES)}, not {count!r}")
+        v = C.c_uint64()
+        self._chk(self.L.brisk_hip_intersect(self.h, other.h, self.COUNT_RULES[count], C.byref(v)))
+        return v.value
+
+    def subtract(self, other: "BriskHip") -> int:
+        """remove the entries that are in `other`, whatever the counts; returns how many were removed"""
+        v = C.c_uint64()
+        self._chk(self.L.brisk_hip_subtract(self.h, other.h, C.byref(v)))
+        return v.value
+
+    def compare(self, other: "BriskHip") -> dict:
+        """read-only: entries in both / only here / only there, and over the shared ones the sums of min(count), self's and other's counts"""
+        out = np.zeros(6, np.uint64)
+        self._chk(self.L.brisk_hip_compare(self.h, other.h, out))
+        return dict(zip(("both", "only_self", "only_other", "sum_min", "sum_self", "sum_other"), (int(x) for x in out)))
 
     def stats(self) -> dict:
         v = [C.c_uint64() for _ in range(5)]

@@ -56,6 +56,9 @@
  *                               no reference counterpart (Brisk::stats and Brisk::next are all it has): the abundance
  *                               spectrum, the entries of a count range, and the index without the entries outside one,
  *                               each one pass over the arena on the device
+ *   brisk_hip_merge / brisk_hip_intersect / brisk_hip_subtract / brisk_hip_compare
+ *                               no reference counterpart (the reference holds one index; kmc_tools and jellyfish merge are
+ *                               the usual tools): two indexes of one geometry combined on the device, partition by partition
  *   brisk_hip_checksum          the next()+get() walk of verif_counts (apps/counter.cpp:90-126), reduced
  *                               to a digest on the device
  *   brisk_hip_scan_packed / brisk_hip_route_records / brisk_hip_insert_records
@@ -270,6 +273,37 @@ int brisk_hip_enumerate_range(brisk_hip_index *h, uint64_t *cursor, uint64_t *ou
  * no device memory is returned and memory_bytes / brisk_hip_memory_info do not shrink (brisk_hip_clear, or a new index, do
  * that).  EINVAL if min_count > max_count. */
 int brisk_hip_prune(brisk_hip_index *h, uint32_t min_count, uint32_t max_count, uint64_t *removed);
+
+/* ---- set operations: merge, intersect, subtract, compare (no reference counterpart) ---- */
+/* Two indexes created with the same (k, m, b) and the same partition layout route an identity to the same partition and store it
+ * as the same key bits, so they are combined on the device partition by partition, keys compared as stored.
+ * Identity is (kmer_s, minimizer_idx), as everywhere else.  Presence is what counts: an entry whose stored count wrapped to 0 is
+ * present with count 0.  `src` (and both sides of compare) is left bit for bit as it was: same checksum, same enumeration order.
+ * Both handles must agree in k, m, b, part_bits, ext_bits, cls_bits, cls_width (brisk_hip_layout) and key width, and live on the
+ * same device: otherwise BRISK_HIP_EINVAL, with a message (brisk_hip_last_error of the first handle) that names the field that
+ * differs.  EINVAL also for a null handle, dst == src, an entry-id index or a sharded handle (n_owners > 1) on either side, and
+ * an unknown count_rule; nothing is changed then.  The counter pointers may be NULL.  Pending deferred inserts of BOTH handles
+ * are completed first; both per-handle locks are held for the call (taken together, as brisk_hip_reallocate takes them), and
+ * src's stream is synchronised before dst's stream reads src's arena. */
+enum { BRISK_HIP_COUNT_LEFT = 0, BRISK_HIP_COUNT_MIN = 1, BRISK_HIP_COUNT_MAX = 2, BRISK_HIP_COUNT_SUM = 3 };
+/* dst := dst UNION src; the count of a shared entry is dst + src mod 256; *added = entries new to dst.  Afterwards dst is exactly
+ * the index that inserting src's reads after dst's reads would have given: the same multiset of (kmer, minimizer_idx, count), so
+ * the same checksum, nb_kmers and nb_buckets; nb_skmers becomes dst's plus src's.  Entries already in dst keep their storage
+ * order; where new ones land is not specified.  BRISK_HIP_ENOMEM as for an insert (src's entries go through dst's insert as
+ * one-k-mer records that carry their counts). */
+int brisk_hip_merge(brisk_hip_index *dst, brisk_hip_index *src, uint64_t *added);
+/* dst keeps the entries whose identity is also in src; their count follows count_rule: LEFT dst's, MIN / MAX of the two,
+ * SUM dst + src mod 256.  *removed = entries dst lost.
+ * After intersect and subtract dst is exactly the index that holds the remaining entries, as after brisk_hip_prune: stats
+ * (nb_kmers, nb_buckets, largest_bucket), checksum, enumerate, lookup, every get and every later insert behave so.  Survivors
+ * keep their storage order.  A partition's slice keeps its offset and capacity and no device memory is returned; nb_skmers is
+ * left as it is. */
+int brisk_hip_intersect(brisk_hip_index *dst, brisk_hip_index *src, uint32_t count_rule, uint64_t *removed);
+/* dst loses the entries whose identity is in src, whatever the counts */
+int brisk_hip_subtract(brisk_hip_index *dst, brisk_hip_index *src, uint64_t *removed);
+/* read-only. out[0] entries in both, out[1] only in a, out[2] only in b,
+ * out[3] sum over shared of min(count_a, count_b), out[4] sum of count_a over shared, out[5] sum of count_b over shared */
+int brisk_hip_compare(brisk_hip_index *a, brisk_hip_index *b, uint64_t out[6]);
 
 /* ---- the path cut at the super-k-mer boundary (multi-GPU) ----------------- */
 /* scan: d_records receives up to cap_records records of record_words u64 each;
