@@ -11,7 +11,12 @@
 //   --merge FILE / --subtract FILE / --intersect FILE   each at most once, applied in that order: FILE is counted into a second index with
 //                    the same parameters and combined with the first on the device (brisk_hip_merge / _subtract / _intersect, counts of
 //                    the first kept by --intersect) before --histo, --min-count / --max-count and the dump take effect; one line on stderr
-//                    per operation with the entries added / removed
+//                    per operation with the entries added / removed.  A FILE that is a snapshot (recognised by its magic) is loaded
+//                    (brisk_hip_load) instead of counted
+//   --load FILE      start from the snapshot FILE (brisk_hip_load, slices with room to grow) instead of the empty index, and count FASTA on
+//                    top; a FASTA of "-" means no reads.  k m b must be the file's (exit status 2 otherwise)
+//   --save FILE      write the final index -- after counting, the set operations and, if given, --min-count / --max-count applied as
+//                    brisk_hip_prune -- as a snapshot (brisk_hip_save)
 // Prints nb_kmers / nb_buckets / sum of counts (of the entries dumped); optionally dumps "KMER idx count" lines (dump.txt, "-" for none) and
 // writes the index as a KFF file (a 7th argument: BriskWriter in --facade mode, brisk_write_kff in --bulk mode).
 #include <algorithm>
@@ -30,6 +35,34 @@
 #include "Brisk.hpp"
 #include "brisk_fasta.hpp"
 #include "writer.hpp"
+
+// a snapshot file is told from a FASTA by its first eight bytes
+static bool is_snapshot(const char* path) {
+    char magic[8] = {0};
+    std::ifstream in(path, std::ios::binary);
+    return in.read(magic, 8) && !memcmp(magic, "BRSKSNP1", 8);
+}
+// FILE into `h` for --load / --merge / --subtract / --intersect.  0 fine, 1 failed, 2 the file's k m b are not the command line's.
+static int load_snapshot(brisk_hip_index* h, const char* opt, const char* path, uint8_t k, uint8_t m, uint8_t b, uint32_t flags) {
+    brisk_hip_snapshot_info info{};
+    info.struct_size = sizeof info;
+    if (brisk_hip_snapshot_info_read(path, &info) != BRISK_HIP_OK) {
+        std::cerr << opt << " " << path << ": not a readable snapshot" << std::endl;
+        return 1;
+    }
+    if (info.k != k || info.m != m || info.b != b) {
+        std::cerr << opt << " " << path << ": the snapshot has k " << info.k << " m " << info.m << " b " << info.b << ", the command line k " << (int)k << " m " << (int)m << " b "
+                  << (int)b << std::endl;
+        return 2;
+    }
+    uint64_t n = 0;
+    if (brisk_hip_load(h, path, flags, &n) != BRISK_HIP_OK) {
+        std::cerr << opt << " " << path << ": " << brisk_hip_last_error(h) << std::endl;
+        return 1;
+    }
+    std::cerr << (opt + 2) << " " << path << ": " << n << " entries loaded" << std::endl;
+    return 0;
+}
 
 static std::vector<std::string> read_fasta(const char* path) {
     std::vector<std::string> out;
@@ -128,6 +161,8 @@ int main(int argc_in, char** argv_in) {
     // named options first: what is left is the positional command line as it always was
     std::vector<char*> args;
     const char* histo = nullptr;
+    const char* save_file = nullptr;
+    const char* load_file = nullptr;
     long min_count = 0, max_count = 255;
     bool have_range = false;
     const char* const setop_names[3] = {"--merge", "--subtract", "--intersect"};  // in the order they are applied
@@ -136,7 +171,7 @@ int main(int argc_in, char** argv_in) {
         int setop = -1;
         for (int q = 0; q < 3; q++)
             if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
-        const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count"));
+        const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count"));
         if (!named) {
             args.push_back(argv_in[i]);
             continue;
@@ -147,6 +182,8 @@ int main(int argc_in, char** argv_in) {
         }
         const char* opt = argv_in[i++];
         if (!strcmp(opt, "--histo")) histo = argv_in[i];
+        else if (!strcmp(opt, "--save")) save_file = argv_in[i];
+        else if (!strcmp(opt, "--load")) load_file = argv_in[i];
         else if (setop >= 0) {
             if (setop_file[setop]) {
                 std::cerr << opt << " may be given once" << std::endl;
@@ -167,8 +204,8 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--histo, --min-count, --max-count, --merge, --subtract and --intersect work on the device index: --bulk only" << std::endl;
+    if ((histo || have_range || have_setop || save_file || load_file) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--histo, --min-count, --max-count, --merge, --subtract, --intersect, --save and --load work on the device index: --bulk only" << std::endl;
         return 2;
     }
     if (min_count > max_count) {
@@ -176,7 +213,7 @@ int main(int argc_in, char** argv_in) {
         return 2;
     }
     if (argc < 6) {
-        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] [--subtract FILE] [--intersect FILE])" << std::endl;
+        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] [--subtract FILE] [--intersect FILE] [--load SNAPSHOT] [--save SNAPSHOT]; FASTA \"-\": no reads; a FILE may be a snapshot)" << std::endl;
         return 2;
     }
     const bool bulk = !strcmp(argv[1], "--bulk");
@@ -253,10 +290,15 @@ int main(int argc_in, char** argv_in) {
             // stream the file: a background thread inflates and segments batch i+1 while the GPU counts batch i
             const bool e2e = getenv("BRISK_E2E_JSON") != nullptr;  // bench.py's end-to-end leg: the stage split as one JSON line
             if (e2e) brisk_hip_profile_enable(h, 1);
+            if (load_file) {  // start from the snapshot; slices with room, since the reads are counted on top
+                if (int lrc = load_snapshot(h, "--load", load_file, k, m, b, BRISK_HIP_LOAD_ROOM)) return lrc;
+            }
+            const bool no_reads = !strcmp(argv[2], "-");
             const auto t_start = std::chrono::steady_clock::now();
             double insert_calls_s = 0.0;
             uint64_t n_reads_in = 0, n_bases_in = 0, n_batches = 0;
-            {
+            if (no_reads) brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+            else {
                 FastaBatcher batches(argv[2], batch_bases);
                 FastaBatch bt;
                 while (batches.next(bt)) {
@@ -302,13 +344,17 @@ int main(int argc_in, char** argv_in) {
                     std::cerr << setop_names[q] << ": brisk_hip_create failed: " << rc << std::endl;
                     return 1;
                 }
-                FastaBatcher batches(setop_file[q], batch_bases);
-                FastaBatch bt;
-                while (batches.next(bt))
-                    if ((rc = brisk_hip_insert_reads(other, bt.flat.data(), bt.offs.data(), bt.size())) != BRISK_HIP_OK) {
-                        std::cerr << setop_names[q] << ": " << brisk_hip_last_error(other) << std::endl;
-                        return 1;
-                    }
+                if (is_snapshot(setop_file[q])) {  // the second index from its snapshot: compact, it only serves this operation
+                    if (int lrc = load_snapshot(other, setop_names[q], setop_file[q], k, m, b, BRISK_HIP_LOAD_COMPACT)) return lrc;
+                } else {
+                    FastaBatcher batches(setop_file[q], batch_bases);
+                    FastaBatch bt;
+                    while (batches.next(bt))
+                        if ((rc = brisk_hip_insert_reads(other, bt.flat.data(), bt.offs.data(), bt.size())) != BRISK_HIP_OK) {
+                            std::cerr << setop_names[q] << ": " << brisk_hip_last_error(other) << std::endl;
+                            return 1;
+                        }
+                }
                 uint64_t changed = 0;
                 rc = q == 0 ? brisk_hip_merge(h, other, &changed) : q == 1 ? brisk_hip_subtract(h, other, &changed) : brisk_hip_intersect(h, other, BRISK_HIP_COUNT_LEFT, &changed);
                 if (rc != BRISK_HIP_OK) {
@@ -318,6 +364,22 @@ int main(int argc_in, char** argv_in) {
                 std::cerr << (setop_names[q] + 2) << " " << setop_file[q] << ": " << changed << (q == 0 ? " entries added" : " entries removed") << std::endl;
                 brisk_hip_destroy(other);
                 brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+            }
+            if (save_file) {  // the final index: what the dump below shows is what the file holds
+                if (have_range) {
+                    uint64_t gone = 0;
+                    if (brisk_hip_prune(h, (uint32_t)min_count, (uint32_t)max_count, &gone) != BRISK_HIP_OK) {
+                        std::cerr << "--save: prune: " << brisk_hip_last_error(h) << std::endl;
+                        return 1;
+                    }
+                    brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+                }
+                uint64_t written = 0;
+                if (brisk_hip_save(h, save_file, &written) != BRISK_HIP_OK) {
+                    std::cerr << "--save " << save_file << ": " << brisk_hip_last_error(h) << std::endl;
+                    return 1;
+                }
+                std::cerr << "save " << save_file << ": " << written << " entries written" << std::endl;
             }
             if (histo) {
                 uint64_t spectrum[256];

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -16,6 +17,10 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include "../../include/brisk_hip.h"
 
@@ -2564,6 +2569,460 @@ BRISK_API int brisk_hip_merge(brisk_hip_index* dst, brisk_hip_index* src, uint64
     if ((rc = dir_entries(h, &after))) return rc;
     if (added) *added = after - before;
     return check_device_flags(h);
+}
+
+// ---- snapshots (no reference counterpart): the index to a file and back (brisk_snapshot.hip; format: DESIGN.md section 4.w) ----
+namespace {
+constexpr char kSnapMagic[8] = {'B', 'R', 'S', 'K', 'S', 'N', 'P', '1'};
+constexpr u32 kSnapHeader = 256, kSnapVersion = 1;
+constexpr u64 kSnapBlockEntries = 1ull << 24;  // the round size of brisk_hip_merge
+
+u32 get32(const unsigned char* p) { u32 v; memcpy(&v, p, 4); return v; }
+u64 get64(const unsigned char* p) { u64 v; memcpy(&v, p, 8); return v; }
+void put32(unsigned char* p, u32 v) { memcpy(p, &v, 4); }
+void put64(unsigned char* p, u64 v) { memcpy(p, &v, 8); }
+u64 pad8(u64 n) { return (n + 7) & ~7ull; }
+
+bool read_all(int fd, void* buf, size_t n) {
+    char* p = (char*)buf;
+    while (n) {
+        const ssize_t r = read(fd, p, n);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return false;
+        p += r;
+        n -= (size_t)r;
+    }
+    return true;
+}
+bool write_all(int fd, const void* buf, size_t n) {
+    const char* p = (const char*)buf;
+    while (n) {
+        const ssize_t r = write(fd, p, n);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return false;
+        p += r;
+        n -= (size_t)r;
+    }
+    return true;
+}
+
+// the 256 header bytes -> info; what is wrong with them -> why.  file_bytes: the file's length.  A file that is shorter than its
+// header says: EFORMAT for the header reader (sizes that disagree), short_code for load (EIO: the file ends early).
+int snap_parse_header(const unsigned char* hd, u64 file_bytes, brisk_hip_snapshot_info* s, std::string* why, int short_code = BRISK_HIP_EFORMAT) {
+    if (memcmp(hd, kSnapMagic, 8) != 0) return *why = "not a snapshot file (magic)", BRISK_HIP_EFORMAT;
+    s->version = get32(hd + 8);
+    s->header_bytes = get32(hd + 12);
+    if (s->version != kSnapVersion) return *why = "snapshot format version " + std::to_string(s->version) + " (this library reads version 1)", BRISK_HIP_EFORMAT;
+    if (s->header_bytes != kSnapHeader) return *why = "snapshot header size " + std::to_string(s->header_bytes), BRISK_HIP_EFORMAT;
+    s->k = get32(hd + 16); s->m = get32(hd + 20); s->b = get32(hd + 24); s->data_bytes = get32(hd + 28);
+    s->part_bits = get32(hd + 32); s->ext_bits = get32(hd + 36); s->cls_bits = get32(hd + 40); s->cls_width = get32(hd + 44);
+    s->key_words = get32(hd + 48); s->shift = get32(hd + 52);
+    s->n_entries = get64(hd + 56); s->n_partitions = get64(hd + 64); s->nb_skmers = get64(hd + 72);
+    for (int i = 0; i < 3; i++) s->checksum[i] = get64(hd + 80 + 8 * i);
+    s->n_blocks = get64(hd + 104);
+    s->file_bytes = file_bytes;
+    if (s->data_bytes != 1 || (s->key_words != 1 && s->key_words != 2) || s->part_bits > 30 || s->k > 63)
+        return *why = "snapshot header: inconsistent layout fields", BRISK_HIP_EFORMAT;
+    // the sizes against the file's length: every block has 16 bytes of its own and at most 7 of padding
+    const u64 body = file_bytes - kSnapHeader;
+    bool ok = s->n_partitions <= (1ull << s->part_bits) && s->n_partitions <= s->n_entries && s->n_blocks <= s->n_partitions && (s->n_entries == 0) == (s->n_blocks == 0) &&
+              s->n_entries < (1ull << 56) && s->checksum[0] == s->n_entries;
+    if (ok) {
+        const u64 least = 16 * s->n_blocks + 8 * s->n_partitions + (8ull * s->key_words + 1) * s->n_entries;
+        if (body < least) return *why = "the file ends early: " + std::to_string(file_bytes) + " bytes, the header's sizes need more", short_code;
+        ok = body - least <= 7 * s->n_blocks && file_bytes % 8 == 0;
+    }
+    if (!ok) return *why = "snapshot header: sizes disagree with the file's length (" + std::to_string(file_bytes) + " bytes)", BRISK_HIP_EFORMAT;
+    return BRISK_HIP_OK;
+}
+
+// the envelope of save and load
+int snap_envelope(brisk_hip_index* h, const char* who) {
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": entry-id index (its DATA lives on the host)");
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": sharded index (n_owners > 1)");
+    return BRISK_HIP_OK;
+}
+
+// Two pinned host buffers, each one block of the file plus the tables the kernels need (base, arena_off, tile_lo), and an event each:
+// "the device is done with this buffer".
+struct SnapPin {
+    char* p[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool busy[2] = {false, false};
+    hipStream_t stream = nullptr;
+    explicit SnapPin(hipStream_t s) : stream(s) {}
+    ~SnapPin() {
+        (void)hipStreamSynchronize(stream);  // no copy of this call is in flight when its buffers go
+        for (int i = 0; i < 2; i++) {
+            if (p[i]) hipHostFree(p[i]);
+            if (ev[i]) hipEventDestroy(ev[i]);
+        }
+    }
+};
+int snap_pin_reserve(brisk_hip_index* h, SnapPin& pin, int slot, size_t bytes) {
+    if (!pin.ev[slot]) HIPCHK(h, hipEventCreateWithFlags(&pin.ev[slot], hipEventDisableTiming));
+    if (pin.cap[slot] >= bytes) return BRISK_HIP_OK;
+    if (pin.p[slot]) HIPCHK(h, hipHostFree(pin.p[slot]));
+    pin.p[slot] = nullptr;
+    pin.cap[slot] = 0;
+    if (hipHostMalloc((void**)&pin.p[slot], bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        pin.p[slot] = nullptr;
+        return fail(h, BRISK_HIP_ENOMEM, "snapshot: pinned host buffer of " + std::to_string(bytes >> 20) + " MiB");
+    }
+    pin.cap[slot] = bytes;
+    return BRISK_HIP_OK;
+}
+int snap_pin_wait(brisk_hip_index* h, SnapPin& pin, int slot) {
+    if (pin.busy[slot]) HIPCHK(h, hipEventSynchronize(pin.ev[slot]));
+    pin.busy[slot] = false;
+    return BRISK_HIP_OK;
+}
+
+// where the parts of a block are in a pinned buffer: the file's image first, the kernels' tables behind it
+struct SnapBlock {
+    u64 p_begin = 0, p_end = 0;  // partitions [p_begin, p_end) (save)
+    u64 n_pairs = 0, n_ent = 0;
+    u64 n_tiles() const { return (n_ent + SNAP_TILE - 1) / SNAP_TILE; }
+    u64 off_pairs() const { return 16; }
+    u64 off_keys(u32 kw) const { (void)kw; return 16 + 8 * n_pairs; }
+    u64 off_counts(u32 kw) const { return off_keys(kw) + 8ull * kw * n_ent; }
+    u64 image_bytes(u32 kw) const { return off_counts(kw) + pad8(n_ent); }
+    u64 off_base(u32 kw) const { return image_bytes(kw); }
+    u64 off_arena(u32 kw) const { return off_base(kw) + 8 * n_pairs; }
+    u64 off_tiles(u32 kw) const { return off_arena(kw) + 8 * n_pairs; }
+    u64 tables_bytes() const { return 16 * n_pairs + pad8(4 * (n_tiles() + 1)); }
+    u64 pinned_bytes(u32 kw) const { return image_bytes(kw) + tables_bytes(); }
+};
+
+// the tables of a block from its pairs (in the pinned image): base[], tile_lo[]; returns false on a pair list that is not one
+// (partitions not ascending or outside the index, a zero count, counts that do not add up to the block's entries).
+// room: arena_off[] gives every slice grow_cap(count) entries from `cursor` on, else exactly its count; *need = entries of arena taken.
+bool snap_tables(char* pin, const SnapBlock& bk, u32 kw, u64 n_parts, long long prev_part, bool with_arena, bool room, u64 cursor, u64* need) {
+    const u32* pairs = (const u32*)(pin + bk.off_pairs());
+    u64* base = (u64*)(pin + bk.off_base(kw));
+    u64* arena = (u64*)(pin + bk.off_arena(kw));
+    u32* tiles = (u32*)(pin + bk.off_tiles(kw));
+    u64 at = 0, taken = 0, next_tile = 0;
+    for (u64 p = 0; p < bk.n_pairs; p++) {
+        const u32 part = pairs[2 * p], cnt = pairs[2 * p + 1];
+        if ((long long)part <= prev_part || part >= n_parts || cnt == 0 || at + cnt > bk.n_ent) return false;
+        prev_part = part;
+        base[p] = at;
+        if (with_arena) {
+            arena[p] = cursor + taken;
+            taken += room ? (u64)cnt + (cnt >> 2) + 8 : cnt;  // grow_cap
+        }
+        at += cnt;
+        while (next_tile * SNAP_TILE < at) tiles[next_tile++] = (u32)p;  // the tiles whose first entry this pair holds
+    }
+    if (at != bk.n_ent || next_tile != bk.n_tiles()) return false;
+    tiles[next_tile] = bk.n_pairs ? (u32)(bk.n_pairs - 1) : 0;
+    if (need) *need = taken;
+    return true;
+}
+
+int launch_snapshot_move(brisk_hip_index* h, bool gather, const SnapBlock& bk, const char* d_tab, u64* d_keys, uint8_t* d_counts) {
+    const u32 kw = h->ix.key_words;
+    const uint2* d_pairs = (const uint2*)d_tab;
+    const u64* d_base = (const u64*)(d_tab + 8 * bk.n_pairs);
+    const u64* d_arena = d_base + bk.n_pairs;
+    const u32* d_tiles = (const u32*)(d_arena + bk.n_pairs);
+    const dim3 grid((u32)std::min<u64>(bk.n_tiles(), 8192)), block(256);
+#define LAUNCH_MOVE(G, KW) hipLaunchKernelGGL((k_snapshot_move<G, KW>), grid, block, 0, h->stream, h->ix, d_pairs, d_base, d_arena, d_tiles, (u32)bk.n_pairs, bk.n_ent, d_keys, d_counts)
+    if (gather) {
+        if (kw == 1) LAUNCH_MOVE(true, 1);
+        else LAUNCH_MOVE(true, 2);
+    } else {
+        if (kw == 1) LAUNCH_MOVE(false, 1);
+        else LAUNCH_MOVE(false, 2);
+    }
+#undef LAUNCH_MOVE
+    return launch_check(h, gather ? "k_snapshot_move (gather)" : "k_snapshot_move (scatter)");
+}
+// the device side of a block's tables: [pairs | base | arena_off | tile_lo] in enum_out (enumeration scratch, free between calls)
+int snap_upload_tables(brisk_hip_index* h, const char* pin, const SnapBlock& bk, char** d_tab) {
+    const u32 kw = h->ix.key_words;
+    if (int rc = ensure(h, h->enum_out, 8 * bk.n_pairs + bk.tables_bytes())) return rc;
+    *d_tab = (char*)h->enum_out.p;
+    HIPCHK(h, hipMemcpyAsync(*d_tab, pin + bk.off_pairs(), 8 * bk.n_pairs, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(*d_tab + 8 * bk.n_pairs, pin + bk.off_base(kw), bk.tables_bytes(), hipMemcpyHostToDevice, h->stream));
+    return BRISK_HIP_OK;
+}
+
+int save_impl(brisk_hip_index* h, int fd, uint64_t* entries_written) {
+    const u32 kw = h->ix.key_words;
+    int rc;
+    // the digest and the partition sizes of the index as it is now
+    u64 ck[3];
+    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 24, h->stream));
+    hipLaunchKernelGGL(k_checksum, dim3(2048), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts, h->d_small);
+    if ((rc = launch_check(h, "k_checksum"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 24, hipMemcpyDeviceToHost, h->stream));
+    std::vector<u32> cnt(h->n_parts);
+    hipLaunchKernelGGL(k_dir_counts, dim3(nblocks(h->n_parts, 256)), dim3(256), 0, h->stream, h->ix.dir, h->n_parts, h->d_cur32);  // (d_cur32: per-batch scratch, free between batches)
+    if ((rc = launch_check(h, "k_dir_counts"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(cnt.data(), h->d_cur32, h->n_parts * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 3; i++) ck[i] = h->h_small[i];
+    // blocks of whole partitions: as many as stay within the limit, a larger partition on its own
+    u64 limit = kSnapBlockEntries;
+    if (const char* e = getenv("BRISK_SNAPSHOT_BLOCK")) {
+        const u64 v = strtoull(e, nullptr, 10);
+        if (v) limit = v;
+    }
+    limit = std::min<u64>(limit, 1ull << 31);
+    std::vector<SnapBlock> blocks;
+    u64 n_entries = 0, n_partitions = 0, pin_bytes = 0, dev_entries = 0;
+    for (u64 p = 0; p < h->n_parts;) {
+        while (p < h->n_parts && cnt[p] == 0) p++;
+        if (p >= h->n_parts) break;
+        SnapBlock bk;
+        bk.p_begin = p;
+        while (p < h->n_parts && (bk.n_ent == 0 || bk.n_ent + cnt[p] <= limit)) {
+            if (cnt[p]) {
+                bk.n_pairs++;
+                bk.n_ent += cnt[p];
+                bk.p_end = p + 1;
+            }
+            p++;
+        }
+        p = bk.p_end;
+        n_entries += bk.n_ent;
+        n_partitions += bk.n_pairs;
+        pin_bytes = std::max<u64>(pin_bytes, bk.pinned_bytes(kw));
+        dev_entries = std::max<u64>(dev_entries, bk.n_ent);
+        blocks.push_back(bk);
+    }
+    if (n_entries != ck[0]) return fail(h, BRISK_HIP_EHIP, "save: the directory holds " + std::to_string(n_entries) + " entries, the digest counted " + std::to_string(ck[0]));
+    unsigned char hd[kSnapHeader];
+    memset(hd, 0, sizeof hd);
+    memcpy(hd, kSnapMagic, 8);
+    put32(hd + 8, kSnapVersion); put32(hd + 12, kSnapHeader);
+    put32(hd + 16, h->P.k); put32(hd + 20, h->P.m); put32(hd + 24, h->P.b); put32(hd + 28, 1);
+    put32(hd + 32, h->P.part_bits); put32(hd + 36, h->P.ext_bits); put32(hd + 40, h->P.cls_bits); put32(hd + 44, h->P.cls_width);
+    put32(hd + 48, kw); put32(hd + 52, h->P.shift);
+    put64(hd + 56, n_entries); put64(hd + 64, n_partitions); put64(hd + 72, h->nb_skmers);
+    for (int i = 0; i < 3; i++) put64(hd + 80 + 8 * i, ck[i]);
+    put64(hd + 104, blocks.size());
+    if (!write_all(fd, hd, sizeof hd)) return fail(h, BRISK_HIP_EIO, std::string("save: write: ") + strerror(errno));
+    if (!blocks.empty()) {
+        SnapPin pin(h->stream);
+        // the dense staging of one block on the device: keys, then counts (insert scratch, free between calls).  One is enough:
+        // the gather of block i + 1 follows the copy-out of block i on the stream.
+        const u64 keys_bytes = pad8(8ull * kw * dev_entries);
+        if ((rc = ensure(h, h->staging, keys_bytes + dev_entries + 16))) return rc;
+        u64* d_keys = (u64*)h->staging.p;
+        uint8_t* d_counts = (uint8_t*)h->staging.p + keys_bytes;
+        for (int s = 0; s < 2; s++)
+            if ((rc = snap_pin_reserve(h, pin, s, pin_bytes))) return rc;
+        auto issue = [&](size_t i) -> int {  // gather block i and copy it out, into pinned buffer i & 1
+            const SnapBlock& bk = blocks[i];
+            const int s = (int)(i & 1);
+            char* buf = pin.p[s];
+            put32((unsigned char*)buf, (u32)bk.n_pairs);
+            put32((unsigned char*)buf + 4, 0);
+            put64((unsigned char*)buf + 8, bk.n_ent);
+            u32* pairs = (u32*)(buf + bk.off_pairs());
+            u64 q = 0;
+            for (u64 p = bk.p_begin; p < bk.p_end; p++)
+                if (cnt[p]) {
+                    pairs[2 * q] = (u32)p;
+                    pairs[2 * q + 1] = cnt[p];
+                    q++;
+                }
+            memset(buf + bk.off_counts(kw) + bk.n_ent, 0, pad8(bk.n_ent) - bk.n_ent);
+            if (!snap_tables(buf, bk, kw, h->n_parts, -1, false, false, 0, nullptr)) return fail(h, BRISK_HIP_EHIP, "save: inconsistent block plan");
+            char* d_tab = nullptr;
+            int r;
+            if ((r = snap_upload_tables(h, buf, bk, &d_tab))) return r;
+            if ((r = launch_snapshot_move(h, true, bk, d_tab, d_keys, d_counts))) return r;
+            HIPCHK(h, hipMemcpyAsync(buf + bk.off_keys(kw), d_keys, 8ull * kw * bk.n_ent, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(buf + bk.off_counts(kw), d_counts, bk.n_ent, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipEventRecord(pin.ev[s], h->stream));
+            pin.busy[s] = true;
+            return BRISK_HIP_OK;
+        };
+        if ((rc = issue(0))) return rc;
+        for (size_t i = 0; i < blocks.size(); i++) {
+            if (i + 1 < blocks.size() && (rc = issue(i + 1))) return rc;  // block i + 1 leaves the device while block i goes to the file
+            if ((rc = snap_pin_wait(h, pin, (int)(i & 1)))) return rc;
+            if (!write_all(fd, pin.p[i & 1], blocks[i].image_bytes(kw))) return fail(h, BRISK_HIP_EIO, std::string("save: write: ") + strerror(errno));
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (entries_written) *entries_written = n_entries;
+    return check_device_flags(h);
+}
+
+int load_impl(brisk_hip_index* h, int fd, const brisk_hip_snapshot_info& s, bool room) {
+    const u32 kw = h->ix.key_words;
+    int rc;
+    // the whole arena at once, so that no block waits for a growth: exact for compact slices, an upper bound for slices with room
+    const u64 arena_need = room ? s.n_entries + s.n_entries / 4 + 8 * s.n_partitions : s.n_entries;
+    if (arena_need && (rc = ensure_arena(h, arena_need))) return rc;
+    SnapPin pin(h->stream);
+    u64 cursor = 0, seen = 0, seen_pairs = 0, file_pos = kSnapHeader;
+    long long prev_part = -1;
+    for (u64 i = 0; i < s.n_blocks; i++) {
+        const int slot = (int)(i & 1);
+        if ((rc = snap_pin_wait(h, pin, slot))) return rc;  // the upload of block i - 2 has left this buffer
+        unsigned char bh[16];
+        if (!read_all(fd, bh, 16)) return fail(h, BRISK_HIP_EIO, "load: the file ends inside block " + std::to_string(i));
+        SnapBlock bk;
+        bk.n_pairs = get32(bh);
+        bk.n_ent = get64(bh + 8);
+        file_pos += 16;
+        if (bk.n_pairs == 0 || bk.n_pairs > bk.n_ent || bk.n_ent > s.n_entries - seen || bk.n_pairs > s.n_partitions - seen_pairs || bk.n_ent >= (1ull << 32) ||
+            bk.image_bytes(kw) - 16 > s.file_bytes - file_pos)
+            return fail(h, BRISK_HIP_EFORMAT, "load: block " + std::to_string(i) + ": sizes disagree with the header");
+        if ((rc = snap_pin_reserve(h, pin, slot, bk.pinned_bytes(kw)))) return rc;
+        char* buf = pin.p[slot];
+        if (!read_all(fd, buf + 16, bk.image_bytes(kw) - 16)) return fail(h, BRISK_HIP_EIO, "load: the file ends inside block " + std::to_string(i));
+        file_pos += bk.image_bytes(kw) - 16;
+        u64 need = 0;
+        if (!snap_tables(buf, bk, kw, h->n_parts, prev_part, true, room, cursor, &need)) return fail(h, BRISK_HIP_EFORMAT, "load: block " + std::to_string(i) + ": not a list of ascending non-empty partitions");
+        prev_part = ((const u32*)(buf + bk.off_pairs()))[2 * (bk.n_pairs - 1)];
+        if (cursor + need > h->arena_cap) return fail(h, BRISK_HIP_EFORMAT, "load: the blocks hold more than the header says");
+        char* d_tab = nullptr;
+        if ((rc = snap_upload_tables(h, buf, bk, &d_tab))) return rc;
+        if (!room) {  // a compact slice is its entries: the block's keys and counts ARE the arena's bytes from the cursor on
+            HIPCHK(h, hipMemcpyAsync(h->ix.keys + (u64)kw * cursor, buf + bk.off_keys(kw), 8ull * kw * bk.n_ent, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->ix.counts + cursor, buf + bk.off_counts(kw), bk.n_ent, hipMemcpyHostToDevice, h->stream));
+        } else {
+            const u64 keys_bytes = pad8(8ull * kw * bk.n_ent);
+            if ((rc = ensure(h, h->staging, keys_bytes + bk.n_ent + 16))) return rc;
+            u64* d_keys = (u64*)h->staging.p;
+            uint8_t* d_counts = (uint8_t*)h->staging.p + keys_bytes;
+            HIPCHK(h, hipMemcpyAsync(d_keys, buf + bk.off_keys(kw), 8ull * kw * bk.n_ent, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(d_counts, buf + bk.off_counts(kw), bk.n_ent, hipMemcpyHostToDevice, h->stream));
+            if ((rc = launch_snapshot_move(h, false, bk, d_tab, d_keys, d_counts))) return rc;
+        }
+        hipLaunchKernelGGL(k_snapshot_dir, dim3((u32)std::min<u64>(nblocks(bk.n_pairs, 256), 2048)), dim3(256), 0, h->stream, h->ix.dir, (u32)h->n_parts, (const uint2*)d_tab,
+                           (const u64*)(d_tab + 16 * bk.n_pairs), (u32)bk.n_pairs, room ? 1u : 0u);
+        if ((rc = launch_check(h, "k_snapshot_dir"))) return rc;
+        HIPCHK(h, hipEventRecord(pin.ev[slot], h->stream));
+        pin.busy[slot] = true;
+        cursor += need;
+        seen += bk.n_ent;
+        seen_pairs += bk.n_pairs;
+    }
+    if (seen != s.n_entries || seen_pairs != s.n_partitions || file_pos != s.file_bytes) return fail(h, BRISK_HIP_EFORMAT, "load: the blocks do not add up to the header's counts");
+    // the handle as one that inserted the entries: the bump cursor past the last slice, no private chunk, the bucket bitmap
+    h->h_small[0] = cursor;
+    HIPCHK(h, hipMemcpyAsync(h->ix.cursor, h->h_small, 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->ix.slot_cur, 0, INSERT_SLOTS * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->ix.slot_end, 0, INSERT_SLOTS * 8, h->stream));
+    h->arena_used_host = cursor;
+    h->nb_skmers = s.nb_skmers;
+    h->dir_snapshot_valid = false;
+    HIPCHK(h, hipMemsetAsync(h->ix.bucket_bits, 0, ((h->n_buckets + 31) / 32) * 4, h->stream));
+    if (s.n_entries) {
+        const u64 threads = h->P.shift ? h->n_parts * 64 : h->n_parts;
+        hipLaunchKernelGGL(k_bucket_bits_rebuild, dim3((u32)std::min<u64>(nblocks(threads, 256), 2048)), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts);
+        if ((rc = launch_check(h, "k_bucket_bits_rebuild"))) return rc;
+    }
+    // verify: the digest of what is now in the index against the header's
+    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 24, h->stream));
+    hipLaunchKernelGGL(k_checksum, dim3(2048), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts, h->d_small);
+    if ((rc = launch_check(h, "k_checksum"))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (the pinned word the cursor was copied from is free again)
+    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 24, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 3; i++)
+        if (h->h_small[i] != s.checksum[i]) return fail(h, BRISK_HIP_EFORMAT, "load: digest mismatch: the entries are not the ones that were saved");
+    return check_device_flags(h);
+}
+}  // namespace
+
+BRISK_API int brisk_hip_snapshot_info_read(const char* path, brisk_hip_snapshot_info* out) {
+    if (!path || !out) return BRISK_HIP_EINVAL;
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return BRISK_HIP_EIO;
+    struct stat st;
+    unsigned char hd[kSnapHeader];
+    const bool got = fstat(fd, &st) == 0 && read_all(fd, hd, sizeof hd);
+    close(fd);
+    if (!got) return BRISK_HIP_EIO;
+    brisk_hip_snapshot_info s{};
+    std::string why;
+    const int rc = snap_parse_header(hd, (u64)st.st_size, &s, &why);
+    if (rc) return rc;
+    const u32 size = out->struct_size ? std::min<u32>(out->struct_size, sizeof s) : (u32)sizeof s;
+    s.struct_size = size;
+    memcpy(out, &s, size);
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_save(brisk_hip_index* h, const char* path, uint64_t* entries_written) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!path) return fail(h, BRISK_HIP_EINVAL, "save: path is null");
+    if (int rc = snap_envelope(h, "save")) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    const std::string tmp = std::string(path) + ".tmp." + std::to_string((long long)getpid());
+    const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+    if (fd < 0) return fail(h, BRISK_HIP_EIO, "save: cannot create " + tmp + ": " + strerror(errno));
+    int rc = save_impl(h, fd, entries_written);
+    if (close(fd) != 0 && !rc) rc = fail(h, BRISK_HIP_EIO, std::string("save: close: ") + strerror(errno));
+    if (!rc && rename(tmp.c_str(), path) != 0) rc = fail(h, BRISK_HIP_EIO, "save: rename to " + std::string(path) + ": " + strerror(errno));
+    if (rc) unlink(tmp.c_str());
+    return rc;
+}
+
+BRISK_API int brisk_hip_load(brisk_hip_index* h, const char* path, uint32_t flags, uint64_t* entries_read) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!path) return fail(h, BRISK_HIP_EINVAL, "load: path is null");
+    if (int rc = snap_envelope(h, "load")) return rc;
+    if (flags > BRISK_HIP_LOAD_ROOM) return fail(h, BRISK_HIP_EINVAL, "load: unknown flags");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    if (entries_read) *entries_read = 0;
+    {
+        unsigned long long used = 0;
+        HIPCHK(h, hipMemcpyAsync(&used, h->ix.cursor, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (used || h->arena_used_host || h->nb_skmers) return fail(h, BRISK_HIP_EINVAL, "load: the index is not empty: load into an empty index, or load into a second handle and merge");
+    }
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return fail(h, BRISK_HIP_EIO, "load: cannot open " + std::string(path) + ": " + strerror(errno));
+    struct stat st;
+    unsigned char hd[kSnapHeader];
+    brisk_hip_snapshot_info s{};
+    std::string why;
+    int rc = BRISK_HIP_OK;
+    if (fstat(fd, &st) != 0 || !read_all(fd, hd, sizeof hd)) rc = fail(h, BRISK_HIP_EIO, "load: " + std::string(path) + " is shorter than a snapshot header");
+    else if ((rc = snap_parse_header(hd, (u64)st.st_size, &s, &why, BRISK_HIP_EIO))) fail(h, rc, "load: " + why);
+    if (!rc) {  // the file's layout against the handle's; the message names the first field that differs
+        const BriskParams& P = h->P;
+        const char* field = nullptr;
+        if (s.k != P.k) field = "k";
+        else if (s.m != P.m) field = "m";
+        else if (s.b != P.b) field = "b";
+        else if (s.part_bits != P.part_bits) field = "part_bits";
+        else if (s.ext_bits != P.ext_bits) field = "ext_bits";
+        else if (s.cls_bits != P.cls_bits) field = "cls_bits";
+        else if (s.cls_width != P.cls_width) field = "cls_width";
+        else if (s.key_words != h->ix.key_words) field = "key_words";
+        else if (s.shift != P.shift) field = "shift";
+        if (field) rc = fail(h, BRISK_HIP_EINVAL, std::string("load: the file and the index differ in ") + field);
+    }
+    if (!rc) {
+        rc = load_impl(h, fd, s, flags == BRISK_HIP_LOAD_ROOM);
+        if (rc) {  // back to the empty index, whatever had arrived; the message of the failure stays
+            const std::string msg = h->err;
+            (void)hipStreamSynchronize(h->stream);
+            (void)brisk_hip_clear(h);
+            (void)hipStreamSynchronize(h->stream);
+            h->err = msg;
+        }
+    }
+    close(fd);
+    if (!rc && entries_read) *entries_read = s.n_entries;
+    return rc;
 }
 
 BRISK_API int brisk_hip_memory_info(brisk_hip_index* h, uint64_t out[4]) {

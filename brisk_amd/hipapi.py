@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 _LIB_NAME = os.environ.get("BRISK_HIP_LIB", "libbrisk_hip.so")
 
-STATUS = {0: "OK", 1: "EINVAL", 2: "EUNSUPPORTED", 3: "EHIP", 4: "ENOMEM", 5: "ECAPACITY", 6: "ENODEVICE"}
+STATUS = {0: "OK", 1: "EINVAL", 2: "EUNSUPPORTED", 3: "EHIP", 4: "ENOMEM", 5: "ECAPACITY", 6: "ENODEVICE", 7: "EIO", 8: "EFORMAT"}
 ECAPACITY = 5
 
 
@@ -34,7 +34,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU). In-tree output."""
     out = library_path()
     srcs = [os.path.join(HERE, "csrc", f) for f in ("brisk_capi.hip", "brisk_kernels.hip", "brisk_scan.hip", "brisk_partition.hip", "brisk_insert.hip",
-                                                    "brisk_readout.hip", "brisk_setops.hip", "brisk_device.h")]
+                                                    "brisk_readout.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_device.h")]
     srcs.append(os.path.join(ROOT, "include", "brisk_hip.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
@@ -93,6 +93,12 @@ class _Layout(C.Structure):
                                           "part_bits", "n_owners", "owner_rank", "ext_bits", "cls_bits", "cls_width")]
 
 
+class _SnapshotInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "version", "header_bytes", "k", "m", "b", "data_bytes", "part_bits", "ext_bits", "cls_bits",
+                                          "cls_width", "key_words", "shift")] + \
+               [(n, C.c_uint64) for n in ("n_entries", "n_partitions", "nb_skmers")] + [("checksum", C.c_uint64 * 3), ("n_blocks", C.c_uint64), ("file_bytes", C.c_uint64)]
+
+
 _u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 
@@ -103,7 +109,8 @@ SYMBOLS = [
     "brisk_hip_enumerate", "brisk_hip_stats", "brisk_hip_memory_info", "brisk_hip_insert_slack", "brisk_hip_reallocate", "brisk_hip_checksum", "brisk_hip_scan_packed", "brisk_hip_scan_bound", "brisk_hip_route_records",
     "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
     "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune",
-    "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_profile_enable",
+    "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
+    "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
 ]
 
@@ -166,6 +173,9 @@ def load() -> C.CDLL:
     L.brisk_hip_intersect.argtypes = [vp, vp, u32, C.POINTER(u64)]
     L.brisk_hip_subtract.argtypes = [vp, vp, C.POINTER(u64)]
     L.brisk_hip_compare.argtypes = [vp, vp, _u64p]
+    L.brisk_hip_snapshot_info_read.argtypes = [C.c_char_p, C.POINTER(_SnapshotInfo)]
+    L.brisk_hip_save.argtypes = [vp, C.c_char_p, C.POINTER(u64)]
+    L.brisk_hip_load.argtypes = [vp, C.c_char_p, u32, C.POINTER(u64)]
     L.brisk_hip_debug_order_keys.argtypes = [vp, _u64p, u64, i32, _u64p]
     L.brisk_hip_profile_enable.argtypes = [vp, i32]
     L.brisk_hip_profile_read.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_char_p), C.POINTER(u64), C.POINTER(C.c_double)]
@@ -195,6 +205,19 @@ def kmer_slots(offsets, k: int) -> np.ndarray:
     if len(lens):
         base[1:] = np.cumsum(np.maximum(lens - (k - 1), 0), dtype=np.uint64)
     return base
+
+
+def snapshot_info(path) -> dict:
+    """The header of a snapshot file (brisk_hip_snapshot_info_read; host only: no device, no handle): k, m, b, data_bytes, part_bits,
+    ext_bits, cls_bits, cls_width, key_words, shift, n_entries, n_partitions (the non-empty ones), nb_skmers, checksum (the three
+    words of BriskHip.checksum at save time), n_blocks, version, header_bytes and file_bytes."""
+    info = _SnapshotInfo(C.sizeof(_SnapshotInfo))
+    rc = load().brisk_hip_snapshot_info_read(os.fsencode(path), C.byref(info))
+    if rc:
+        raise BriskHipError(rc, f"snapshot_info({os.fspath(path)!r})")
+    out = {n: getattr(info, n) for n, _ in _SnapshotInfo._fields_ if n not in ("struct_size", "checksum")}
+    out["checksum"] = tuple(int(x) for x in info.checksum)
+    return out
 
 
 _live = weakref.WeakSet()
@@ -365,6 +388,39 @@ class BriskHip:
         out = np.zeros(6, np.uint64)
         self._chk(self.L.brisk_hip_compare(self.h, other.h, out))
         return dict(zip(("both", "only_self", "only_other", "sum_min", "sum_self", "sum_other"), (int(x) for x in out)))
+
+    # ---- snapshots (brisk_hip_save / brisk_hip_load): the index to a file and back, entries as stored
+    def save(self, path) -> int:
+        """write the index to `path` (whole or not at all: written under a temporary name, then renamed); returns the entries
+        written.  The index is left as it was."""
+        v = C.c_uint64()
+        self._chk(self.L.brisk_hip_save(self.h, os.fsencode(path), C.byref(v)))
+        return v.value
+
+    def load(self, path, room: bool = False) -> int:
+        """read a snapshot into this EMPTY index of the same layout; returns the entries read.  room=False: compact slices (the
+        file's bytes go straight into the arena); room=True: every slice with the room an insert would have given it, for an index
+        that keeps growing.  After a failed load the index is empty and usable."""
+        v = C.c_uint64()
+        self._chk(self.L.brisk_hip_load(self.h, os.fsencode(path), 1 if room else 0, C.byref(v)))
+        return v.value
+
+    @classmethod
+    def open(cls, path, device: int = 0, room: bool = False, **kw) -> "BriskHip":
+        """A new handle with the layout of the snapshot at `path`, and the snapshot loaded into it.  The create options come from
+        the header: k, m, b as stored and part_bits = 0 if ext_bits > 0 else part_bits -- brisk_hip_create extends the routing id
+        (ext_bits > 0) only when part_bits was left at its default of 0, and without an extension the stored part_bits is what an
+        explicit part_bits gives (min(part_bits, 2b), 2^24 partitions at most by default).  cls_bits also depends on the environment
+        (BRISK_CLS_BITS): a file saved under another setting is refused by load (EINVAL, the field named).  **kw: further
+        constructor options (max_batch_reads, immediate_inserts, ...)."""
+        info = snapshot_info(path)
+        ix = cls(info["k"], info["m"], info["b"], device=device, part_bits=0 if info["ext_bits"] > 0 else info["part_bits"], **kw)
+        try:
+            ix.load(path, room=room)
+        except Exception:
+            ix.close()
+            raise
+        return ix
 
     def stats(self) -> dict:
         v = [C.c_uint64() for _ in range(5)]

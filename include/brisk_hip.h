@@ -59,6 +59,9 @@
  *   brisk_hip_merge / brisk_hip_intersect / brisk_hip_subtract / brisk_hip_compare
  *                               no reference counterpart (the reference holds one index; kmc_tools and jellyfish merge are
  *                               the usual tools): two indexes of one geometry combined on the device, partition by partition
+ *   brisk_hip_save / brisk_hip_load / brisk_hip_snapshot_info_read
+ *                               no reference counterpart (the reference's index lives as long as its process; jellyfish and KMC
+ *                               keep their databases on disk): the directory and the live entries, as stored, to a file and back
  *   brisk_hip_checksum          the next()+get() walk of verif_counts (apps/counter.cpp:90-126), reduced
  *                               to a digest on the device
  *   brisk_hip_scan_packed / brisk_hip_route_records / brisk_hip_insert_records
@@ -105,7 +108,9 @@ enum {
     BRISK_HIP_EHIP = 3,         /* a HIP runtime call failed; see brisk_hip_last_error */
     BRISK_HIP_ENOMEM = 4,       /* device or host allocation failed */
     BRISK_HIP_ECAPACITY = 5,    /* caller-provided output buffer too small */
-    BRISK_HIP_ENODEVICE = 6     /* no usable gfx950 device */
+    BRISK_HIP_ENODEVICE = 6,    /* no usable gfx950 device */
+    BRISK_HIP_EIO = 7,          /* a snapshot file: open/read/write/rename failed, or the file ends early */
+    BRISK_HIP_EFORMAT = 8       /* not a snapshot, unknown version, inconsistent sizes, digest mismatch */
 };
 
 typedef struct brisk_hip_index brisk_hip_index;
@@ -304,6 +309,48 @@ int brisk_hip_subtract(brisk_hip_index *dst, brisk_hip_index *src, uint64_t *rem
 /* read-only. out[0] entries in both, out[1] only in a, out[2] only in b,
  * out[3] sum over shared of min(count_a, count_b), out[4] sum of count_a over shared, out[5] sum of count_b over shared */
 int brisk_hip_compare(brisk_hip_index *a, brisk_hip_index *b, uint64_t out[6]);
+
+/* ---- snapshots: an index saved to a file and loaded back (no reference counterpart) ---- */
+/* An entry's stored key plus its partition number is its whole identity, so a snapshot is the directory and the live entries of
+ * every slice, as stored: nothing is unhashed, scanned or inserted again.  The file format (version 1, little-endian: a 256-byte
+ * header, then blocks of whole partitions in ascending order) is specified byte by byte in DESIGN.md section 4.w.
+ * All three: EINVAL on a null handle or path.  save and load: EINVAL on an entry-id index and on a sharded handle (n_owners > 1);
+ * pending deferred inserts are completed first; the handle's lock is held for the call; the file streams through two pinned host
+ * buffers of one block each (device <-> host of one block runs under the file I/O of its neighbour), so host memory does not grow
+ * with the index.  BRISK_HIP_EIO: the file system refused; BRISK_HIP_EFORMAT: the bytes are not a consistent version-1 snapshot. */
+enum { BRISK_HIP_LOAD_COMPACT = 0, BRISK_HIP_LOAD_ROOM = 1 };
+typedef struct brisk_hip_snapshot_info {
+    uint32_t struct_size;       /* sizeof(brisk_hip_snapshot_info), set by the caller */
+    uint32_t version, header_bytes;
+    uint32_t k, m, b, data_bytes;
+    uint32_t part_bits, ext_bits, cls_bits, cls_width; /* as brisk_hip_layout */
+    uint32_t key_words;         /* u64 words per stored key: 1 or 2 */
+    uint32_t shift;             /* 2b + ext_bits - part_bits: routing-id bits kept inside a key */
+    uint64_t n_entries, n_partitions /* non-empty ones */, nb_skmers;
+    uint64_t checksum[3];       /* brisk_hip_checksum at save time */
+    uint64_t n_blocks;
+    uint64_t file_bytes;        /* length of the file (not stored in it) */
+} brisk_hip_snapshot_info;
+/* The header of a snapshot file.  Host only: no device and no handle are needed.  EIO: the file cannot be opened or is shorter than
+ * a header; EFORMAT: wrong magic, a version other than 1, or sizes that disagree with the file's length (brisk_hip_load
+ * answers EIO for a file that is shorter than its header says: it ends early). */
+int brisk_hip_snapshot_info_read(const char *path, brisk_hip_snapshot_info *out);
+/* Writes the index to `path`; *entries_written (may be NULL) receives the entries.  The bytes go to `path` plus a temporary suffix
+ * and are renamed at the end: a file under the final name is always whole, and a failed save leaves none behind.  Live entries
+ * only: the room a prune or subtract left inside slices, and abandoned slices, are not written.  The index is left bit for bit as
+ * it was (same checksum, same enumeration order), and two saves of one index are the same bytes.  The writer cuts blocks of about
+ * 2^24 entries; the environment variable BRISK_SNAPSHOT_BLOCK=<entries>, read at each call, sets another limit (a test hook). */
+int brisk_hip_save(brisk_hip_index *h, const char *path, uint64_t *entries_written);
+/* Reads a snapshot into an EMPTY bulk-count index (EINVAL otherwise: "load into an empty index, or load into a second handle and
+ * merge") whose k, m, b, data_bytes, part_bits, ext_bits, cls_bits, cls_width, key_words and shift are the file's (EINVAL otherwise;
+ * the message names the first field that differs).  Afterwards the handle is what it would be had it inserted the entries: every
+ * call behaves so, enumeration order is the saved index's, nb_skmers is the saved one.  flags: BRISK_HIP_LOAD_COMPACT -- every slice
+ * exactly as large as its entries, slices back to back: the file's bytes go straight into the arena, and this is the compaction
+ * that brisk_hip_prune cannot do; BRISK_HIP_LOAD_ROOM -- every slice with the room an insert would have given it, for an index that
+ * keeps growing (an insert into a compact slice moves it).  When the last block is in, the digest of the loaded index is compared
+ * with the header's (EFORMAT on a mismatch).  BRISK_HIP_ENOMEM as for an insert (BRISK_ARENA_LIMIT is honoured).  After any failed
+ * load the handle is the empty index and usable.  *entries_read may be NULL. */
+int brisk_hip_load(brisk_hip_index *h, const char *path, uint32_t flags, uint64_t *entries_read);
 
 /* ---- the path cut at the super-k-mer boundary (multi-GPU) ----------------- */
 /* scan: d_records receives up to cap_records records of record_words u64 each;
