@@ -163,7 +163,9 @@ int main(int argc_in, char** argv_in) {
     const char* histo = nullptr;
     const char* save_file = nullptr;
     const char* load_file = nullptr;
-    long min_count = 0, max_count = 255;
+    const char* profile_file = nullptr;
+    long min_count = 0, max_count = 255, solid = 2;
+    bool have_solid = false;
     bool have_range = false;
     const char* const setop_names[3] = {"--merge", "--subtract", "--intersect"};  // in the order they are applied
     const char* setop_file[3] = {nullptr, nullptr, nullptr};
@@ -171,7 +173,8 @@ int main(int argc_in, char** argv_in) {
         int setop = -1;
         for (int q = 0; q < 3; q++)
             if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
-        const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count"));
+        const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count") ||
+                                    !strcmp(argv_in[i], "--profile") || !strcmp(argv_in[i], "--solid"));
         if (!named) {
             args.push_back(argv_in[i]);
             continue;
@@ -184,6 +187,16 @@ int main(int argc_in, char** argv_in) {
         if (!strcmp(opt, "--histo")) histo = argv_in[i];
         else if (!strcmp(opt, "--save")) save_file = argv_in[i];
         else if (!strcmp(opt, "--load")) load_file = argv_in[i];
+        else if (!strcmp(opt, "--profile")) profile_file = argv_in[i];
+        else if (!strcmp(opt, "--solid")) {  // (above 255: no k-mer is solid)
+            char* end = nullptr;
+            solid = strtol(argv_in[i], &end, 10);
+            if (end == argv_in[i] || *end || solid < 0 || solid > 0xffffffffl) {
+                std::cerr << "--solid: a count threshold, got " << argv_in[i] << std::endl;
+                return 2;
+            }
+            have_solid = true;
+        }
         else if (setop >= 0) {
             if (setop_file[setop]) {
                 std::cerr << opt << " may be given once" << std::endl;
@@ -204,8 +217,12 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop || save_file || load_file) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--histo, --min-count, --max-count, --merge, --subtract, --intersect, --save and --load work on the device index: --bulk only" << std::endl;
+    if ((histo || have_range || have_setop || save_file || load_file || profile_file || have_solid) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--histo, --min-count, --max-count, --merge, --subtract, --intersect, --save, --load, --profile and --solid work on the device index: --bulk only" << std::endl;
+        return 2;
+    }
+    if (have_solid && !profile_file) {
+        std::cerr << "--solid is the threshold of --profile FILE" << std::endl;
         return 2;
     }
     if (min_count > max_count) {
@@ -213,7 +230,7 @@ int main(int argc_in, char** argv_in) {
         return 2;
     }
     if (argc < 6) {
-        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] [--subtract FILE] [--intersect FILE] [--load SNAPSHOT] [--save SNAPSHOT]; FASTA \"-\": no reads; a FILE may be a snapshot)" << std::endl;
+        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] [--subtract FILE] [--intersect FILE] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]]; FASTA \"-\": no reads; a FILE may be a snapshot)" << std::endl;
         return 2;
     }
     const bool bulk = !strcmp(argv[1], "--bulk");
@@ -365,21 +382,47 @@ int main(int argc_in, char** argv_in) {
                 brisk_hip_destroy(other);
                 brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
             }
-            if (save_file) {  // the final index: what the dump below shows is what the file holds
-                if (have_range) {
-                    uint64_t gone = 0;
-                    if (brisk_hip_prune(h, (uint32_t)min_count, (uint32_t)max_count, &gone) != BRISK_HIP_OK) {
-                        std::cerr << "--save: prune: " << brisk_hip_last_error(h) << std::endl;
-                        return 1;
-                    }
-                    brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+            if ((save_file || profile_file) && have_range) {  // the final index: what the dump below shows is what the file holds and what the reads are profiled against
+                uint64_t gone = 0;
+                if (brisk_hip_prune(h, (uint32_t)min_count, (uint32_t)max_count, &gone) != BRISK_HIP_OK) {
+                    std::cerr << (save_file ? "--save" : "--profile") << ": prune: " << brisk_hip_last_error(h) << std::endl;
+                    return 1;
                 }
+                brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+            }
+            if (save_file) {
                 uint64_t written = 0;
                 if (brisk_hip_save(h, save_file, &written) != BRISK_HIP_OK) {
                     std::cerr << "--save " << save_file << ": " << brisk_hip_last_error(h) << std::endl;
                     return 1;
                 }
                 std::cerr << "save " << save_file << ": " << written << " entries written" << std::endl;
+            }
+            if (profile_file) {  // the reads of the input again, in input order, against the final index: one line per read
+                std::ofstream out(profile_file);
+                out << "#read_index\tn_kmers\tn_present\tn_solid\trun_start\trun_len\tmin\tmax\tmedian\tmedian_present\tsum\n";
+                uint64_t read_index = 0;
+                if (!no_reads) {
+                    FastaBatcher batches(argv[2], batch_bases);
+                    FastaBatch bt;
+                    std::vector<brisk_hip_read_profile> recs;
+                    while (batches.next(bt)) {
+                        recs.resize(bt.size());
+                        if (brisk_hip_read_profile_reads(h, bt.flat.data(), bt.offs.data(), bt.size(), (uint32_t)solid, recs.data()) != BRISK_HIP_OK) {
+                            std::cerr << "--profile: " << brisk_hip_last_error(h) << std::endl;
+                            return 1;
+                        }
+                        for (const brisk_hip_read_profile& r : recs)
+                            out << read_index++ << "\t" << r.n_kmers << "\t" << r.n_present << "\t" << r.n_solid << "\t" << r.run_start << "\t" << r.run_len << "\t" << (unsigned)r.min_present
+                                << "\t" << (unsigned)r.max_present << "\t" << (unsigned)r.median << "\t" << (unsigned)r.median_present << "\t" << r.sum << "\n";
+                    }
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "--profile " << profile_file << ": write failed" << std::endl;
+                    return 1;
+                }
+                std::cerr << "profile " << profile_file << ": " << read_index << " reads, solid >= " << solid << std::endl;
             }
             if (histo) {
                 uint64_t spectrum[256];

@@ -31,10 +31,12 @@
 
 namespace {
 
-enum Slot { S_PACK, S_SYNTH, S_COUNT, S_SCAN, S_HIST, S_PSUM, S_TOUCHED, S_SCATTER, S_INSERT, S_QUERY, S_ENUM, S_LOOKUP, S_UPLOAD, S_NSLOTS };
+enum Slot { S_PACK, S_SYNTH, S_COUNT, S_SCAN, S_HIST, S_PSUM, S_TOUCHED, S_SCATTER, S_INSERT, S_QUERY, S_ENUM, S_LOOKUP, S_PROFILE, S_PROFILE_LONG, S_UPLOAD, S_NSLOTS };
 // (the last slot is host wall time, not a kernel: a host batch's bytes from the caller's memory to the packed stream on the device)
 const char* const kSlotNames[S_NSLOTS] = {"k_pack_ascii", "k_synth", "k_count_kmers", "k_scan", "k_part_hist", "k_psum", "k_touched_need",
-                                          "k_scatter", "k_insert", "k_query", "k_enumerate", "k_lookup", "host_upload_and_pack_wall"};
+                                          "k_scatter", "k_insert", "k_query", "k_enumerate", "k_lookup", "k_profile_reads", "k_profile_segments_and_fold",
+                                          "host_upload_and_pack_wall"};
+static_assert(S_NSLOTS <= BRISK_HIP_PROFILE_SLOTS, "brisk_hip_profile_read fills caller arrays of BRISK_HIP_PROFILE_SLOTS");
 
 struct DevBuf {
     void* p = nullptr;
@@ -102,6 +104,7 @@ struct brisk_hip_index {
     DevBuf staging, parted, desc, chunk_buf, tags_a, tags_b, packed_tmp, bases_tmp, starts_tmp, sums_tmp, enum_out, lookup_buf;
     DevBuf packed_tmp2, starts_tmp2;  // the second set of insert_reads_pipelined: one sub-batch is scanned while the next one arrives
     DevBuf anchors, slot_buf, kout_tmp;  // per-position mode (brisk_hip_get_kmers): records' slot anchors, the batch's slot bases, host-call output
+    DevBuf prof_out, prof_plan;          // brisk_hip_read_profile_*: a host call's records; counters, long-read and segment lists, partials
     u32* d_ovf_cnt = nullptr;              // OVF_REGIONS counters of the binned scan's overflow area
     std::vector<u64> owner_cut;            // sharded index: owner o holds partitions [owner_cut[o], owner_cut[o + 1]) (n_owners + 1 entries)
     u32* d_owner_cut = nullptr;            // the same on the device once brisk_hip_set_owner_cuts has replaced the equal ranges (else null)
@@ -1653,7 +1656,7 @@ void free_all(brisk_hip_index* h) {
     hipStreamSynchronize(h->stream);  // nothing of ours may be in flight when the arena is unmapped
     auto fr = [](void* p) { if (p) hipFree(p); };
     for (DevBuf* b : {&h->huge, &h->pend, &h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp, &h->enum_out,
-                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2})
+                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan})
         fr(b->p);
     fr(h->d_coef);
     fr(h->d_tabs);
@@ -2110,6 +2113,135 @@ BRISK_API int brisk_hip_get_kmers_packed(brisk_hip_index* h, const uint32_t* d_p
     return check_device_flags(h);
 }
 
+// ---- per-read abundance profiles (no reference counterpart; kernels: brisk_profile.hip) ----
+static_assert(sizeof(brisk_hip_read_profile) == sizeof(ReadProfile) && offsetof(brisk_hip_read_profile, sum) == offsetof(ReadProfile, sum) &&
+                  offsetof(brisk_hip_read_profile, run_len) == offsetof(ReadProfile, run_len) && offsetof(brisk_hip_read_profile, median_present) == offsetof(ReadProfile, median_present),
+              "the kernels write the C-ABI's record");
+
+// reads above this many slots are reduced in segments of that many: -DBRISK_PROFILE_SEG=<slots> or the environment, read once
+#ifndef BRISK_PROFILE_SEG
+#define BRISK_PROFILE_SEG 4096
+#endif
+static u32 profile_seg() {
+    static const u32 seg = [] {
+        long v = BRISK_PROFILE_SEG;
+        if (const char* e = getenv("BRISK_PROFILE_SEG")) v = atol(e);
+        return (u32)std::min<long>(std::max<long>(v, 1), (long)PROFILE_SEG_MAX);
+    }();
+    return seg;
+}
+// a profile call's batches hold at most this many reads (and at most max_batch_reads): their slots are the call's device memory
+static u64 profile_batch_reads() {
+    static const u64 n = getenv("BRISK_PROFILE_BATCH") && atoll(getenv("BRISK_PROFILE_BATCH")) > 0 ? (u64)atoll(getenv("BRISK_PROFILE_BATCH")) : (1ull << 24);
+    return n;
+}
+struct BatchLimit {  // the handle's lock is held
+    brisk_hip_index* h;
+    u64 saved;
+    explicit BatchLimit(brisk_hip_index* h_) : h(h_), saved(h_->max_batch_reads) { h->max_batch_reads = std::min<u64>(saved, profile_batch_reads()); }
+    ~BatchLimit() { h->max_batch_reads = saved; }
+};
+
+// One batch: its slots into kout_tmp (zeroed; kmers_packed_impl exactly as brisk_hip_get_kmers runs it), then one record per read into
+// d_out[0 .. n_reads).  n_slots: the batch's slots (count_kmers / host_slots).
+static int profile_batch(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u64 n_slots, u32 solid_min, ReadProfile* d_out) {
+    int rc;
+    const u32 seg = profile_seg();
+    // what the table holds: reads that need segments, and a read too long for the record's 32-bit fields
+    if ((rc = ensure(h, h->prof_plan, 64))) return rc;
+    unsigned long long* d_ctr = (unsigned long long*)h->prof_plan.p;
+    HIPCHK(h, hipMemsetAsync(d_ctr, 0, 64, h->stream));
+    const u32 grid_reads = std::max<u32>(std::min<u32>(nblocks(n_reads, 256), 4096), 1);
+    hipLaunchKernelGGL(k_profile_count_long, dim3(grid_reads), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, seg, d_ctr);
+    if ((rc = launch_check(h, "k_profile_count_long"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->h_small, d_ctr, 24, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 n_segs = h->h_small[0], n_longs = h->h_small[1];
+    if (h->h_small[2]) return fail(h, BRISK_HIP_EINVAL, "read_profile: a read of more than 2^32-1 slots does not fit the record");
+    if (n_slots) {
+        if ((rc = ensure(h, h->kout_tmp, n_slots * 2))) return rc;
+        HIPCHK(h, hipMemsetAsync(h->kout_tmp.p, 0, n_slots * 2, h->stream));
+        if ((rc = kmers_packed_impl(h, d_packed, d_starts, n_reads, (uint16_t*)h->kout_tmp.p, n_slots))) return rc;
+    } else {  // nothing to look up; the records still need the table's slot bases (all zero slots: never read)
+        if ((rc = ensure(h, h->slot_buf, (n_reads + 1) * 8))) return rc;
+    }
+    const uint16_t* d_slots = (const uint16_t*)h->kout_tmp.p;
+    const u64* d_slot_base = (const u64*)h->slot_buf.p;
+    {
+        ProfScope ps(h, S_PROFILE);
+        const u32 grid = std::max<u32>((u32)std::min<u64>((n_reads + 3) / 4, 8192), 1);  // a wave per read, grid-stride
+        hipLaunchKernelGGL(k_profile_reads, dim3(grid), dim3(256), 0, h->stream, d_slots, d_starts, d_slot_base, n_reads, (u32)h->P.k, solid_min, seg, d_out);
+        if ((rc = launch_check(h, "k_profile_reads"))) return rc;
+    }
+    if (!n_longs) return BRISK_HIP_OK;
+    // [64 bytes of counters][long reads][segments][partials]
+    const size_t off_longs = 64, off_segs = off_longs + n_longs * sizeof(ProfileLong), off_part = (off_segs + n_segs * sizeof(ProfileSeg) + 15) / 16 * 16;
+    if ((rc = ensure(h, h->prof_plan, off_part + n_segs * sizeof(ProfilePartial)))) return rc;
+    char* b0 = (char*)h->prof_plan.p;
+    d_ctr = (unsigned long long*)b0;
+    HIPCHK(h, hipMemsetAsync(d_ctr, 0, 64, h->stream));  // (ensure may have moved the buffer)
+    ProfileLong* d_longs = (ProfileLong*)(b0 + off_longs);
+    ProfileSeg* d_segs = (ProfileSeg*)(b0 + off_segs);
+    ProfilePartial* d_part = (ProfilePartial*)(b0 + off_part);
+    ProfScope ps(h, S_PROFILE_LONG);
+    hipLaunchKernelGGL(k_profile_plan, dim3(grid_reads), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, seg, d_ctr, d_longs, n_longs, d_segs, n_segs);
+    if ((rc = launch_check(h, "k_profile_plan"))) return rc;
+    hipLaunchKernelGGL(k_profile_segments, dim3((u32)std::min<u64>((n_segs + 3) / 4, 8192)), dim3(256), 0, h->stream, d_slots, d_starts, d_slot_base, (u32)h->P.k, solid_min, seg,
+                       (const ProfileSeg*)d_segs, n_segs, d_part);
+    if ((rc = launch_check(h, "k_profile_segments"))) return rc;
+    hipLaunchKernelGGL(k_profile_fold, dim3((u32)std::min<u64>((n_longs + 3) / 4, 8192)), dim3(256), 0, h->stream, d_starts, (u32)h->P.k, seg, (const ProfileLong*)d_longs, n_longs,
+                       (const ProfilePartial*)d_part, d_out);
+    return launch_check(h, "k_profile_fold");
+}
+
+BRISK_API int brisk_hip_read_profile_reads(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t solid_min,
+                                           brisk_hip_read_profile* out) {
+    if (!h || (n_reads && (!bases || !offsets || !out))) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "read_profile_reads on a sharded index sees one bucket range only");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "read_profile_reads on an entry-id index: DATA lives with the caller (find_kmers)");
+    for (u64 r = 0; r < n_reads; r++) {
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (offsets[r + 1] - offsets[r] >= PROFILE_MAX_SLOTS + h->P.k) return fail(h, BRISK_HIP_EINVAL, "read_profile: a read of more than 2^32-1 slots does not fit the record");
+    }
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    BatchLimit limit(h);
+    int rc = for_each_host_batch(h, bases, offsets, n_reads, [&](u64 r0, u64 nr) -> int {
+        int rc2;
+        if ((rc2 = ensure(h, h->prof_out, nr * sizeof(ReadProfile)))) return rc2;
+        if ((rc2 = profile_batch(h, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, nr, host_slots(offsets, r0, r0 + nr, h->P.k), solid_min, (ReadProfile*)h->prof_out.p)))
+            return rc2;
+        HIPCHK(h, hipMemcpyAsync(out + r0, h->prof_out.p, nr * sizeof(ReadProfile), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    });
+    if (rc) return rc;
+    return check_device_flags(h);
+}
+
+BRISK_API int brisk_hip_read_profile_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min,
+                                            brisk_hip_read_profile* d_out) {
+    if (!h || (n_reads && (!d_packed || !d_starts || !d_out))) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "read_profile_packed on a sharded index sees one bucket range only");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "read_profile_packed on an entry-id index: DATA lives with the caller (find_kmers)");
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    const u64 batch = std::min<u64>(h->max_batch_reads, profile_batch_reads());
+    for (u64 r0 = 0; r0 < n_reads; r0 += batch) {
+        const u64 nb = std::min<u64>(batch, n_reads - r0);
+        u64 ns = 0;
+        int rc;
+        if ((rc = count_kmers(h, d_starts + r0, nb, &ns))) return rc;  // (EINVAL on a table that does not ascend)
+        if ((rc = profile_batch(h, d_packed, d_starts + r0, nb, ns, solid_min, (ReadProfile*)d_out + r0))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return check_device_flags(h);
+}
+
 BRISK_API int brisk_hip_lookup(brisk_hip_index* h, const uint64_t* kmer_lo, const uint64_t* kmer_hi, const uint8_t* minimizer_idx, uint64_t n,
                                uint8_t* out_data, uint8_t* out_found) {
     if (!h || (n && (!kmer_lo || !kmer_hi || !minimizer_idx || !out_data || !out_found))) return BRISK_HIP_EINVAL;
@@ -2312,7 +2444,7 @@ BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t
     if (memory_bytes) {
         u64 m = h->arena_cap * (8ull * h->ix.key_words + 1) + h->n_parts * 16 + (h->n_buckets + 7) / 8 + (h->n_parts + 1) * 20;
         for (const DevBuf* b : {&h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp,
-                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2})
+                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan})
             m += b->bytes;
         *memory_bytes = m;
     }

@@ -34,7 +34,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU). In-tree output."""
     out = library_path()
     srcs = [os.path.join(HERE, "csrc", f) for f in ("brisk_capi.hip", "brisk_kernels.hip", "brisk_scan.hip", "brisk_partition.hip", "brisk_insert.hip",
-                                                    "brisk_readout.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_device.h")]
+                                                    "brisk_readout.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_device.h")]
     srcs.append(os.path.join(ROOT, "include", "brisk_hip.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
@@ -109,6 +109,7 @@ SYMBOLS = [
     "brisk_hip_enumerate", "brisk_hip_stats", "brisk_hip_memory_info", "brisk_hip_insert_slack", "brisk_hip_reallocate", "brisk_hip_checksum", "brisk_hip_scan_packed", "brisk_hip_scan_bound", "brisk_hip_route_records",
     "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
     "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune",
+    "brisk_hip_read_profile_reads", "brisk_hip_read_profile_packed",
     "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
     "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
@@ -142,6 +143,9 @@ def load() -> C.CDLL:
     _u16p = np.ctypeslib.ndpointer(dtype=np.uint16, flags="C_CONTIGUOUS")
     L.brisk_hip_get_kmers.argtypes = [vp, _u8p, _u64p, u64, _u16p, u64]
     L.brisk_hip_get_kmers_packed.argtypes = [vp, vp, vp, u64, vp]
+    _profp = np.ctypeslib.ndpointer(dtype=READ_PROFILE_DTYPE, flags="C_CONTIGUOUS")
+    L.brisk_hip_read_profile_reads.argtypes = [vp, _u8p, _u64p, u64, u32, _profp]
+    L.brisk_hip_read_profile_packed.argtypes = [vp, vp, vp, u64, u32, vp]
     L.brisk_hip_enumerate.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64)]
     L.brisk_hip_stats.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.brisk_hip_checksum.argtypes = [vp, _u64p]
@@ -205,6 +209,47 @@ def kmer_slots(offsets, k: int) -> np.ndarray:
     if len(lens):
         base[1:] = np.cumsum(np.maximum(lens - (k - 1), 0), dtype=np.uint64)
     return base
+
+
+# brisk_hip_read_profile (include/brisk_hip.h): 32 bytes, little-endian, no padding
+READ_PROFILE_DTYPE = np.dtype([("n_kmers", "<u4"), ("n_present", "<u4"), ("n_solid", "<u4"), ("run_start", "<u4"), ("run_len", "<u4"),
+                               ("min_present", "u1"), ("max_present", "u1"), ("median", "u1"), ("median_present", "u1"), ("sum", "<u8")])
+assert READ_PROFILE_DTYPE.itemsize == 32
+
+
+def profile_from_slots(counts, found, base, solid_min: int) -> np.ndarray:
+    """The record of brisk_hip_read_profile_reads computed on the host from the three outputs of BriskHip.get_kmers (counts
+    uint8[n_slots], found bool[n_slots], base uint64[n_reads + 1]): the definition of every field, written out.  No device needed.
+    A slot is solid when it is found and its count is >= solid_min (so none is when solid_min > 255); medians are lower medians,
+    sorted[(n - 1) // 2]; `median` counts an absent slot as 0; the run is the first of the longest runs of consecutive solid slots."""
+    counts = np.asarray(counts, np.uint8)
+    found = np.asarray(found, bool)
+    base = np.asarray(base, np.uint64).astype(np.int64)
+    out = np.zeros(len(base) - 1, READ_PROFILE_DTYPE)
+    for r in range(len(base) - 1):
+        c, f = counts[base[r]:base[r + 1]].astype(np.int64), found[base[r]:base[r + 1]]
+        n = len(c)
+        if n > 0xffffffff:
+            raise ValueError("a read of more than 2^32 - 1 slots does not fit the record")
+        rec = out[r]
+        rec["n_kmers"] = n
+        if n == 0:
+            continue
+        present = c[f]
+        solid = f & (c >= solid_min)
+        rec["n_present"] = len(present)
+        rec["n_solid"] = int(solid.sum())
+        rec["median"] = np.sort(np.where(f, c, 0))[(n - 1) // 2]
+        if len(present):
+            rec["min_present"], rec["max_present"] = present.min(), present.max()
+            rec["median_present"] = np.sort(present)[(len(present) - 1) // 2]
+            rec["sum"] = int(present.sum())
+        if solid.any():  # runs: where the padded mask rises and falls
+            edge = np.diff(np.concatenate(([0], solid.astype(np.int8), [0])))
+            starts, ends = np.nonzero(edge == 1)[0], np.nonzero(edge == -1)[0]
+            best = int(np.argmax(ends - starts))  # argmax returns the first of equal maxima
+            rec["run_start"], rec["run_len"] = starts[best], ends[best] - starts[best]
+    return out
 
 
 def snapshot_info(path) -> dict:
@@ -309,6 +354,18 @@ class BriskHip:
         self._chk(self.L.brisk_hip_get_kmers(self.h, flat, offs, len(offs) - 1, out, total))
         out = out[:total]
         return (out & 0xff).astype(np.uint8), (out & 0x100) != 0, base
+
+    def read_profile(self, seqs: Sequence, solid_min: int = 2) -> np.ndarray:
+        """One abundance record per read (brisk_hip_read_profile_reads): READ_PROFILE_DTYPE[n_reads] -- n_kmers, n_present, n_solid
+        (present and count >= solid_min), the first longest run of solid slots (run_start, run_len), min / max / lower median of
+        the present counts, the lower median over all slots (absent = 0) and the sum.  What profile_from_slots(*get_kmers(seqs),
+        solid_min) gives, reduced on the device: the slots never reach the host."""
+        flat, offs = _pack_reads(seqs)
+        out = np.zeros(len(offs) - 1, READ_PROFILE_DTYPE)
+        if len(flat) == 0:
+            flat = np.zeros(1, np.uint8)
+        self._chk(self.L.brisk_hip_read_profile_reads(self.h, flat, offs, len(offs) - 1, solid_min, out if len(out) else np.zeros(1, READ_PROFILE_DTYPE)))
+        return out
 
     def lookup(self, lo, hi, idx) -> Tuple[np.ndarray, np.ndarray]:
         lo = np.ascontiguousarray(lo, np.uint64)
@@ -467,6 +524,10 @@ class BriskHip:
     def get_kmers_packed(self, d_packed: int, d_starts: int, n_reads: int, d_out: int):
         """per-k-mer answers (brisk_hip_get_kmers), reads and uint16 slots on the device (d_out sized by kmer_slots)"""
         self._chk(self.L.brisk_hip_get_kmers_packed(self.h, d_packed, d_starts, n_reads, d_out))
+
+    def read_profile_packed(self, d_packed: int, d_starts: int, n_reads: int, d_out: int, solid_min: int = 2):
+        """per-read abundance records (brisk_hip_read_profile_packed), reads and records (32 bytes a read, READ_PROFILE_DTYPE) on the device"""
+        self._chk(self.L.brisk_hip_read_profile_packed(self.h, d_packed, d_starts, n_reads, solid_min, d_out))
 
     def scan_bound(self, d_starts: int, n_reads: int) -> int:
         out = C.c_uint64()

@@ -46,6 +46,10 @@
  *                               Brisk::get_sequence (brisk/Brisk.hpp:28: one DATA* per k-mer of the sequence;
  *                               declared, never defined) as Brisk::get_superkmer (brisk/Brisk.hpp:102-118) over
  *                               every vector SuperKmerEnumerator yields; _packed: reads and answers on the device
+ *   brisk_hip_read_profile_reads / brisk_hip_read_profile_packed
+ *                               no reference counterpart (the reference answers one k-mer or one super-k-mer at a time; khmer's
+ *                               normalize-by-median and trim-low-abund are the usual tools): the answers of brisk_hip_get_kmers
+ *                               reduced on the device to one abundance record per read
  *   brisk_hip_lookup            Brisk::get (brisk/Brisk.hpp:64-69)
  *   brisk_hip_enumerate         Brisk::next / restart_kmer_enumeration
  *                               (brisk/Brisk.hpp:166-179, brisk/DenseMenuYo.hpp:476-521)
@@ -212,6 +216,41 @@ int brisk_hip_get_kmers(brisk_hip_index *h, const char *bases, const uint64_t *o
 /* DEVICE reads (layout of brisk_hip_insert_packed); d_out DEVICE, sized to the total slots. */
 int brisk_hip_get_kmers_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
                                uint16_t *d_out);
+
+/* Per-read abundance profile: the answers of brisk_hip_get_kmers reduced, on the device, to one record per read (no reference
+ * counterpart).  A slot is PRESENT when its k-mer is in the index (the 0x100 bit of get_kmers) and SOLID when it is present and its
+ * stored count is >= solid_min.  Stored counts are mod 256: an entry whose count wrapped to 0 is present with count 0, and solid only
+ * when solid_min == 0; solid_min > 255 means that no slot is solid.  `median` is the lower median over ALL slots of the read, an
+ * absent slot counting 0 (what digital normalisation compares with its cutoff); `median_present` leaves the absent slots out.  The
+ * run is the longest stretch of consecutive solid slots, the FIRST one when several are equally long: nucleotides
+ * [run_start, run_start + run_len + k - 1) of the read are covered by solid k-mers only (abundance trimming keeps them).
+ * Semantics are those of brisk_hip_get_kmers: the same read layouts; a k-mer is looked up under the (kmer_s, minimizer_idx) that the
+ * scan of the WHOLE read gives it; every slot is answered (the stop of brisk_hip_get_reads at a returned minimizer of 0 does not
+ * apply); pending deferred inserts are completed first; the answer does not depend on max_batch_reads, on how the call is batched or
+ * on which kernels run.  A read shorter than k gets the all-zero record.  EINVAL on a sharded index (n_owners > 1), on an entry-id
+ * index, on offsets that do not ascend and on a read of more than 2^32 - 1 slots.  The slots never leave the library: they are
+ * written for one internal batch at a time into scratch memory of the handle and reduced there, so device memory grows with a
+ * batch's slots (2 bytes each; a batch is at most min(max_batch_reads, BRISK_PROFILE_BATCH = 2^24) reads), not with the call's, and
+ * the caller never allocates a slot array.  Reads of more than BRISK_PROFILE_SEG slots (environment, read once per process;
+ * default 4096) are reduced in segments of that many slots and their partial results folded in order; the record is the same. */
+typedef struct brisk_hip_read_profile {   /* 32 bytes, little-endian, no padding */
+    uint32_t n_kmers;        /* slots of the read: max(0, len - k + 1) */
+    uint32_t n_present;      /* slots whose k-mer is in the index */
+    uint32_t n_solid;        /* present and stored count >= solid_min */
+    uint32_t run_start;      /* longest run of consecutive solid slots: first slot (nucleotide position) ... */
+    uint32_t run_len;        /* ... and its length; the FIRST such run on ties; 0, 0 when n_solid == 0 */
+    uint8_t  min_present;    /* smallest / largest stored count over present slots; 0, 0 when n_present == 0 */
+    uint8_t  max_present;
+    uint8_t  median;         /* lower median over ALL slots, an absent slot counting 0: sorted[(n_kmers - 1) / 2]; 0 when n_kmers == 0 */
+    uint8_t  median_present; /* lower median over present slots only; 0 when n_present == 0 */
+    uint64_t sum;            /* sum of the stored counts of present slots */
+} brisk_hip_read_profile;
+/* HOST reads (layout of brisk_hip_get_reads); out[n_reads] HOST: 32 bytes a read come back */
+int brisk_hip_read_profile_reads(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
+                                 uint32_t solid_min, brisk_hip_read_profile *out);
+/* DEVICE reads (layout of brisk_hip_insert_packed); d_out[n_reads] DEVICE */
+int brisk_hip_read_profile_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                                  uint32_t solid_min, brisk_hip_read_profile *d_out);
 
 /* point lookups of UNHASHED (kmer_s, minimizer_idx) pairs, as Brisk::get takes them.
  * HOST arrays; out_found[i] in {0,1}; out_data[i] valid when found. */
