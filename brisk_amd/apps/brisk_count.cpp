@@ -7,6 +7,10 @@
 //                                                 the first reads of batches that are already in; prints what every get saw
 // --bulk only, anywhere on the command line (taken out before the positional arguments are read):
 //   --histo FILE     the count spectrum (brisk_hip_count_spectrum): 256 lines "count<TAB>entries", empty bins included
+//   --saturate       counts stop at 255 instead of wrapping (brisk_hip_options.count_mode = BRISK_HIP_COUNTS_SATURATE): the index, and the
+//                    second index of --merge / --subtract / --intersect FILE, are created in that mode; --load FILE (or a set operation's
+//                    FILE) of a snapshot of the other mode fails with the library's message.  The --histo file then starts with a
+//                    "#" comment line saying so, and its last line is "255+<TAB>entries": the entries seen 255 times or more
 //   --min-count N / --max-count N   the dump and the KFF file hold only the entries with N <= count (<= N): brisk_hip_enumerate_range
 //   --merge FILE / --subtract FILE / --intersect FILE   each at most once, applied in that order: FILE is counted into a second index with
 //                    the same parameters and combined with the first on the device (brisk_hip_merge / _subtract / _intersect, counts of
@@ -167,9 +171,22 @@ int main(int argc_in, char** argv_in) {
     long min_count = 0, max_count = 255, solid = 2;
     bool have_solid = false;
     bool have_range = false;
+    bool saturate = false;
     const char* const setop_names[3] = {"--merge", "--subtract", "--intersect"};  // in the order they are applied
     const char* setop_file[3] = {nullptr, nullptr, nullptr};
+    static const char* const usage =
+        "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] "
+        "[--subtract FILE] [--intersect FILE] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]]; FASTA \"-\": no reads; a FILE may be a snapshot)\n"
+        "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+";
     for (int i = 0; i < argc_in; i++) {
+        if (i > 0 && (!strcmp(argv_in[i], "--help") || !strcmp(argv_in[i], "-h"))) {
+            std::cout << usage << std::endl;
+            return 0;
+        }
+        if (i > 0 && !strcmp(argv_in[i], "--saturate")) {
+            saturate = true;
+            continue;
+        }
         int setop = -1;
         for (int q = 0; q < 3; q++)
             if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
@@ -217,8 +234,8 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop || save_file || load_file || profile_file || have_solid) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--histo, --min-count, --max-count, --merge, --subtract, --intersect, --save, --load, --profile and --solid work on the device index: --bulk only" << std::endl;
+    if ((histo || have_range || have_setop || save_file || load_file || profile_file || have_solid || saturate) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --save, --load, --profile and --solid work on the device index: --bulk only" << std::endl;
         return 2;
     }
     if (have_solid && !profile_file) {
@@ -230,7 +247,7 @@ int main(int argc_in, char** argv_in) {
         return 2;
     }
     if (argc < 6) {
-        std::cerr << "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] [--subtract FILE] [--intersect FILE] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]]; FASTA \"-\": no reads; a FILE may be a snapshot)" << std::endl;
+        std::cerr << usage << std::endl;
         return 2;
     }
     const bool bulk = !strcmp(argv[1], "--bulk");
@@ -298,6 +315,7 @@ int main(int argc_in, char** argv_in) {
         } else {
             brisk_hip_options o{};
             o.struct_size = sizeof o;
+            o.count_mode = saturate ? BRISK_HIP_COUNTS_SATURATE : BRISK_HIP_COUNTS_WRAP;  // (also the second index's of a set operation)
             brisk_hip_index* h = nullptr;
             int rc = brisk_hip_create(&h, k, m, b, 1, params.dede->coef(), &o);
             if (rc != BRISK_HIP_OK) {
@@ -431,7 +449,10 @@ int main(int argc_in, char** argv_in) {
                     return 1;
                 }
                 std::ofstream out(histo);
-                for (int c = 0; c < 256; c++) out << c << "\t" << spectrum[c] << "\n";
+                // a saturating index: no count wrapped, and the last bin holds everything seen 255 times or more
+                if (saturate) out << "# counts saturate (--saturate): the last line, 255+, is the entries seen 255 times or more\n";
+                for (int c = 0; c < 255; c++) out << c << "\t" << spectrum[c] << "\n";
+                out << (saturate ? "255+" : "255") << "\t" << spectrum[255] << "\n";
             }
             uint64_t cursor = 0, n = 0;
             const uint64_t cap = 1u << 20;

@@ -79,6 +79,7 @@ struct brisk_hip_index {
     size_t scan_lds = 0;
     bool scan_v1 = false;       // BRISK_SCAN_V1=1: the plain restatement kernel
     bool entry_ids = false;
+    u32 count_mode = 0;         // brisk_hip_options.count_mode: BRISK_HIP_COUNTS_WRAP, or _SATURATE (the insert kernels' SAT instantiations)
     bool use_vmm = false;
     bool scan_hist_valid = false;  // d_hist holds the per-partition histogram of the last brisk_hip_scan_packed
     u64 arena_limit = 0;        // BRISK_ARENA_LIMIT (entries): artificial ceiling, for tests of the out-of-memory path
@@ -580,26 +581,26 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         };
         // instantiations with the record geometry (nw, k - b, routing-id bits kept in the key) as constants, for the
         // common parameter sets under the default partition layout; anything else takes the generic body
+        // (every one of them twice: counts that wrap, and -- SAT -- counts that stop at 255; the mode is the handle's)
+        const bool sat = h->count_mode == BRISK_HIP_COUNTS_SATURATE;
+#define LAUNCH_INSERT_K(KERNEL, NW, KB, SH, SAT)                                                                                                                    \
+    {                                                                                                                                                               \
+        const dim3 grid(std::min<u32>(batches, resident((const void*)KERNEL<NW, KB, SH, SAT>)));                                                                  \
+        hipLaunchKernelGGL((KERNEL<NW, KB, SH, SAT>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix,                         \
+                           (u32*)(h->d_small + 6));                                                                                                                 \
+    }
 #define LAUNCH_INSERT(NW, KB, SH)                                                                                                                                   \
     {                                                                                                                                                               \
-        if (big) {                                                                                                                                                  \
-            const dim3 grid(std::min<u32>(batches, resident((const void*)k_insert_big<NW, KB, SH>)));                                                             \
-            hipLaunchKernelGGL((k_insert_big<NW, KB, SH>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix,                    \
-                               (u32*)(h->d_small + 6));                                                                                                             \
-        } else {                                                                                                                                                    \
-            const dim3 grid(std::min<u32>(batches, resident((const void*)k_insert<NW, KB, SH>)));                                                                 \
-            hipLaunchKernelGGL((k_insert<NW, KB, SH>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix,                        \
-                               (u32*)(h->d_small + 6));                                                                                                             \
-        }                                                                                                                                                           \
+        if (big && sat) LAUNCH_INSERT_K(k_insert_big, NW, KB, SH, true)                                                                                             \
+        else if (big) LAUNCH_INSERT_K(k_insert_big, NW, KB, SH, false)                                                                                              \
+        else if (sat) LAUNCH_INSERT_K(k_insert, NW, KB, SH, true)                                                                                                   \
+        else LAUNCH_INSERT_K(k_insert, NW, KB, SH, false)                                                                                                           \
     }
 #define LAUNCH_INSERT_FAST(NW, KB, SH)                                                                                                                              \
     {                                                                                                                                                               \
         if (big) LAUNCH_INSERT(NW, KB, SH)                                                                                                                          \
-        else {                                                                                                                                                      \
-            const dim3 grid(std::min<u32>(batches, resident((const void*)k_insert_fast<NW, KB, SH>)));                                                            \
-            hipLaunchKernelGGL((k_insert_fast<NW, KB, SH>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix,                   \
-                               (u32*)(h->d_small + 6));                                                                                                             \
-        }                                                                                                                                                           \
+        else if (sat) LAUNCH_INSERT_K(k_insert_fast, NW, KB, SH, true)                                                                                              \
+        else LAUNCH_INSERT_K(k_insert_fast, NW, KB, SH, false)                                                                                                      \
     }
         static const bool generic_only = getenv("BRISK_INSERT_GENERIC") != nullptr;  // A/B and tests: force the run-time body
         if (!generic_only && P.nw == 3 && P.kb == 49 && P.shift == 4) LAUNCH_INSERT_FAST(3, 49, 4)        // k63 m21 b14
@@ -613,12 +614,15 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         else LAUNCH_INSERT(0, 0, 0)
 #undef LAUNCH_INSERT_FAST
 #undef LAUNCH_INSERT
+#undef LAUNCH_INSERT_K
         if ((rc = launch_check(h, big ? "k_insert_big" : "k_insert"))) return rc;
         if (h->trace) fprintf(stderr, "[brisk_hip] path: insert of %llu records (%s layout, histogram %s) into %u partitions: %s, %u partitions to k_insert_huge\n", (unsigned long long)n_rec,
                               bl ? "binned" : "classic", have_hist ? "from the scan" : "counted here", n_touched, big ? "k_insert_big (in-place collapse for partitions of > 128 records)" : "k_insert", n_huge);
         if (n_huge) {
-            hipLaunchKernelGGL(k_insert_huge, dim3(std::min<u32>(n_huge, 256u)), dim3(HG_THREADS), 0, h->stream, P, src, (const PartDesc*)h->desc.p, (const u32*)h->huge.p + 1,
-                               (const u32*)h->huge.p, h->ix);
+            if (sat) hipLaunchKernelGGL(k_insert_huge<true>, dim3(std::min<u32>(n_huge, 256u)), dim3(HG_THREADS), 0, h->stream, P, src, (const PartDesc*)h->desc.p,
+                                        (const u32*)h->huge.p + 1, (const u32*)h->huge.p, h->ix);
+            else hipLaunchKernelGGL(k_insert_huge<false>, dim3(std::min<u32>(n_huge, 256u)), dim3(HG_THREADS), 0, h->stream, P, src, (const PartDesc*)h->desc.p,
+                                    (const u32*)h->huge.p + 1, (const u32*)h->huge.p, h->ix);
             if ((rc = launch_check(h, "k_insert_huge"))) return rc;
         }
     }
@@ -1709,13 +1713,17 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
     // Parameters contract (parameters.hpp:19-22, Brisk.hpp:50-51, counter.cpp:32)
     if (!(b >= 1 && b <= m && m < k && k <= 63 && (m & 1) && m <= 31) || !coef_table) return BRISK_HIP_EINVAL;
     if (b > 16) return BRISK_HIP_EUNSUPPORTED;  // bucket ids are 32-bit, as the reference's uint32_t directory (DenseMenuYo.hpp:37,105)
-    if (data_bytes != 1 && !(opt && opt->struct_size >= sizeof(brisk_hip_options) && opt->entry_ids)) return BRISK_HIP_EUNSUPPORTED;
     brisk_hip_options o{};
     if (opt) memcpy(&o, opt, std::min<size_t>(opt->struct_size ? opt->struct_size : sizeof(o), sizeof(o)));
+    if (data_bytes != 1 && !o.entry_ids) return BRISK_HIP_EUNSUPPORTED;  // (a struct_size that ends before entry_ids leaves it 0)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || o.device < 0 || o.device >= ndev) return BRISK_HIP_ENODEVICE;
+    // (a caller that passes the struct as it was before count_mode existed leaves it 0: counts wrap)
+    if (o.count_mode != BRISK_HIP_COUNTS_WRAP && o.count_mode != BRISK_HIP_COUNTS_SATURATE) return BRISK_HIP_EINVAL;
+    if (o.count_mode == BRISK_HIP_COUNTS_SATURATE && o.entry_ids) return BRISK_HIP_EINVAL;  // that DATA lives with the caller: nothing here counts
     brisk_hip_index* h = new (std::nothrow) brisk_hip_index();
     if (!h) return BRISK_HIP_ENOMEM;
+    h->count_mode = o.count_mode;
 
     BriskParams& P = h->P;
     P.k = k; P.m = m; P.b = b;
@@ -1994,6 +2002,7 @@ BRISK_API int brisk_hip_get_layout(const brisk_hip_index* h, brisk_hip_layout* o
     out->cls_width = P.cls_width;
     out->n_owners = P.n_owners;
     out->owner_rank = P.owner_rank;
+    out->count_mode = h->count_mode;
     return BRISK_HIP_OK;
 }
 
@@ -2469,6 +2478,7 @@ BRISK_API int brisk_hip_reallocate(brisk_hip_index* from, brisk_hip_index* to) {
     if (from->P.k != to->P.k || from->device != to->device) return fail(h, BRISK_HIP_EINVAL, "reallocate: both indexes must have the same k and device");
     if (from->entry_ids || to->entry_ids) return fail(h, BRISK_HIP_EINVAL, "reallocate: entry-id indexes are re-bucketed by the facade (DATA lives on the host)");
     if (to->P.n_owners > 1 || from->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "reallocate on a sharded index");
+    if (from->count_mode != to->count_mode) return fail(h, BRISK_HIP_EINVAL, "reallocate: the two indexes differ in count_mode");
     HIPCHK(h, hipSetDevice(h->device));
     if (int frc = enter(from)) return fail(h, frc, "reallocate: " + from->err);
     if (int frc = enter(to)) return frc;
@@ -2547,6 +2557,7 @@ int setop_compatible(brisk_hip_index* h, const brisk_hip_index* a, const brisk_h
     else if (a->P.cls_width != b->P.cls_width) field = "cls_width";
     else if (a->ix.key_words != b->ix.key_words) field = "key width";
     else if (a->device != b->device) field = "device";
+    else if (a->count_mode != b->count_mode) field = "count_mode";
     if (field) return fail(h, BRISK_HIP_EINVAL, who + "the two indexes differ in " + field);
     return BRISK_HIP_OK;
 }
@@ -2622,7 +2633,9 @@ BRISK_API int brisk_hip_intersect(brisk_hip_index* dst, brisk_hip_index* src, ui
     if (int rc = setop_enter(dst, src, "intersect")) return rc;
     std::lock_guard<std::recursive_mutex> lock_dst(dst->call_mu, std::adopt_lock), lock_src(src->call_mu, std::adopt_lock);
     if (removed) *removed = 0;
-    return join_remove(dst, src, JOIN_INTERSECT, count_rule, removed);
+    // (the kernel's rule 4: the sum clamped to 255, what SUM means between two saturating indexes)
+    const u32 rule = count_rule == BRISK_HIP_COUNT_SUM && dst->count_mode == BRISK_HIP_COUNTS_SATURATE ? JOIN_RULE_SUM_SAT : count_rule;
+    return join_remove(dst, src, JOIN_INTERSECT, rule, removed);
 }
 
 BRISK_API int brisk_hip_subtract(brisk_hip_index* dst, brisk_hip_index* src, uint64_t* removed) {
@@ -2752,9 +2765,12 @@ int snap_parse_header(const unsigned char* hd, u64 file_bytes, brisk_hip_snapsho
     s->n_entries = get64(hd + 56); s->n_partitions = get64(hd + 64); s->nb_skmers = get64(hd + 72);
     for (int i = 0; i < 3; i++) s->checksum[i] = get64(hd + 80 + 8 * i);
     s->n_blocks = get64(hd + 104);
+    s->count_mode = get32(hd + 112);  // (zero in every file written before the field existed: counts wrap)
     s->file_bytes = file_bytes;
     if (s->data_bytes != 1 || (s->key_words != 1 && s->key_words != 2) || s->part_bits > 30 || s->k > 63)
         return *why = "snapshot header: inconsistent layout fields", BRISK_HIP_EFORMAT;
+    if (s->count_mode != BRISK_HIP_COUNTS_WRAP && s->count_mode != BRISK_HIP_COUNTS_SATURATE)
+        return *why = "snapshot header: unknown count_mode " + std::to_string(s->count_mode), BRISK_HIP_EFORMAT;
     // the sizes against the file's length: every block has 16 bytes of its own and at most 7 of padding
     const u64 body = file_bytes - kSnapHeader;
     bool ok = s->n_partitions <= (1ull << s->part_bits) && s->n_partitions <= s->n_entries && s->n_blocks <= s->n_partitions && (s->n_entries == 0) == (s->n_blocks == 0) &&
@@ -2938,6 +2954,7 @@ int save_impl(brisk_hip_index* h, int fd, uint64_t* entries_written) {
     put64(hd + 56, n_entries); put64(hd + 64, n_partitions); put64(hd + 72, h->nb_skmers);
     for (int i = 0; i < 3; i++) put64(hd + 80 + 8 * i, ck[i]);
     put64(hd + 104, blocks.size());
+    put32(hd + 112, h->count_mode);
     if (!write_all(fd, hd, sizeof hd)) return fail(h, BRISK_HIP_EIO, std::string("save: write: ") + strerror(errno));
     if (!blocks.empty()) {
         SnapPin pin(h->stream);
@@ -3140,6 +3157,7 @@ BRISK_API int brisk_hip_load(brisk_hip_index* h, const char* path, uint32_t flag
         else if (s.cls_width != P.cls_width) field = "cls_width";
         else if (s.key_words != h->ix.key_words) field = "key_words";
         else if (s.shift != P.shift) field = "shift";
+        else if (s.count_mode != h->count_mode) field = "count_mode";
         if (field) rc = fail(h, BRISK_HIP_EINVAL, std::string("load: the file and the index differ in ") + field);
     }
     if (!rc) {

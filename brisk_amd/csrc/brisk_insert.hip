@@ -8,7 +8,7 @@
 //   1. the instances are de-duplicated in an LDS table whose slots hold the index
 //      of the first instance and a multiplicity;
 //   2. the partition's existing entries stream through the table: a hit adds the
-//      multiplicity to the entry's count (uint8_t, wraps; counter.cpp:264-268);
+//      multiplicity to the entry's count (uint8_t, wraps; counter.cpp:264-268 -- or, in a saturating index, stops at 255);
 //   3. unmatched table entries are appended as new entries (count = multiplicity).
 // Storage per partition: keys[] (u128) and counts[] (u8) in a bump-allocated arena.
 // A partition that outgrows its slice moves to a fresh one taken from the
@@ -62,6 +62,14 @@ struct IndexDev {
     u32 key_words;               // u64 words per stored key: 1 where [routing id low bits | compacted k-mer | idx'] fits 64 bits
                                  // (shift + 2(k-b) + 6 <= 64: k31 b14, k31 b11, ...: 9 bytes per entry instead of 17), else 2
 };
+// An entry's count byte from an exact sum or multiplicity.  SAT false (the default, as the reference's uint8_t counter): its low 8
+// bits.  SAT true (brisk_hip_options.count_mode == BRISK_HIP_COUNTS_SATURATE): clamped to 255.  Saturating addition of
+// non-negative numbers is associative, so every stage may clamp what it hands on; the wider sums in between are exact.
+// A compile-time parameter of the bodies: the default instantiations are instruction for instruction what they were.
+template <bool SAT>
+__device__ __forceinline__ u32 count8(u32 x) {
+    return SAT ? (x < 255u ? x : 255u) : (x & 0xffu);
+}
 // an entry's key in the arena (KW: the word count where the caller knows it at compile time, 0: from ix)
 template <u32 KW = 0>
 __device__ __forceinline__ u128x load_key(const IndexDev& ix, unsigned long long at) {
@@ -202,7 +210,7 @@ __device__ __forceinline__ u128x record_kmer_lds(const BriskParams& P, const u64
 
 // NI-instances-per-lane body of the expand + de-duplicate phases (NI = 4 when the
 // chunk has <= 256 instances, else 8: all NI instances of a lane are in flight together)
-template <u32 NI, u32 NW>
+template <u32 NI, u32 NW, bool SAT>
 __device__ __forceinline__ void expand_and_dedupe(const BriskParams& P, u32 lane, u32 ninst, u32 tsize, const u64* s_rec, const u32* s_pref,
                                                   const uint8_t* s_irec, const u32* s_rmult, u64* s_key, u32* s_tab) {
     u64 klo[NI], khi[NI];
@@ -224,7 +232,7 @@ __device__ __forceinline__ void expand_and_dedupe(const BriskParams& P, u32 lane
         klo[it] = key.lo;
         khi[it] = key.hi;
         hh[it] = hash_key32(key) & (tsize - 1);
-        mult[it] = (s_rmult[r] & 0xffu) << WI_CNT_SHIFT;  // counts wrap at 256: so may the multiplicities
+        mult[it] = count8<SAT>(s_rmult[r]) << WI_CNT_SHIFT;  // counts wrap at 256 (SAT: stop at 255): so may the multiplicities
         if (i < ninst) {
             s_key[2 * i] = key.lo;
             s_key[2 * i + 1] = key.hi;
@@ -298,9 +306,9 @@ struct LaneInst {
     u32 hh[NIMAX];
     u32 won;
 };
-// s_imult: every instance slot's multiplicity, mod 256 (the chunk's records folded: section 4 finding 15)
+// s_imult: every instance slot's multiplicity, mod 256 (SAT: clamped to 255; the chunk's records folded: section 4 finding 15)
 // (FOLD false: s_rmult, per record)
-template <u32 NI, u32 NW, u32 KB, u32 SHIFT, u32 NIMAX, bool FOLD>
+template <u32 NI, u32 NW, u32 KB, u32 SHIFT, u32 NIMAX, bool FOLD, bool SAT>
 __device__ __forceinline__ void expand_and_dedupe_words(u32 lane, u32 ninst, u32 tsize, const u32* s_rw, const uint8_t* s_irec, const uint8_t* s_imult,
                                                         const u32* s_rmult, u64* s_key, u32* s_tab, u32* dbg_rounds, LaneInst<NIMAX>& li) {
     constexpr u32 RS = RecGeom<NW>::RS, INFO = RecGeom<NW>::INFO, KBITS = 2 * KB + 6;
@@ -347,8 +355,8 @@ __device__ __forceinline__ void expand_and_dedupe_words(u32 lane, u32 ninst, u32
         klo[it] = lo;
         khi[it] = hi;
         hh[it] = hash_key32(mk128(lo, hi)) & (tsize - 1);
-        // counts wrap at 256: so may the multiplicities
-        mult[it] = FOLD ? (u32)s_imult[i < ninst ? i : 0] << WI_CNT_SHIFT : (s_rmult[rix[it]] & 0xffu) << WI_CNT_SHIFT;
+        // counts wrap at 256 (SAT: stop at 255): so may the multiplicities
+        mult[it] = FOLD ? (u32)s_imult[i < ninst ? i : 0] << WI_CNT_SHIFT : count8<SAT>(s_rmult[rix[it]]) << WI_CNT_SHIFT;
         if (i < ninst) {
             s_key[2 * i] = lo;
             s_key[2 * i + 1] = hi;
@@ -396,10 +404,10 @@ __device__ __forceinline__ void expand_and_dedupe_words(u32 lane, u32 ninst, u32
 
 // Record-level de-duplication of the <= 64 records the lanes hold (also in s_rec): the first copy of every distinct record
 // survives, s_rmult[its lane] = the multiplicities of all its copies added up; returns whether this lane's record is a
-// later copy.  Header bits 48..55 carry a record's multiplicity (mod 256: counts wrap there anyway) once a partition's
-// records have been collapsed; they are not part of its identity.
+// later copy.  Header bits 48..55 carry a record's multiplicity (mod 256: counts wrap there anyway; clamped to 255 in a saturating
+// index) once a partition's records have been collapsed; they are not part of its identity.
 #define HDR_ID_MASK 0x0000ffffffffffffull
-#define HDR_HAS_MULT (1ull << 56)   // header bits 48..55 hold the record's multiplicity (mod 256, as the counts are)
+#define HDR_HAS_MULT (1ull << 56)   // header bits 48..55 hold the record's multiplicity (a count byte: mod 256, or clamped to 255, as the index's counts are)
 __device__ __forceinline__ bool dedupe_records(u32 stride, const RecRegs& rr, u32 my_mult, u32 nrec, u32 lane, const u64* s_rec, u32* s_rtab, u32* s_rmult) {
     s_rtab[lane] = EMPTY_SLOT;
     s_rtab[lane + 64] = EMPTY_SLOT;
@@ -514,7 +522,8 @@ __device__ __forceinline__ bool fold_records(const FoldFrame& f, u32 nrec, u32 l
 // strides fold, nothing of BriskParams stays in scalar registers (the generic body spills 48 of them into vector
 // lanes and pays a v_readlane per use), and k-mers are cut out of 32-bit words (expand_and_dedupe_words).  NW == 0:
 // everything from P at run time.
-template <u32 MAXI, u32 NW, u32 KB, u32 SHIFT>
+// SAT: the index's counts stop at 255 instead of wrapping (count8).
+template <u32 MAXI, u32 NW, u32 KB, u32 SHIFT, bool SAT>
 __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc& src, const PartDesc* __restrict__ desc, u32 n_touched, const IndexDev& ix,
                                             u32* __restrict__ work_counter) {
     u64* const rec = src.rec;  // the in-place collapse of the big-partition kernel (classic layout only)
@@ -641,7 +650,7 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                     const unsigned long long bal = __ballot(keep);
                     if (keep) {  // survivors move to the front of the partition's records (never past what is still to be read)
                         u64* dst = rec + (u64)(wr + (u32)__popcll(bal & lanes_below(lane))) * P.stride;
-                        const u64 keep_id = HDR_ID_MASK, mult = ((u64)(s_rmult[lane] & 0xffu) << 48) | HDR_HAS_MULT;
+                        const u64 keep_id = HDR_ID_MASK, mult = ((u64)count8<SAT>(s_rmult[lane]) << 48) | HDR_HAS_MULT;  // (a window's copies add up to 64 x 255 at most)
                         dst[0] = rr.w0;
                         dst[1] = P.stride == 2 ? (rr.w1 & keep_id) | mult : rr.w1;
                         if (P.stride > 2) dst[2] = P.stride == 3 ? (rr.w2 & keep_id) | mult : rr.w2;
@@ -733,7 +742,8 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                     // (records lie in lane order).  Every lane owns MAXI/64 consecutive instances here.
                     // FOLD, in the same rounds: every instance's multiplicity.  Each record adds its own
                     // at the start of its range and takes it off at the end; a prefix sum over the slots (the lane's NI,
-                    // then the wave) adds up the records over every slot.  u32, wrapping: only the low 8 bits count.
+                    // then the wave) adds up the records over every slot.  u32, wrapping: the steps cancel, so every slot's sum is exact
+                    // (64 records x 255 at most) and its count byte is taken from it (count8).
                     u32* irec32 = (u32*)s_irec;
 #pragma unroll
                     for (u32 q = 0; q < MAXI / 256; q++) irec32[q * 64 + lane] = 0;
@@ -765,8 +775,9 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                         u32* mult32 = (u32*)s_imult;
 #pragma unroll
                         for (u32 q = 0; q < NI / 4; q++)
-                            mult32[lane * (NI / 4) + q] = ((mv[4 * q] + before) & 0xff) | (((mv[4 * q + 1] + before) & 0xff) << 8) |
-                                                          (((mv[4 * q + 2] + before) & 0xff) << 16) | ((mv[4 * q + 3] + before) << 24);
+                            mult32[lane * (NI / 4) + q] = count8<SAT>(mv[4 * q] + before) | (count8<SAT>(mv[4 * q + 1] + before) << 8) |
+                                                          (count8<SAT>(mv[4 * q + 2] + before) << 16) |
+                                                          ((SAT ? count8<SAT>(mv[4 * q + 3] + before) : mv[4 * q + 3] + before) << 24);
                     }
                     u32 carry = wave_prev_lane(wave_incl_max_scan(run));  // the last mark before this lane's instances
 #pragma unroll
@@ -792,15 +803,15 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                     if (FOLD && lane < nrec) s_rw[lane * RecGeom<NW ? NW : 1>::RS + RecGeom<NW ? NW : 1>::INFO] = (x - my_n) | info_hi;
                     if (!FOLD && lane < nrec) store_rec_words<NW ? NW : 1>(s_rw + lane * RecGeom<NW ? NW : 1>::RS, rr, (x - my_n) | info_hi);
                     wave_sync();
-                    if (ninst <= 64) expand_and_dedupe_words<1, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
-                    else if (ninst <= 128) expand_and_dedupe_words<2, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
-                    else if (ninst <= 192) expand_and_dedupe_words<3, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
-                    else if (NI <= 4 || ninst <= 256) expand_and_dedupe_words<4, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
-                    else expand_and_dedupe_words<NI, NW ? NW : 1, KB, SHIFT, NI, FOLD>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    if (ninst <= 64) expand_and_dedupe_words<1, NW ? NW : 1, KB, SHIFT, NI, FOLD, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    else if (ninst <= 128) expand_and_dedupe_words<2, NW ? NW : 1, KB, SHIFT, NI, FOLD, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    else if (ninst <= 192) expand_and_dedupe_words<3, NW ? NW : 1, KB, SHIFT, NI, FOLD, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    else if (NI <= 4 || ninst <= 256) expand_and_dedupe_words<4, NW ? NW : 1, KB, SHIFT, NI, FOLD, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
+                    else expand_and_dedupe_words<NI, NW ? NW : 1, KB, SHIFT, NI, FOLD, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, s_rmult, s_key, s_tab, &dbg_r, li);
                 } else {
-                    if (ninst <= 128) expand_and_dedupe<2, 0>(P, lane, ninst, tsize, s_rec, s_pref, s_irec, s_rmult, s_key, s_tab);
-                    else if (NI <= 4 || ninst <= 256) expand_and_dedupe<4, 0>(P, lane, ninst, tsize, s_rec, s_pref, s_irec, s_rmult, s_key, s_tab);
-                    else expand_and_dedupe<NI, 0>(P, lane, ninst, tsize, s_rec, s_pref, s_irec, s_rmult, s_key, s_tab);
+                    if (ninst <= 128) expand_and_dedupe<2, 0, SAT>(P, lane, ninst, tsize, s_rec, s_pref, s_irec, s_rmult, s_key, s_tab);
+                    else if (NI <= 4 || ninst <= 256) expand_and_dedupe<4, 0, SAT>(P, lane, ninst, tsize, s_rec, s_pref, s_irec, s_rmult, s_key, s_tab);
+                    else expand_and_dedupe<NI, 0, SAT>(P, lane, ninst, tsize, s_rec, s_pref, s_irec, s_rmult, s_key, s_tab);
                 }
                 wave_sync();
                 CNT(8, dbg_r)
@@ -836,7 +847,7 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                             if (v == EMPTY_SLOT) break;
                             const u32 i = v & WI_IDX_MASK;
                             if (s_key[2 * i] == klo[q] && s_key[2 * i + 1] == khi[q]) {
-                                ix.counts[off + e] = (uint8_t)(cnt[q] + ((v & ~MATCHED_BIT) >> WI_CNT_SHIFT));
+                                ix.counts[off + e] = (uint8_t)count8<SAT>(cnt[q] + ((v & ~MATCHED_BIT) >> WI_CNT_SHIFT));
                                 s_tab[h] = v | MATCHED_BIT;
                                 break;
                             }
@@ -933,7 +944,7 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                         if ((new_mask >> it) & 1) {
                             const unsigned long long at = off + n_exist + new_rank[it];
                             store_key<KW>(ix, at, li.klo[it], li.khi[it]);
-                            ix.counts[at] = (uint8_t)(new_word[it] >> WI_CNT_SHIFT);
+                            ix.counts[at] = (uint8_t)count8<SAT>(new_word[it] >> WI_CNT_SHIFT);  // (a new entry's word has no MATCHED_BIT)
                             const u32 bl = P.shift ? ((u32)shr128(mk128(li.klo[it], li.khi[it]), kbits).lo & ((1u << P.shift) - 1)) : 0;
                             const u32 bb = P.shift > 6 ? (bl >> (P.shift - 6)) : bl;  // 64 bins at most
                             if (bb < 32) bm0 |= 1u << bb; else bm1 |= 1u << (bb - 32);
@@ -946,7 +957,7 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                         const u64 klo2 = s_key[2 * i], khi2 = s_key[2 * i + 1];
                         const unsigned long long at = off + n_exist + q;
                         store_key<KW>(ix, at, klo2, khi2);
-                        ix.counts[at] = (uint8_t)(v >> WI_CNT_SHIFT);
+                        ix.counts[at] = (uint8_t)count8<SAT>(v >> WI_CNT_SHIFT);
                         // bucket id inside the partition: the key's top `shift` bits (<= 6 of them used here)
                         const u32 bl = P.shift ? ((u32)shr128(mk128(klo2, khi2), kbits).lo & ((1u << P.shift) - 1)) : 0;
                         const u32 bb = P.shift > 6 ? (bl >> (P.shift - 6)) : bl;  // 64 bins at most
@@ -1004,21 +1015,21 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
 // at 96 it spills 10 to scratch and the fifth wave is worth it: 29.8 -> 26.3 ms per 50 M reads (5120 resident waves).
 #define WI_WAVES_PER_EU_FAST 5
 #endif
-template <u32 NW, u32 KB, u32 SHIFT>
+template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVES_PER_EU_FAST, 8))) k_insert_fast(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
                                                                                                         u32 n_touched, IndexDev ix, u32* __restrict__ work_counter) {
     static_assert(NW > 0, "compile-time record geometry");
-    insert_body<WI_MAX_INST, NW, KB, SHIFT>(P, src, desc, n_touched, ix, work_counter);
+    insert_body<WI_MAX_INST, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter);
 }
-template <u32 NW, u32 KB, u32 SHIFT>
+template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVES_PER_EU, 8))) k_insert(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
                                                u32 n_touched, IndexDev ix, u32* __restrict__ work_counter) {
-    insert_body<WI_MAX_INST, NW, KB, SHIFT>(P, src, desc, n_touched, ix, work_counter);
+    insert_body<WI_MAX_INST, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter);
 }
-template <u32 NW, u32 KB, u32 SHIFT>
+template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) k_insert_big(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
                                                                                          u32 n_touched, IndexDev ix, u32* __restrict__ work_counter) {
-    insert_body<2 * WI_MAX_INST, NW, KB, SHIFT>(P, src, desc, n_touched, ix, work_counter);
+    insert_body<2 * WI_MAX_INST, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter);
 }
 
 // bucket occupancy for partitions wider than 64 buckets (small part_bits): one pass over all entries
@@ -1076,7 +1087,7 @@ __global__ void __launch_bounds__(256) k_stats(const DirEnt* __restrict__ dir, u
 // kernels work off in chunks of 256 / 512 instances, every chunk streaming the partition's entries through its table --
 // entries x instances / 256 probes by 64 lanes while the rest of the device idles.  Here a chunk is 2048 instances in a
 // table shared by 1024 lanes: 8 times fewer passes over the entries, each 16 times as wide.  Same semantics as insert_body
-// (find-all then insert-missing, DenseMenuYo.hpp:248-310; counts wrap at 256); run-time geometry; classic and binned record
+// (find-all then insert-missing, DenseMenuYo.hpp:248-310; counts wrap at 256, or with SAT stop at 255); run-time geometry; classic and binned record
 // layouts.  Partitions are chosen by k_need (PartDesc::n_inst > IndexDev::huge_at); the wave kernels skip them.
 #define HG_THREADS 1024u
 #define HG_INST 2048u          // k-mer instances per chunk
@@ -1108,6 +1119,7 @@ __device__ __forceinline__ u32 block_incl_scan(u32 v, u32* s_wsum, u32* total) {
     *total = all;
     return x + before;
 }
+template <bool SAT>
 __global__ void __launch_bounds__(HG_THREADS) k_insert_huge(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc, const u32* __restrict__ huge_list,
                                                             const u32* __restrict__ n_huge, IndexDev ix) {
     __shared__ u64 s_key[2 * HG_INST];
@@ -1184,7 +1196,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_insert_huge(BriskParams P, RecSr
             }
             __syncthreads();
             const u32 nkeys = s_nkeys;
-            // ---- the partition's entries: the ones that are in the chunk take its multiplicity (mod 256)
+            // ---- the partition's entries: the ones that are in the chunk take its multiplicity (mod 256; SAT: up to 255)
             for (u32 e = tid; e < n_exist; e += HG_THREADS) {
                 const u128x ke = load_key(ix, off + e);
                 const u64 klo = ke.lo, khi = ke.hi;
@@ -1194,7 +1206,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_insert_huge(BriskParams P, RecSr
                     if (v == EMPTY_SLOT) break;
                     if (s_key[2 * v] == klo && s_key[2 * v + 1] == khi) {
                         const u32 m = atomicOr(&s_cnt[v], HG_EXIST) & HG_MULT;
-                        ix.counts[off + e] = (uint8_t)(ix.counts[off + e] + m);
+                        ix.counts[off + e] = (uint8_t)count8<SAT>(ix.counts[off + e] + m);
                         break;
                     }
                     h = (h + 1) & (HG_TAB - 1);
@@ -1245,7 +1257,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_insert_huge(BriskParams P, RecSr
                     const unsigned long long at = off + n_exist + done + pos - 1;
                     const u64 klo = s_key[2 * q], khi = s_key[2 * q + 1];
                     store_key(ix, at, klo, khi);
-                    ix.counts[at] = (uint8_t)(cv & HG_MULT);
+                    ix.counts[at] = (uint8_t)count8<SAT>(cv & HG_MULT);
                     // bucket id inside the partition: the key's top `shift` bits (<= 6 of them used here), as insert_body has it
                     const u32 bl = P.shift ? ((u32)shr128(mk128(klo, khi), kbits).lo & ((1u << P.shift) - 1)) : 0;
                     const u32 bb = P.shift > 6 ? (bl >> (P.shift - 6)) : bl;

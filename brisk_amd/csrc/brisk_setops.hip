@@ -31,6 +31,7 @@
 #define JOIN_INTERSECT 0u
 #define JOIN_SUBTRACT 1u
 #define JOIN_COMPARE 2u
+#define JOIN_RULE_SUM_SAT 4u   // k_join's rule beyond BRISK_HIP_COUNT_*: SUM between two saturating indexes, min(255, dst + src)
 #define JN_FOUND 0x100u   // match word: JN_FOUND | the src entry's count; 0: not found (a count of 0 is still found)
 
 // one probe of the table by every lane that has `valid`: returns the match word
@@ -53,7 +54,7 @@ __device__ __forceinline__ u32 join_probe(const u64* s_key, const u32* s_tab, u3
     return found;
 }
 
-// rule: BRISK_HIP_COUNT_LEFT / MIN / MAX / SUM (INTERSECT only).  out: INTERSECT / SUBTRACT out[0] += entries removed;
+// rule: BRISK_HIP_COUNT_LEFT / MIN / MAX / SUM, or JOIN_RULE_SUM_SAT (INTERSECT only).  out: INTERSECT / SUBTRACT out[0] += entries removed;
 // COMPARE out[0..5] as brisk_hip_compare documents them (dst is a, src is b).
 template <u32 OP, u32 KW>
 __global__ void __launch_bounds__(64) k_join(IndexDev dst, IndexDev src, u32 n_parts, u32 rule, unsigned long long* __restrict__ out) {
@@ -140,7 +141,7 @@ __global__ void __launch_bounds__(64) k_join(IndexDev dst, IndexDev src, u32 n_p
                 } else {
                     const bool keep = valid && (OP == JOIN_INTERSECT ? hit : !hit);
                     u32 nc = cnt[q];
-                    if (OP == JOIN_INTERSECT) nc = rule == 1 ? min(nc, cs) : rule == 2 ? max(nc, cs) : rule == 3 ? (nc + cs) & 0xffu : nc;
+                    if (OP == JOIN_INTERSECT) nc = rule == 1 ? min(nc, cs) : rule == 2 ? max(nc, cs) : rule == 3 ? (nc + cs) & 0xffu : rule == JOIN_RULE_SUM_SAT ? min(nc + cs, 255u) : nc;
                     const unsigned long long bal = __ballot(keep);
                     const u32 slot = written + (u32)__popcll(bal & lanes_below(lane));  // <= e
                     if (keep && slot != e) store_key<KW>(dst, dd.off + slot, key[q].lo, key[q].hi);

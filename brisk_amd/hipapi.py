@@ -85,18 +85,23 @@ def coef_table(m: int) -> np.ndarray:
 class _Options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("stream", C.c_void_p), ("part_bits", C.c_uint32),
                 ("owner_rank", C.c_uint32), ("n_owners", C.c_uint32), ("arena_entries", C.c_uint64),
-                ("max_batch_reads", C.c_uint64), ("entry_ids", C.c_uint32), ("immediate_inserts", C.c_uint32)]
+                ("max_batch_reads", C.c_uint64), ("entry_ids", C.c_uint32), ("immediate_inserts", C.c_uint32),
+                ("count_mode", C.c_uint32)]
+
+
+# brisk_hip_options.count_mode: BRISK_HIP_COUNTS_WRAP / BRISK_HIP_COUNTS_SATURATE
+COUNT_MODES = {"wrap": 0, "saturate": 1}
 
 
 class _Layout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("k", "m", "b", "m_reduc", "compacted_size", "allocated_bytes", "record_words",
-                                          "part_bits", "n_owners", "owner_rank", "ext_bits", "cls_bits", "cls_width")]
+                                          "part_bits", "n_owners", "owner_rank", "ext_bits", "cls_bits", "cls_width", "count_mode")]
 
 
 class _SnapshotInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "version", "header_bytes", "k", "m", "b", "data_bytes", "part_bits", "ext_bits", "cls_bits",
                                           "cls_width", "key_words", "shift")] + \
-               [(n, C.c_uint64) for n in ("n_entries", "n_partitions", "nb_skmers")] + [("checksum", C.c_uint64 * 3), ("n_blocks", C.c_uint64), ("file_bytes", C.c_uint64)]
+               [(n, C.c_uint64) for n in ("n_entries", "n_partitions", "nb_skmers")] + [("checksum", C.c_uint64 * 3), ("n_blocks", C.c_uint64), ("file_bytes", C.c_uint64), ("count_mode", C.c_uint32)]
 
 
 _u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
@@ -255,7 +260,7 @@ def profile_from_slots(counts, found, base, solid_min: int) -> np.ndarray:
 def snapshot_info(path) -> dict:
     """The header of a snapshot file (brisk_hip_snapshot_info_read; host only: no device, no handle): k, m, b, data_bytes, part_bits,
     ext_bits, cls_bits, cls_width, key_words, shift, n_entries, n_partitions (the non-empty ones), nb_skmers, checksum (the three
-    words of BriskHip.checksum at save time), n_blocks, version, header_bytes and file_bytes."""
+    words of BriskHip.checksum at save time), n_blocks, version, header_bytes, file_bytes and count_mode (0 wrap, 1 saturate: COUNT_MODES)."""
     info = _SnapshotInfo(C.sizeof(_SnapshotInfo))
     rc = load().brisk_hip_snapshot_info_read(os.fsencode(path), C.byref(info))
     if rc:
@@ -280,16 +285,22 @@ def _close_all_handles():
 
 
 class BriskHip:
-    """One index handle.  Methods map one-to-one onto the C-ABI."""
+    """One index handle.  Methods map one-to-one onto the C-ABI.
+
+    count_mode: "wrap" (the default: the count byte wraps at 256, as the reference's) or "saturate": an entry's count is
+    min(255, the times its identity was inserted) -- 255 means "255 or more" and no present entry has count 0.  The mode is fixed
+    at create time (the attribute `count_mode`), travels with snapshots, and two indexes of a set operation must agree in it."""
 
     def __init__(self, k: int, m: int, b: int, device: int = 0, stream: Optional[int] = None, part_bits: int = 0,
                  owner_rank: int = 0, n_owners: int = 1, arena_entries: int = 0, max_batch_reads: int = 0,
-                 entry_ids: bool = False, immediate_inserts: bool = False):
+                 entry_ids: bool = False, immediate_inserts: bool = False, count_mode: str = "wrap"):
+        if count_mode not in COUNT_MODES:
+            raise ValueError(f"count_mode must be one of {sorted(COUNT_MODES)}, not {count_mode!r}")
         self.L = load()
         self.h = C.c_void_p()
         self.k, self.m, self.b = k, m, b
         opt = _Options(C.sizeof(_Options), device, stream, part_bits, owner_rank, n_owners, arena_entries, max_batch_reads,
-                       1 if entry_ids else 0, 1 if immediate_inserts else 0)
+                       1 if entry_ids else 0, 1 if immediate_inserts else 0, COUNT_MODES[count_mode])
         coef = coef_table(m) if 1 <= m <= 31 else np.zeros(4, np.float64)
         rc = self.L.brisk_hip_create(C.byref(self.h), k, m, b, 1, coef.ctypes.data_as(C.POINTER(C.c_double)), C.byref(opt))
         if rc:
@@ -300,6 +311,7 @@ class BriskHip:
         self._chk(self.L.brisk_hip_get_layout(self.h, C.byref(lay)))
         self.layout = {n: getattr(lay, n) for n, _ in _Layout._fields_}
         self.record_words = lay.record_words
+        self.count_mode = {v: n for n, v in COUNT_MODES.items()}[lay.count_mode]
 
     def _chk(self, rc: int):
         if rc:
@@ -343,8 +355,9 @@ class BriskHip:
         return out
 
     def get_kmers(self, seqs: Sequence) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """The count at every k-mer position (brisk_hip_get_kmers): counts uint8[n_slots] (mod 256), found bool[n_slots],
-        base uint64[n_reads + 1] -- the k-mer at nucleotide i of read r is slot base[r] + i."""
+        """The count at every k-mer position (brisk_hip_get_kmers): counts uint8[n_slots] (mod 256; in a saturating index 1..255 where
+        found, 255 meaning "255 or more"), found bool[n_slots], base uint64[n_reads + 1] -- the k-mer at nucleotide i of read r is
+        slot base[r] + i."""
         flat, offs = _pack_reads(seqs)
         base = kmer_slots(offs, self.k)
         total = int(base[-1])
@@ -359,7 +372,9 @@ class BriskHip:
         """One abundance record per read (brisk_hip_read_profile_reads): READ_PROFILE_DTYPE[n_reads] -- n_kmers, n_present, n_solid
         (present and count >= solid_min), the first longest run of solid slots (run_start, run_len), min / max / lower median of
         the present counts, the lower median over all slots (absent = 0) and the sum.  What profile_from_slots(*get_kmers(seqs),
-        solid_min) gives, reduced on the device: the slots never reach the host."""
+        solid_min) gives, reduced on the device: the slots never reach the host.  Counts are the stored bytes: in a wrapping index an
+        entry seen 256 times is present with count 0 and pulls a median down; in a saturating index (count_mode="saturate") counts stop
+        at 255, which stands for "255 or more" in min / max / medians and the sum."""
         flat, offs = _pack_reads(seqs)
         out = np.zeros(len(offs) - 1, READ_PROFILE_DTYPE)
         if len(flat) == 0:
@@ -405,13 +420,16 @@ class BriskHip:
         return cat(los, np.uint64), cat(his, np.uint64), cat(idxs, np.uint8), cat(cnts, np.uint8)
 
     def count_spectrum(self) -> np.ndarray:
-        """uint64[256]: out[c] = entries whose stored count (mod 256) is c"""
+        """uint64[256]: out[c] = entries whose stored count (mod 256) is c.  In a saturating index (count_mode="saturate") bin 0 is
+        empty and bin 255 holds the entries seen 255 times or more."""
         out = np.zeros(256, np.uint64)
         self._chk(self.L.brisk_hip_count_spectrum(self.h, out))
         return out
 
     def prune(self, min_count: int, max_count: int = 255) -> int:
-        """remove, in place, every entry whose count is outside [min_count, max_count]; returns how many were removed"""
+        """remove, in place, every entry whose count is outside [min_count, max_count]; returns how many were removed.  The stored
+        byte is compared: a wrapping index loses an entry seen 256 or 257 times to prune(2, 255); a saturating one
+        (count_mode="saturate") holds it at 255 = "255 or more" and keeps it."""
         v = C.c_uint64()
         self._chk(self.L.brisk_hip_prune(self.h, min_count, max_count, C.byref(v)))
         return v.value
@@ -420,14 +438,16 @@ class BriskHip:
     COUNT_RULES = {"left": 0, "min": 1, "max": 2, "sum": 3}
 
     def merge(self, other: "BriskHip") -> int:
-        """self := self UNION other, counts of shared entries added mod 256; returns the entries new to self"""
+        """self := self UNION other, counts of shared entries added mod 256 -- between saturating indexes min(255, sum), 255 meaning
+        "255 or more"; returns the entries new to self.  Both indexes have the same count_mode (EINVAL otherwise)."""
         v = C.c_uint64()
         self._chk(self.L.brisk_hip_merge(self.h, other.h, C.byref(v)))
         return v.value
 
     def intersect(self, other: "BriskHip", count: str = "left") -> int:
         """keep the entries that are also in `other`; their count is self's ("left"), the "min", the "max" or the "sum"
-        (mod 256) of the two; returns how many entries were removed"""
+        (mod 256; between saturating indexes min(255, sum), 255 meaning "255 or more") of the two; returns how many entries were
+        removed.  Both indexes have the same count_mode (EINVAL otherwise)."""
         if count not in self.COUNT_RULES:
             raise ValueError(f"count must be one of {sorted(self.COUNT_RULES)}, not {count!r}")
         v = C.c_uint64()
@@ -465,12 +485,13 @@ class BriskHip:
     @classmethod
     def open(cls, path, device: int = 0, room: bool = False, **kw) -> "BriskHip":
         """A new handle with the layout of the snapshot at `path`, and the snapshot loaded into it.  The create options come from
-        the header: k, m, b as stored and part_bits = 0 if ext_bits > 0 else part_bits -- brisk_hip_create extends the routing id
+        the header: k, m, b and count_mode as stored and part_bits = 0 if ext_bits > 0 else part_bits -- brisk_hip_create extends the routing id
         (ext_bits > 0) only when part_bits was left at its default of 0, and without an extension the stored part_bits is what an
         explicit part_bits gives (min(part_bits, 2b), 2^24 partitions at most by default).  cls_bits also depends on the environment
         (BRISK_CLS_BITS): a file saved under another setting is refused by load (EINVAL, the field named).  **kw: further
         constructor options (max_batch_reads, immediate_inserts, ...)."""
         info = snapshot_info(path)
+        kw.setdefault("count_mode", {v: n for n, v in COUNT_MODES.items()}[info["count_mode"]])
         ix = cls(info["k"], info["m"], info["b"], device=device, part_bits=0 if info["ext_bits"] > 0 else info["part_bits"], **kw)
         try:
             ix.load(path, room=room)

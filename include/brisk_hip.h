@@ -144,7 +144,16 @@ typedef struct brisk_hip_options {
                                  * the deferred part (BRISK_HIP_ENOMEM) is returned by the call that completes it.  Streams
                                  * of 2 M-read batches go in 3x faster that way.  1: every insert call completes before it
                                  * returns. */
+    uint32_t count_mode;        /* BRISK_HIP_COUNTS_WRAP (0, also what a caller passing the struct without this field gets): the
+                                 * count byte wraps, first touch = 1, then ++ mod 256, as the reference's uint8_t counter.
+                                 * BRISK_HIP_COUNTS_SATURATE: an entry's stored count is min(255, the number of times its identity
+                                 * was inserted), whatever the batching, the deferral, the kernels that ran or the record layout:
+                                 * 255 means "255 or more", and a present entry never has count 0.  Any other value: EINVAL, as is
+                                 * SATURATE together with entry_ids (that DATA lives with the caller).  The mode is the index's
+                                 * for life: brisk_hip_layout.count_mode reports it, snapshots carry it, and two handles of a set
+                                 * operation or of brisk_hip_reallocate must agree in it. */
 } brisk_hip_options;
+enum { BRISK_HIP_COUNTS_WRAP = 0, BRISK_HIP_COUNTS_SATURATE = 1 };
 
 /* ---- lifetime ----------------------------------------------------------- */
 /* coef_table: the 4*m doubles of DecyclingSet(m) computed on the HOST with libm
@@ -172,10 +181,11 @@ typedef struct brisk_hip_layout {
                                  * 2^cls_bits - 1) of the record's k-mers, and a super-k-mer spanning several classes is
                                  * scanned into one record per class (each a valid super-k-mer of the same bucket) */
     uint32_t cls_width;
+    uint32_t count_mode;        /* brisk_hip_options.count_mode of the handle: BRISK_HIP_COUNTS_WRAP or BRISK_HIP_COUNTS_SATURATE */
 } brisk_hip_layout;
 int brisk_hip_get_layout(const brisk_hip_index *h, brisk_hip_layout *out);
 
-/* ---- bulk count (DATA = uint8_t counter: first touch = 1, then ++ mod 256) -- */
+/* ---- bulk count (DATA = uint8_t counter: first touch = 1, then ++ mod 256; with BRISK_HIP_COUNTS_SATURATE: ++ up to 255) -- */
 /* HOST buffers: `bases` = concatenated sequences, `offsets[n_reads+1]`.  Sequences
  * must be clean ([ACGTacgt]; the N-splitting of counter.cpp:130-169 is the caller's);
  * sequences shorter than k are skipped (counter.cpp:233-235).  A large batch is taken in
@@ -204,7 +214,8 @@ int brisk_hip_get_packed(brisk_hip_index *h, const uint32_t *d_packed, const uin
  * shorter than k contributes nothing).  Read r owns max(0, len_r - k + 1) slots, starting at base_r = the sum of the earlier
  * reads' slots (64-bit: 50 M reads at k = 63 are 4.4 G slots); slot base_r + i is the k-mer that starts at nucleotide i of read
  * r.  A slot holds 0 when the k-mer is absent and 0x100 | count when it is present (the count is kept mod 256, so a present
- * k-mer can have count 0: the 0x100 bit says it is there).  A k-mer is looked up under the (kmer_s, minimizer_idx) that
+ * k-mer can have count 0: the 0x100 bit says it is there; in a saturating index, brisk_hip_options.count_mode, a present k-mer's
+ * count is 1..255 and 255 means "255 or more").  A k-mer is looked up under the (kmer_s, minimizer_idx) that
  * SuperKmerEnumerator gives it while scanning the WHOLE read -- the identity brisk_hip_insert_reads stored; minimizer ties make
  * it depend on the context, so it is not always the identity of the k-mer enumerated on its own.  Every slot of every read is
  * answered: the stop of brisk_hip_get_reads at a returned minimizer of 0 (counter.cpp:304-306) belongs to that per-read sum,
@@ -220,7 +231,8 @@ int brisk_hip_get_kmers_packed(brisk_hip_index *h, const uint32_t *d_packed, con
 /* Per-read abundance profile: the answers of brisk_hip_get_kmers reduced, on the device, to one record per read (no reference
  * counterpart).  A slot is PRESENT when its k-mer is in the index (the 0x100 bit of get_kmers) and SOLID when it is present and its
  * stored count is >= solid_min.  Stored counts are mod 256: an entry whose count wrapped to 0 is present with count 0, and solid only
- * when solid_min == 0; solid_min > 255 means that no slot is solid.  `median` is the lower median over ALL slots of the read, an
+ * when solid_min == 0 (a saturating index, brisk_hip_options.count_mode, has no such entry: its counts stop at 255, which then
+ * stands for "255 or more" in min_present, max_present, the medians and the sum); solid_min > 255 means that no slot is solid.  `median` is the lower median over ALL slots of the read, an
  * absent slot counting 0 (what digital normalisation compares with its cutoff); `median_present` leaves the absent slots out.  The
  * run is the longest stretch of consecutive solid slots, the FIRST one when several are equally long: nucleotides
  * [run_start, run_start + run_len + k - 1) of the read are covered by solid k-mers only (abundance trimming keeps them).
@@ -273,8 +285,9 @@ int brisk_hip_stats(brisk_hip_index *h, uint64_t *nb_buckets, uint64_t *nb_skmer
 
 /* Brisk::reallocate (brisk/Brisk.hpp:202-224: the index re-bucketed to (m + 2, b + 2); dormant in the reference): every
  * entry of `from` goes into `to` -- an EMPTY bulk-count index over the same k and device, created by the caller with the
- * new (m, b) -- under the identity (kmer_s, minimizer_idx) that SuperKmerEnumerator gives the k-mer at the new m, with
- * its count; entries that the new minimizer maps to one identity merge, counts added mod 256.  `from` stays as it is. */
+ * new (m, b) and the same count_mode (EINVAL otherwise, the message names count_mode) -- under the identity (kmer_s,
+ * minimizer_idx) that SuperKmerEnumerator gives the k-mer at the new m, with its count; entries that the new minimizer maps to
+ * one identity merge, counts added mod 256 (saturating indexes: added and clamped to 255).  `from` stays as it is. */
 int brisk_hip_reallocate(brisk_hip_index *from, brisk_hip_index *to);
 
 /* Where the arena's memory is (no reference counterpart; Brisk::stats reports the process' peak RSS, brisk/Brisk.hpp:184-189):
@@ -299,7 +312,9 @@ int brisk_hip_checksum(brisk_hip_index *h, uint64_t out[3]);
 /* All three compare the STORED count byte: counts are kept mod 256, so an entry whose count wrapped to 0 is an entry with
  * count 0 (it is in bin 0, a range must include 0 to hold it, prune(1, 255) removes it).  All three complete pending
  * deferred inserts first, return EINVAL on an entry-id index (its DATA lives with the caller), and on a sharded handle
- * (n_owners > 1) speak about this owner's partitions only, as brisk_hip_checksum does.  A bound above 255 means 255. */
+ * (n_owners > 1) speak about this owner's partitions only, as brisk_hip_checksum does.  A bound above 255 means 255.
+ * In a saturating index (brisk_hip_options.count_mode) no count wraps: bin 0 is empty, bin 255 holds the entries seen 255 times
+ * OR MORE, and prune(2, 255) keeps every entry seen at least twice. */
 /* out[c] = number of entries whose count is c (HOST array).  Sum over c == nb_kmers of brisk_hip_stats; sum of c * out[c] ==
  * out[1] of brisk_hip_checksum.  Spectra of bucket-range shards add up. */
 int brisk_hip_count_spectrum(brisk_hip_index *h, uint64_t out[256]);
@@ -323,21 +338,21 @@ int brisk_hip_prune(brisk_hip_index *h, uint32_t min_count, uint32_t max_count, 
  * as the same key bits, so they are combined on the device partition by partition, keys compared as stored.
  * Identity is (kmer_s, minimizer_idx), as everywhere else.  Presence is what counts: an entry whose stored count wrapped to 0 is
  * present with count 0.  `src` (and both sides of compare) is left bit for bit as it was: same checksum, same enumeration order.
- * Both handles must agree in k, m, b, part_bits, ext_bits, cls_bits, cls_width (brisk_hip_layout) and key width, and live on the
- * same device: otherwise BRISK_HIP_EINVAL, with a message (brisk_hip_last_error of the first handle) that names the field that
+ * Both handles must agree in k, m, b, part_bits, ext_bits, cls_bits, cls_width, count_mode (brisk_hip_layout) and key width, and
+ * live on the same device: otherwise BRISK_HIP_EINVAL, with a message (brisk_hip_last_error of the first handle) that names the field that
  * differs.  EINVAL also for a null handle, dst == src, an entry-id index or a sharded handle (n_owners > 1) on either side, and
  * an unknown count_rule; nothing is changed then.  The counter pointers may be NULL.  Pending deferred inserts of BOTH handles
  * are completed first; both per-handle locks are held for the call (taken together, as brisk_hip_reallocate takes them), and
  * src's stream is synchronised before dst's stream reads src's arena. */
 enum { BRISK_HIP_COUNT_LEFT = 0, BRISK_HIP_COUNT_MIN = 1, BRISK_HIP_COUNT_MAX = 2, BRISK_HIP_COUNT_SUM = 3 };
-/* dst := dst UNION src; the count of a shared entry is dst + src mod 256; *added = entries new to dst.  Afterwards dst is exactly
+/* dst := dst UNION src; the count of a shared entry is dst + src mod 256 (saturating indexes: min(255, dst + src)); *added = entries new to dst.  Afterwards dst is exactly
  * the index that inserting src's reads after dst's reads would have given: the same multiset of (kmer, minimizer_idx, count), so
  * the same checksum, nb_kmers and nb_buckets; nb_skmers becomes dst's plus src's.  Entries already in dst keep their storage
  * order; where new ones land is not specified.  BRISK_HIP_ENOMEM as for an insert (src's entries go through dst's insert as
  * one-k-mer records that carry their counts). */
 int brisk_hip_merge(brisk_hip_index *dst, brisk_hip_index *src, uint64_t *added);
 /* dst keeps the entries whose identity is also in src; their count follows count_rule: LEFT dst's, MIN / MAX of the two,
- * SUM dst + src mod 256.  *removed = entries dst lost.
+ * SUM dst + src mod 256 (saturating indexes: min(255, dst + src)).  *removed = entries dst lost.
  * After intersect and subtract dst is exactly the index that holds the remaining entries, as after brisk_hip_prune: stats
  * (nb_kmers, nb_buckets, largest_bucket), checksum, enumerate, lookup, every get and every later insert behave so.  Survivors
  * keep their storage order.  A partition's slice keeps its offset and capacity and no device memory is returned; nb_skmers is
@@ -369,9 +384,11 @@ typedef struct brisk_hip_snapshot_info {
     uint64_t checksum[3];       /* brisk_hip_checksum at save time */
     uint64_t n_blocks;
     uint64_t file_bytes;        /* length of the file (not stored in it) */
+    uint32_t count_mode;        /* brisk_hip_options.count_mode of the saved index (header offset 112; 0 in files written before
+                                 * the field existed: counts wrap).  A caller whose struct_size ends before it sees no change */
 } brisk_hip_snapshot_info;
 /* The header of a snapshot file.  Host only: no device and no handle are needed.  EIO: the file cannot be opened or is shorter than
- * a header; EFORMAT: wrong magic, a version other than 1, or sizes that disagree with the file's length (brisk_hip_load
+ * a header; EFORMAT: wrong magic, a version other than 1, an unknown count_mode, or sizes that disagree with the file's length (brisk_hip_load
  * answers EIO for a file that is shorter than its header says: it ends early). */
 int brisk_hip_snapshot_info_read(const char *path, brisk_hip_snapshot_info *out);
 /* Writes the index to `path`; *entries_written (may be NULL) receives the entries.  The bytes go to `path` plus a temporary suffix
@@ -381,7 +398,7 @@ int brisk_hip_snapshot_info_read(const char *path, brisk_hip_snapshot_info *out)
  * 2^24 entries; the environment variable BRISK_SNAPSHOT_BLOCK=<entries>, read at each call, sets another limit (a test hook). */
 int brisk_hip_save(brisk_hip_index *h, const char *path, uint64_t *entries_written);
 /* Reads a snapshot into an EMPTY bulk-count index (EINVAL otherwise: "load into an empty index, or load into a second handle and
- * merge") whose k, m, b, data_bytes, part_bits, ext_bits, cls_bits, cls_width, key_words and shift are the file's (EINVAL otherwise;
+ * merge") whose k, m, b, data_bytes, part_bits, ext_bits, cls_bits, cls_width, key_words, shift and count_mode are the file's (EINVAL otherwise;
  * the message names the first field that differs).  Afterwards the handle is what it would be had it inserted the entries: every
  * call behaves so, enumeration order is the saved index's, nb_skmers is the saved one.  flags: BRISK_HIP_LOAD_COMPACT -- every slice
  * exactly as large as its entries, slices back to back: the file's bytes go straight into the arena, and this is the compaction
