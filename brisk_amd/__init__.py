@@ -7,3 +7,4 @@ and ``__graft_entry__``; it never computes anything itself and raises if the
 library is missing (there is no CPU fallback).
 """
 from .hipapi import BriskHip, BriskHipError, build_apps, build_library, library_path, coef_table, kmer_slots, snapshot_info, READ_PROFILE_DTYPE, profile_from_slots, COUNT_MODES  # noqa: F401
+from .hipapi import READ_INTERVAL_DTYPE, SELECT_KINDS, intervals_from_profile, select_rule  # noqa: F401

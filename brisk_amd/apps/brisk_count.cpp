@@ -21,6 +21,12 @@
 //                    top; a FASTA of "-" means no reads.  k m b must be the file's (exit status 2 otherwise)
 //   --save FILE      write the final index -- after counting, the set operations and, if given, --min-count / --max-count applied as
 //                    brisk_hip_prune -- as a snapshot (brisk_hip_save)
+//   --extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]
+//                    after load, set operations and prune (where --profile runs): the reads of the input again, against the final index,
+//                    through brisk_hip_trim_reads; FILE receives what the rule keeps of every kept read as FASTA, the header
+//                    ">read_index start len".  trim (the default): the stretch covered by the first longest run of k-mers with count
+//                    >= N (--solid, default 2); median:LO:HI: the whole read when LO <= its median count <= HI; present:LO:HI: when
+//                    LO <= the permille of its k-mers that are in the index <= HI.  --min-len L: at least L nucleotides (default k)
 // Prints nb_kmers / nb_buckets / sum of counts (of the entries dumped); optionally dumps "KMER idx count" lines (dump.txt, "-" for none) and
 // writes the index as a KFF file (a 7th argument: BriskWriter in --facade mode, brisk_write_kff in --bulk mode).
 #include <algorithm>
@@ -168,6 +174,9 @@ int main(int argc_in, char** argv_in) {
     const char* save_file = nullptr;
     const char* load_file = nullptr;
     const char* profile_file = nullptr;
+    const char* extract_file = nullptr;
+    const char* rule_text = nullptr;
+    long min_len = 0;
     long min_count = 0, max_count = 255, solid = 2;
     bool have_solid = false;
     bool have_range = false;
@@ -176,7 +185,8 @@ int main(int argc_in, char** argv_in) {
     const char* setop_file[3] = {nullptr, nullptr, nullptr};
     static const char* const usage =
         "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] "
-        "[--subtract FILE] [--intersect FILE] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]]; FASTA \"-\": no reads; a FILE may be a snapshot)\n"
+        "[--subtract FILE] [--intersect FILE] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]] "
+        "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]]; FASTA \"-\": no reads; a FILE may be a snapshot)\n"
         "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+";
     for (int i = 0; i < argc_in; i++) {
         if (i > 0 && (!strcmp(argv_in[i], "--help") || !strcmp(argv_in[i], "-h"))) {
@@ -191,7 +201,8 @@ int main(int argc_in, char** argv_in) {
         for (int q = 0; q < 3; q++)
             if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
         const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count") ||
-                                    !strcmp(argv_in[i], "--profile") || !strcmp(argv_in[i], "--solid"));
+                                    !strcmp(argv_in[i], "--profile") || !strcmp(argv_in[i], "--solid") || !strcmp(argv_in[i], "--extract") || !strcmp(argv_in[i], "--rule") ||
+                                    !strcmp(argv_in[i], "--min-len"));
         if (!named) {
             args.push_back(argv_in[i]);
             continue;
@@ -205,6 +216,16 @@ int main(int argc_in, char** argv_in) {
         else if (!strcmp(opt, "--save")) save_file = argv_in[i];
         else if (!strcmp(opt, "--load")) load_file = argv_in[i];
         else if (!strcmp(opt, "--profile")) profile_file = argv_in[i];
+        else if (!strcmp(opt, "--extract")) extract_file = argv_in[i];
+        else if (!strcmp(opt, "--rule")) rule_text = argv_in[i];
+        else if (!strcmp(opt, "--min-len")) {
+            char* end = nullptr;
+            min_len = strtol(argv_in[i], &end, 10);
+            if (end == argv_in[i] || *end || min_len < 0 || min_len > 0xffffffffl) {
+                std::cerr << "--min-len: a number of nucleotides, got " << argv_in[i] << std::endl;
+                return 2;
+            }
+        }
         else if (!strcmp(opt, "--solid")) {  // (above 255: no k-mer is solid)
             char* end = nullptr;
             solid = strtol(argv_in[i], &end, 10);
@@ -234,13 +255,39 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop || save_file || load_file || profile_file || have_solid || saturate) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --save, --load, --profile and --solid work on the device index: --bulk only" << std::endl;
+    if ((histo || have_range || have_setop || save_file || load_file || profile_file || have_solid || saturate || extract_file || rule_text || min_len) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --save, --load, --profile, --solid, --extract, --rule and --min-len work on the device "
+                     "index: --bulk only" << std::endl;
         return 2;
     }
-    if (have_solid && !profile_file) {
-        std::cerr << "--solid is the threshold of --profile FILE" << std::endl;
+    if (have_solid && !profile_file && !extract_file) {
+        std::cerr << "--solid is the threshold of --profile FILE and of --extract FILE" << std::endl;
         return 2;
+    }
+    if ((rule_text || min_len) && !extract_file) {
+        std::cerr << "--rule and --min-len belong to --extract FILE" << std::endl;
+        return 2;
+    }
+    brisk_hip_select_rule rule{};
+    rule.struct_size = sizeof rule;
+    rule.kind = BRISK_HIP_SELECT_SOLID_RUN;
+    rule.min_len = (uint32_t)min_len;
+    rule.hi = 0xffffffffu;
+    if (rule_text && strcmp(rule_text, "trim")) {  // median:LO:HI or present:LO:HI
+        unsigned long lo = 0, hi = 0;
+        char tail = 0;
+        if (sscanf(rule_text, "median:%lu:%lu%c", &lo, &hi, &tail) == 2) rule.kind = BRISK_HIP_SELECT_MEDIAN;
+        else if (sscanf(rule_text, "present:%lu:%lu%c", &lo, &hi, &tail) == 2) rule.kind = BRISK_HIP_SELECT_PRESENT;
+        else {
+            std::cerr << "--rule: trim, median:LO:HI or present:LO:HI, got " << rule_text << std::endl;
+            return 2;
+        }
+        if (lo > hi || hi > 0xfffffffful) {
+            std::cerr << "--rule " << rule_text << ": LO <= HI < 2^32" << std::endl;
+            return 2;
+        }
+        rule.lo = (uint32_t)lo;
+        rule.hi = (uint32_t)hi;
     }
     if (min_count > max_count) {
         std::cerr << "--min-count " << min_count << " is above --max-count " << max_count << std::endl;
@@ -400,10 +447,10 @@ int main(int argc_in, char** argv_in) {
                 brisk_hip_destroy(other);
                 brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
             }
-            if ((save_file || profile_file) && have_range) {  // the final index: what the dump below shows is what the file holds and what the reads are profiled against
+            if ((save_file || profile_file || extract_file) && have_range) {  // the final index: what the dump below shows is what the file holds and what the reads are profiled against
                 uint64_t gone = 0;
                 if (brisk_hip_prune(h, (uint32_t)min_count, (uint32_t)max_count, &gone) != BRISK_HIP_OK) {
-                    std::cerr << (save_file ? "--save" : "--profile") << ": prune: " << brisk_hip_last_error(h) << std::endl;
+                    std::cerr << (save_file ? "--save" : profile_file ? "--profile" : "--extract") << ": prune: " << brisk_hip_last_error(h) << std::endl;
                     return 1;
                 }
                 brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
@@ -441,6 +488,37 @@ int main(int argc_in, char** argv_in) {
                     return 1;
                 }
                 std::cerr << "profile " << profile_file << ": " << read_index << " reads, solid >= " << solid << std::endl;
+            }
+            if (extract_file) {  // the reads of the input again, against the final index: what the rule keeps of them, as FASTA
+                std::ofstream out(extract_file);
+                uint64_t read_index = 0, kept = 0, kept_nts = 0;
+                if (!no_reads) {
+                    FastaBatcher batches(argv[2], batch_bases);
+                    FastaBatch bt;
+                    std::vector<brisk_hip_read_interval> ivs;
+                    while (batches.next(bt)) {
+                        ivs.resize(bt.size());
+                        if (brisk_hip_trim_reads(h, bt.flat.data(), bt.offs.data(), bt.size(), (uint32_t)solid, &rule, ivs.data()) != BRISK_HIP_OK) {
+                            std::cerr << "--extract: " << brisk_hip_last_error(h) << std::endl;
+                            return 1;
+                        }
+                        for (size_t i = 0; i < bt.size(); i++, read_index++) {
+                            if (!ivs[i].len) continue;
+                            out << ">" << read_index << " " << ivs[i].start << " " << ivs[i].len << "\n";
+                            out.write(bt.flat.data() + bt.offs[i] + ivs[i].start, ivs[i].len);
+                            out << "\n";
+                            kept++;
+                            kept_nts += ivs[i].len;
+                        }
+                    }
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "--extract " << extract_file << ": write failed" << std::endl;
+                    return 1;
+                }
+                std::cerr << "extract " << extract_file << ": " << kept << " of " << read_index << " reads, " << kept_nts << " nucleotides (--rule " << (rule_text ? rule_text : "trim")
+                          << ")" << std::endl;
             }
             if (histo) {
                 uint64_t spectrum[256];

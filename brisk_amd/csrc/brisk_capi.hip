@@ -106,6 +106,7 @@ struct brisk_hip_index {
     DevBuf packed_tmp2, starts_tmp2;  // the second set of insert_reads_pipelined: one sub-batch is scanned while the next one arrives
     DevBuf anchors, slot_buf, kout_tmp;  // per-position mode (brisk_hip_get_kmers): records' slot anchors, the batch's slot bases, host-call output
     DevBuf prof_out, prof_plan;          // brisk_hip_read_profile_*: a host call's records; counters, long-read and segment lists, partials
+    DevBuf ext_iv, ext_tmp, ext_src;     // brisk_hip_extract_packed / _trim_*: a call's intervals; flags and block sums; the kept reads' source positions
     u32* d_ovf_cnt = nullptr;              // OVF_REGIONS counters of the binned scan's overflow area
     std::vector<u64> owner_cut;            // sharded index: owner o holds partitions [owner_cut[o], owner_cut[o + 1]) (n_owners + 1 entries)
     u32* d_owner_cut = nullptr;            // the same on the device once brisk_hip_set_owner_cuts has replaced the equal ranges (else null)
@@ -1660,7 +1661,7 @@ void free_all(brisk_hip_index* h) {
     hipStreamSynchronize(h->stream);  // nothing of ours may be in flight when the arena is unmapped
     auto fr = [](void* p) { if (p) hipFree(p); };
     for (DevBuf* b : {&h->huge, &h->pend, &h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp, &h->enum_out,
-                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan})
+                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->ext_iv, &h->ext_tmp, &h->ext_src})
         fr(b->p);
     fr(h->d_coef);
     fr(h->d_tabs);
@@ -2251,6 +2252,158 @@ BRISK_API int brisk_hip_read_profile_packed(brisk_hip_index* h, const uint32_t* 
     return check_device_flags(h);
 }
 
+// ---- read extraction: rule, gather, the composed calls (no reference counterpart; kernels: brisk_extract.hip) ----
+static_assert(sizeof(brisk_hip_read_interval) == sizeof(ReadInterval) && offsetof(brisk_hip_read_interval, len) == offsetof(ReadInterval, len), "the kernels write the C-ABI's interval");
+static_assert(BRISK_HIP_SELECT_SOLID_RUN == SELECT_SOLID_RUN && BRISK_HIP_SELECT_MEDIAN == SELECT_MEDIAN && BRISK_HIP_SELECT_PRESENT == SELECT_PRESENT, "the kernel's kinds are the header's");
+
+static int check_rule(brisk_hip_index* h, const brisk_hip_select_rule* rule, const char* who) {
+    if (!rule) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": null rule");
+    if (rule->struct_size < sizeof(brisk_hip_select_rule)) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.struct_size is smaller than brisk_hip_select_rule");
+    if (rule->kind > BRISK_HIP_SELECT_PRESENT) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": unknown rule.kind " + std::to_string(rule->kind));
+    if (rule->lo > rule->hi) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.lo " + std::to_string(rule->lo) + " is above rule.hi " + std::to_string(rule->hi));
+    return BRISK_HIP_OK;
+}
+// the handle's lock is held; the rule is checked
+static int select_impl(brisk_hip_index* h, const ReadProfile* d_prof, u64 n_reads, const brisk_hip_select_rule* rule, ReadInterval* d_iv) {
+    if (!n_reads) return BRISK_HIP_OK;
+    hipLaunchKernelGGL(k_select_intervals, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_prof, n_reads, (u32)h->P.k, rule->kind, std::max<u32>(rule->min_len, h->P.k), rule->lo,
+                       rule->hi, d_iv);
+    return launch_check(h, "k_select_intervals");
+}
+
+BRISK_API int brisk_hip_select_intervals(brisk_hip_index* h, const brisk_hip_read_profile* d_profiles, uint64_t n_reads, const brisk_hip_select_rule* rule,
+                                         brisk_hip_read_interval* d_intervals) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int rrc = check_rule(h, rule, "select_intervals")) return rrc;
+    if (n_reads && (!d_profiles || !d_intervals)) return fail(h, BRISK_HIP_EINVAL, "select_intervals: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int rc = select_impl(h, (const ReadProfile*)d_profiles, n_reads, rule, (ReadInterval*)d_intervals)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held.  Counts and flags first (one pass over the table, a host synchronisation), then -- only when the
+// intervals are valid and the output has room -- the tables of the kept reads and the gather: a refused call writes nothing.
+static int extract_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, const ReadInterval* d_iv, u32* d_out, u64 cap_words, u64* d_out_starts,
+                        u64* d_out_index, u64* n_out_reads, u64* n_out_nts) {
+    int rc;
+    *n_out_reads = *n_out_nts = 0;
+    u64 n_out = 0, n_nts = 0;
+    const u32 nb = nblocks(n_reads, 256 * EXT_ITEMS);
+    u64 *d_bs_reads = nullptr, *d_bs_nts = nullptr;
+    if (n_reads) {
+        // [64 bytes of flags][block sums of kept reads, nb + 1][of kept nucleotides, nb + 1]
+        if ((rc = ensure(h, h->ext_tmp, 64 + 2 * ((size_t)nb + 1) * 8))) return rc;
+        unsigned long long* d_flags = (unsigned long long*)h->ext_tmp.p;
+        d_bs_reads = (u64*)((char*)h->ext_tmp.p + 64);
+        d_bs_nts = d_bs_reads + nb + 1;
+        HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 8, h->stream));
+        HIPCHK(h, hipMemsetAsync(d_flags + 1, 0, 8, h->stream));
+        hipLaunchKernelGGL(k_extract_block, dim3(nb), dim3(256), 0, h->stream, d_starts, d_iv, n_reads, d_bs_reads, d_bs_nts, d_flags);
+        hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bs_reads, nb);
+        hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bs_nts, nb);
+        if ((rc = launch_check(h, "k_extract_block / k_slot_top"))) return rc;
+        u64 got[4] = {0, 0, 0, 0};
+        HIPCHK(h, hipMemcpyAsync(got, d_flags, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 2, d_bs_reads + nb, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 3, d_bs_nts + nb, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (got[1]) return fail(h, BRISK_HIP_EINVAL, "extract_packed: read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (got[0] != ~0ull) return fail(h, BRISK_HIP_EINVAL, "extract_packed: the interval of read " + std::to_string(got[0]) + " ends beyond the read (start + len > its length)");
+        n_out = got[2];
+        n_nts = got[3];
+    }
+    *n_out_reads = n_out;
+    *n_out_nts = n_nts;
+    const u64 n_words = (n_nts + 15) / 16;
+    if (cap_words < n_words + 2)
+        return fail(h, BRISK_HIP_ECAPACITY, "extract_packed: " + std::to_string(n_nts) + " kept nucleotides need " + std::to_string(n_words + 2) + " words, out_cap_words is " + std::to_string(cap_words));
+    if (!n_out) {  // nothing kept: the empty stream
+        HIPCHK(h, hipMemsetAsync(d_out_starts, 0, 8, h->stream));
+        HIPCHK(h, hipMemsetAsync(d_out, 0, 8, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    }
+    if ((rc = ensure(h, h->ext_src, n_out * 8))) return rc;
+    hipLaunchKernelGGL(k_extract_apply, dim3(nb), dim3(256), 0, h->stream, d_starts, d_iv, n_reads, (const u64*)d_bs_reads, (const u64*)d_bs_nts, d_out_starts, d_out_index,
+                       (u64*)h->ext_src.p);
+    if ((rc = launch_check(h, "k_extract_apply"))) return rc;
+    if (n_words + 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "extract_packed: more output words than one launch covers");
+    hipLaunchKernelGGL(k_extract_gather, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_packed, (const u64*)d_out_starts, (const u64*)h->ext_src.p, n_out, n_words, d_out);
+    if ((rc = launch_check(h, "k_extract_gather"))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_extract_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, const brisk_hip_read_interval* d_intervals,
+                                       uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, uint64_t* d_out_index, uint64_t* n_out_reads,
+                                       uint64_t* n_out_nts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!n_out_reads || !n_out_nts || !d_out_packed || !d_out_starts || (n_reads && (!d_packed || !d_starts || !d_intervals))) return fail(h, BRISK_HIP_EINVAL, "extract_packed: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    return extract_impl(h, d_packed, d_starts, n_reads, (const ReadInterval*)d_intervals, d_out_packed, out_cap_words, d_out_starts, d_out_index, n_out_reads, n_out_nts);
+}
+
+BRISK_API int brisk_hip_trim_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, const brisk_hip_select_rule* rule,
+                                    uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, uint64_t* d_out_index, uint64_t* n_out_reads, uint64_t* n_out_nts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "trim_packed on a sharded index sees one bucket range only");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "trim_packed on an entry-id index: DATA lives with the caller (find_kmers)");
+    if (int rrc = check_rule(h, rule, "trim_packed")) return rrc;
+    if (!n_out_reads || !n_out_nts || !d_out_packed || !d_out_starts || (n_reads && (!d_packed || !d_starts))) return fail(h, BRISK_HIP_EINVAL, "trim_packed: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    int rc;
+    if (n_reads) {
+        if ((rc = ensure(h, h->ext_iv, n_reads * sizeof(ReadInterval)))) return rc;
+        const u64 batch = std::min<u64>(h->max_batch_reads, profile_batch_reads());
+        if ((rc = ensure(h, h->prof_out, std::min<u64>(batch, n_reads) * sizeof(ReadProfile)))) return rc;
+        for (u64 r0 = 0; r0 < n_reads; r0 += batch) {
+            const u64 nb = std::min<u64>(batch, n_reads - r0);
+            u64 ns = 0;
+            if ((rc = count_kmers(h, d_starts + r0, nb, &ns))) return rc;  // (EINVAL on a table that does not ascend)
+            if ((rc = profile_batch(h, d_packed, d_starts + r0, nb, ns, solid_min, (ReadProfile*)h->prof_out.p))) return rc;
+            if ((rc = select_impl(h, (const ReadProfile*)h->prof_out.p, nb, rule, (ReadInterval*)h->ext_iv.p + r0))) return rc;
+        }
+        if ((rc = check_device_flags(h))) return rc;
+    }
+    return extract_impl(h, d_packed, d_starts, n_reads, (const ReadInterval*)h->ext_iv.p, d_out_packed, out_cap_words, d_out_starts, d_out_index, n_out_reads, n_out_nts);
+}
+
+BRISK_API int brisk_hip_trim_reads(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t solid_min, const brisk_hip_select_rule* rule,
+                                   brisk_hip_read_interval* out) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "trim_reads on a sharded index sees one bucket range only");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "trim_reads on an entry-id index: DATA lives with the caller (find_kmers)");
+    if (int rrc = check_rule(h, rule, "trim_reads")) return rrc;
+    if (n_reads && (!bases || !offsets || !out)) return fail(h, BRISK_HIP_EINVAL, "trim_reads: null pointer");
+    for (u64 r = 0; r < n_reads; r++) {
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (offsets[r + 1] - offsets[r] >= PROFILE_MAX_SLOTS + h->P.k) return fail(h, BRISK_HIP_EINVAL, "trim_reads: a read of more than 2^32-1 slots does not fit the record");
+    }
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    BatchLimit limit(h);
+    int rc = for_each_host_batch(h, bases, offsets, n_reads, [&](u64 r0, u64 nr) -> int {
+        int rc2;
+        if ((rc2 = ensure(h, h->prof_out, nr * sizeof(ReadProfile)))) return rc2;
+        if ((rc2 = ensure(h, h->ext_iv, nr * sizeof(ReadInterval)))) return rc2;
+        if ((rc2 = profile_batch(h, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, nr, host_slots(offsets, r0, r0 + nr, h->P.k), solid_min, (ReadProfile*)h->prof_out.p)))
+            return rc2;
+        if ((rc2 = select_impl(h, (const ReadProfile*)h->prof_out.p, nr, rule, (ReadInterval*)h->ext_iv.p))) return rc2;
+        HIPCHK(h, hipMemcpyAsync(out + r0, h->ext_iv.p, nr * sizeof(ReadInterval), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    });
+    if (rc) return rc;
+    return check_device_flags(h);
+}
+
 BRISK_API int brisk_hip_lookup(brisk_hip_index* h, const uint64_t* kmer_lo, const uint64_t* kmer_hi, const uint8_t* minimizer_idx, uint64_t n,
                                uint8_t* out_data, uint8_t* out_found) {
     if (!h || (n && (!kmer_lo || !kmer_hi || !minimizer_idx || !out_data || !out_found))) return BRISK_HIP_EINVAL;
@@ -2453,7 +2606,7 @@ BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t
     if (memory_bytes) {
         u64 m = h->arena_cap * (8ull * h->ix.key_words + 1) + h->n_parts * 16 + (h->n_buckets + 7) / 8 + (h->n_parts + 1) * 20;
         for (const DevBuf* b : {&h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp,
-                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan})
+                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->ext_iv, &h->ext_tmp, &h->ext_src})
             m += b->bytes;
         *memory_bytes = m;
     }
@@ -3609,6 +3762,16 @@ BRISK_API int brisk_hip_pack_ascii(brisk_hip_index* h, const char* d_bases, uint
     ProfScope ps(h, S_PACK);
     hipLaunchKernelGGL(k_pack_ascii, dim3(nblocks(n_words, 256)), dim3(256), 0, h->stream, (const uint8_t*)d_bases, n_bases, d_packed, n_words);
     return launch_check(h, "k_pack_ascii");
+}
+
+BRISK_API int brisk_hip_unpack_ascii(brisk_hip_index* h, const uint32_t* d_packed, uint64_t first_nt, uint64_t n_nts, char* d_bases) {
+    if (!h || (n_nts && (!d_packed || !d_bases))) return BRISK_HIP_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (!n_nts) return BRISK_HIP_OK;
+    if ((n_nts + 15) / 16 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "unpack_ascii: more nucleotides than one launch covers");
+    hipLaunchKernelGGL(k_unpack_ascii, dim3(nblocks((n_nts + 15) / 16, 256)), dim3(256), 0, h->stream, d_packed, first_nt, n_nts, (uint8_t*)d_bases);
+    return launch_check(h, "k_unpack_ascii");
 }
 
 BRISK_API int brisk_hip_synth_reads(brisk_hip_index* h, uint64_t genome_len, uint64_t first_read, uint64_t n_reads, uint32_t read_len,

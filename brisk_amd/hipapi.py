@@ -34,7 +34,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU). In-tree output."""
     out = library_path()
     srcs = [os.path.join(HERE, "csrc", f) for f in ("brisk_capi.hip", "brisk_kernels.hip", "brisk_scan.hip", "brisk_partition.hip", "brisk_insert.hip",
-                                                    "brisk_readout.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_device.h")]
+                                                    "brisk_readout.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_extract.hip", "brisk_device.h")]
     srcs.append(os.path.join(ROOT, "include", "brisk_hip.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
@@ -115,6 +115,7 @@ SYMBOLS = [
     "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
     "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune",
     "brisk_hip_read_profile_reads", "brisk_hip_read_profile_packed",
+    "brisk_hip_select_intervals", "brisk_hip_extract_packed", "brisk_hip_trim_packed", "brisk_hip_trim_reads", "brisk_hip_unpack_ascii",
     "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
     "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
@@ -151,6 +152,12 @@ def load() -> C.CDLL:
     _profp = np.ctypeslib.ndpointer(dtype=READ_PROFILE_DTYPE, flags="C_CONTIGUOUS")
     L.brisk_hip_read_profile_reads.argtypes = [vp, _u8p, _u64p, u64, u32, _profp]
     L.brisk_hip_read_profile_packed.argtypes = [vp, vp, vp, u64, u32, vp]
+    _ivp = np.ctypeslib.ndpointer(dtype=READ_INTERVAL_DTYPE, flags="C_CONTIGUOUS")
+    L.brisk_hip_select_intervals.argtypes = [vp, vp, u64, C.POINTER(_SelectRule), vp]
+    L.brisk_hip_extract_packed.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.brisk_hip_trim_packed.argtypes = [vp, vp, vp, u64, u32, C.POINTER(_SelectRule), vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.brisk_hip_trim_reads.argtypes = [vp, _u8p, _u64p, u64, u32, C.POINTER(_SelectRule), _ivp]
+    L.brisk_hip_unpack_ascii.argtypes = [vp, vp, u64, u64, vp]
     L.brisk_hip_enumerate.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64)]
     L.brisk_hip_stats.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.brisk_hip_checksum.argtypes = [vp, _u64p]
@@ -254,6 +261,54 @@ def profile_from_slots(counts, found, base, solid_min: int) -> np.ndarray:
             starts, ends = np.nonzero(edge == 1)[0], np.nonzero(edge == -1)[0]
             best = int(np.argmax(ends - starts))  # argmax returns the first of equal maxima
             rec["run_start"], rec["run_len"] = starts[best], ends[best] - starts[best]
+    return out
+
+
+# brisk_hip_read_interval (include/brisk_hip.h): nucleotides [start, start + len) of a read; len == 0: the read is dropped
+READ_INTERVAL_DTYPE = np.dtype([("start", "<u4"), ("len", "<u4")])
+assert READ_INTERVAL_DTYPE.itemsize == 8
+
+# brisk_hip_select_rule.kind: BRISK_HIP_SELECT_SOLID_RUN / _MEDIAN / _PRESENT ("trim" is the command line's name for the first)
+SELECT_KINDS = {"solid_run": 0, "trim": 0, "median": 1, "present": 2}
+
+
+class _SelectRule(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "kind", "min_len", "lo", "hi")]
+
+
+def select_rule(kind, min_len: int = 0, lo: int = 0, hi: int = 0xffffffff) -> _SelectRule:
+    """A brisk_hip_select_rule: kind "solid_run" (the nucleotides the first longest run of solid k-mers covers), "median" (the whole
+    read when lo <= median <= hi) or "present" (the whole read when lo <= 1000 * n_present / n_kmers <= hi, in permille), or the
+    number of one; min_len: a kept interval has at least max(min_len, k) nucleotides.  Nothing is checked here: the library (EINVAL)
+    and intervals_from_profile (ValueError) refuse an unknown kind and lo > hi."""
+    return _SelectRule(C.sizeof(_SelectRule), SELECT_KINDS[kind] if isinstance(kind, str) else int(kind), min_len, lo, hi)
+
+
+def intervals_from_profile(profile, k: int, rule) -> np.ndarray:
+    """The rule of brisk_hip_select_intervals on the host: READ_INTERVAL_DTYPE[n] from READ_PROFILE_DTYPE[n] records, the handle's k
+    and a select_rule(...).  The definition, written out; no device needed.  A read without k-mers is dropped (len 0), and so is an
+    interval shorter than max(min_len, k) nucleotides or longer than 2^32 - 1."""
+    if rule.struct_size < C.sizeof(_SelectRule) or rule.kind > 2 or rule.lo > rule.hi:
+        raise ValueError("not a rule: struct_size %d kind %d lo %d hi %d" % (rule.struct_size, rule.kind, rule.lo, rule.hi))
+    p = np.asarray(profile)
+    assert p.dtype == READ_PROFILE_DTYPE
+    n_kmers, lo, hi = p["n_kmers"].astype(np.int64), int(rule.lo), int(rule.hi)
+    start = np.zeros(len(p), np.int64)
+    if rule.kind == 0:
+        keep = p["run_len"] >= 1
+        start = np.where(keep, p["run_start"].astype(np.int64), 0)
+        length = np.where(keep, p["run_len"].astype(np.int64) + k - 1, 0)
+    else:
+        if rule.kind == 1:
+            keep = (p["median"] >= lo) & (p["median"] <= hi)
+        else:  # (Python integers where a product can pass 2^63)
+            n_present = p["n_present"].astype(np.int64)
+            keep = np.array([lo * int(n) <= 1000 * int(q) <= hi * int(n) for n, q in zip(n_kmers, n_present)], bool)
+        length = np.where(keep, n_kmers + k - 1, 0)
+    keep = (n_kmers > 0) & (length >= max(int(rule.min_len), k)) & (length <= 0xffffffff)
+    out = np.zeros(len(p), READ_INTERVAL_DTYPE)
+    out["start"] = np.where(keep, start, 0)
+    out["len"] = np.where(keep, length, 0)
     return out
 
 
@@ -381,6 +436,18 @@ class BriskHip:
             flat = np.zeros(1, np.uint8)
         self._chk(self.L.brisk_hip_read_profile_reads(self.h, flat, offs, len(offs) - 1, solid_min, out if len(out) else np.zeros(1, READ_PROFILE_DTYPE)))
         return out
+
+    def trim_reads(self, seqs: Sequence, solid_min: int = 2, rule: Optional[_SelectRule] = None) -> np.ndarray:
+        """One interval per read (brisk_hip_trim_reads): READ_INTERVAL_DTYPE[n_reads] -- what intervals_from_profile(read_profile(seqs,
+        solid_min), k, rule) gives, computed on the device; seqs[i][start:start + len] is what the rule keeps of read i, and len == 0
+        means that the read is dropped.  rule: a select_rule(...); the default is select_rule("solid_run")."""
+        flat, offs = _pack_reads(seqs)
+        out = np.zeros(max(len(offs) - 1, 1), READ_INTERVAL_DTYPE)
+        if len(flat) == 0:
+            flat = np.zeros(1, np.uint8)
+        rule = select_rule("solid_run") if rule is None else rule
+        self._chk(self.L.brisk_hip_trim_reads(self.h, flat, offs, len(offs) - 1, solid_min, C.byref(rule), out))
+        return out[:len(offs) - 1]
 
     def lookup(self, lo, hi, idx) -> Tuple[np.ndarray, np.ndarray]:
         lo = np.ascontiguousarray(lo, np.uint64)
@@ -550,6 +617,32 @@ class BriskHip:
         """per-read abundance records (brisk_hip_read_profile_packed), reads and records (32 bytes a read, READ_PROFILE_DTYPE) on the device"""
         self._chk(self.L.brisk_hip_read_profile_packed(self.h, d_packed, d_starts, n_reads, solid_min, d_out))
 
+    def select_intervals(self, d_profiles: int, n_reads: int, rule: _SelectRule, d_intervals: int):
+        """d_intervals[r] (READ_INTERVAL_DTYPE, 8 bytes a read) = the rule applied to d_profiles[r] (brisk_hip_select_intervals), both on
+        the device"""
+        self._chk(self.L.brisk_hip_select_intervals(self.h, d_profiles, n_reads, C.byref(rule), d_intervals))
+
+    def extract_packed(self, d_packed: int, d_starts: int, n_reads: int, d_intervals: int, d_out_packed: int, out_cap_words: int, d_out_starts: int,
+                       d_out_index: Optional[int] = None) -> Tuple[int, int]:
+        """the kept intervals of a packed stream as a new packed stream (brisk_hip_extract_packed), everything on the device; returns
+        (kept reads, kept nucleotides).  d_out_packed holds out_cap_words >= ceil(nts / 16) + 2 words (as many as the input always do),
+        d_out_starts n_reads + 1 uint64, d_out_index (optional) n_reads uint64: the input index of every kept read."""
+        n_out, n_nts = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.brisk_hip_extract_packed(self.h, d_packed, d_starts, n_reads, d_intervals, d_out_packed, out_cap_words, d_out_starts, d_out_index,
+                                                  C.byref(n_out), C.byref(n_nts)))
+        return n_out.value, n_nts.value
+
+    def trim_packed(self, d_packed: int, d_starts: int, n_reads: int, d_out_packed: int, out_cap_words: int, d_out_starts: int,
+                    d_out_index: Optional[int] = None, solid_min: int = 2, rule: Optional[_SelectRule] = None) -> Tuple[int, int]:
+        """read_profile_packed, the rule (default select_rule("solid_run")) and extract_packed in one call (brisk_hip_trim_packed):
+        the trimmed or filtered reads as a packed stream that insert_packed, get_packed and read_profile_packed take; returns (kept
+        reads, kept nucleotides)"""
+        rule = select_rule("solid_run") if rule is None else rule
+        n_out, n_nts = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.brisk_hip_trim_packed(self.h, d_packed, d_starts, n_reads, solid_min, C.byref(rule), d_out_packed, out_cap_words, d_out_starts, d_out_index,
+                                               C.byref(n_out), C.byref(n_nts)))
+        return n_out.value, n_nts.value
+
     def scan_bound(self, d_starts: int, n_reads: int) -> int:
         out = C.c_uint64()
         self._chk(self.L.brisk_hip_scan_bound(self.h, d_starts, n_reads, C.byref(out)))
@@ -612,6 +705,10 @@ class BriskHip:
 
     def pack_ascii(self, d_bases: int, n_bases: int, d_packed: int):
         self._chk(self.L.brisk_hip_pack_ascii(self.h, d_bases, n_bases, d_packed))
+
+    def unpack_ascii(self, d_packed: int, first_nt: int, n_nts: int, d_bases: int):
+        """d_bases[i] = "ACTG"[code of nucleotide first_nt + i of the packed stream] (brisk_hip_unpack_ascii): pack_ascii's inverse"""
+        self._chk(self.L.brisk_hip_unpack_ascii(self.h, d_packed, first_nt, n_nts, d_bases))
 
     def synth_reads(self, genome_len: int, first_read: int, n_reads: int, read_len: int, d_packed: int, d_starts: int,
                     seed_g: int = 1, seed_r: int = 2):

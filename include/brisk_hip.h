@@ -50,6 +50,10 @@
  *                               no reference counterpart (the reference answers one k-mer or one super-k-mer at a time; khmer's
  *                               normalize-by-median and trim-low-abund are the usual tools): the answers of brisk_hip_get_kmers
  *                               reduced on the device to one abundance record per read
+ *   brisk_hip_select_intervals / brisk_hip_extract_packed / brisk_hip_trim_packed / brisk_hip_trim_reads
+ *                               no reference counterpart (khmer's trim-low-abund and normalize-by-median act on the abundances
+ *                               that brisk_hip_read_profile_* measures): a profile record becomes a nucleotide interval of its
+ *                               read, and the kept intervals a new packed stream, on the device
  *   brisk_hip_lookup            Brisk::get (brisk/Brisk.hpp:64-69)
  *   brisk_hip_enumerate         Brisk::next / restart_kmer_enumeration
  *                               (brisk/Brisk.hpp:166-179, brisk/DenseMenuYo.hpp:476-521)
@@ -88,6 +92,8 @@
  *   brisk_hip_find_kmers        Brisk::get_superkmer / Brisk::get (brisk/Brisk.hpp:64-69,102-118)
  *   brisk_hip_enumerate_ids     Brisk::next (brisk/Brisk.hpp:166-172)
  *   brisk_hip_pack_ascii        nuc2int (brisk/Kmers.cpp:442-444) applied in bulk
+ *   brisk_hip_unpack_ascii      no reference counterpart (kmer2str, brisk/Kmers.cpp, prints one k-mer): the inverse of
+ *                               brisk_hip_pack_ascii over a stretch of a packed stream
  *   brisk_hip_synth_reads       no reference counterpart (benchmark input,
  *                               SURVEY.md 8(d))
  *   brisk_hip_debug_order_keys  bfc_hash_64 + DecyclingSet::memDouble in bulk
@@ -263,6 +269,59 @@ int brisk_hip_read_profile_reads(brisk_hip_index *h, const char *bases, const ui
 /* DEVICE reads (layout of brisk_hip_insert_packed); d_out[n_reads] DEVICE */
 int brisk_hip_read_profile_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
                                   uint32_t solid_min, brisk_hip_read_profile *d_out);
+
+/* ---- read extraction: trim and filter by abundance profile (no reference counterpart) ---- */
+/* A rule turns a profile record into an interval of its read, in nucleotides; len == 0 means that the read is dropped.
+ *   BRISK_HIP_SELECT_SOLID_RUN  [run_start, run_start + run_len + k - 1) when run_len >= 1 (the nucleotides that the first longest run
+ *                               of solid k-mers covers: abundance trimming), else dropped
+ *   BRISK_HIP_SELECT_MEDIAN     the whole read [0, n_kmers + k - 1) when lo <= median <= hi (digital normalisation keeps a read whose
+ *                               median is below its cut-off; a screen keeps one whose median is at least 1), else dropped
+ *   BRISK_HIP_SELECT_PRESENT    the whole read when lo * n_kmers <= 1000 * n_present <= hi * n_kmers (the share of the read's k-mers
+ *                               that are in the index, in permille, 64-bit products), else dropped
+ * For every kind: a read with n_kmers == 0 is dropped, and so is an interval shorter than max(min_len, k) nucleotides (and one of
+ * 2^32 nucleotides or more, which the record cannot hold).  EINVAL: a null rule, struct_size < sizeof(brisk_hip_select_rule), an
+ * unknown kind, lo > hi.  brisk_amd.intervals_from_profile is the same rule in numpy: the definition the tests compare with. */
+typedef struct brisk_hip_read_interval { uint32_t start, len; } brisk_hip_read_interval; /* nucleotides of the read; len == 0: the read is dropped */
+enum { BRISK_HIP_SELECT_SOLID_RUN = 0, BRISK_HIP_SELECT_MEDIAN = 1, BRISK_HIP_SELECT_PRESENT = 2 };
+typedef struct brisk_hip_select_rule {
+    uint32_t struct_size;
+    uint32_t kind;
+    uint32_t min_len;   /* kept interval must have at least this many nts; 0 means k */
+    uint32_t lo, hi;    /* MEDIAN: lo <= record.median <= hi.  PRESENT: lo*n_kmers <= 1000*n_present <= hi*n_kmers (permille, 64-bit products) */
+} brisk_hip_select_rule;
+/* d_intervals[r] = the rule applied to d_profiles[r] (both DEVICE, n_reads each), with the handle's k.  Needs no index state: any
+ * handle serves. */
+int brisk_hip_select_intervals(brisk_hip_index *h, const brisk_hip_read_profile *d_profiles, uint64_t n_reads,
+                               const brisk_hip_select_rule *rule, brisk_hip_read_interval *d_intervals);
+/* The kept intervals of a packed stream as a new packed stream, all on the device.  Input: the layout of brisk_hip_insert_packed and
+ * d_intervals[n_reads].  Output, in the same layout: 16 nts per u32, first nt in the top bits; the kept reads (len > 0) concatenated
+ * at nucleotide granularity in input order, dropped reads absent; d_out_starts[0 .. n_out] ascending from 0 (room for n_reads + 1);
+ * d_out_index[j] (room for n_reads; may be NULL) = the index, in the input, of kept read j; the unused low bits of the last word zero
+ * and the two words after it zero ("readable 8 bytes past the last used word").  *n_out_reads and *n_out_nts (HOST) receive the
+ * counts (64-bit: 50 M reads of 150 bp are 7.5 G nucleotides).  out_cap_words >= ceil(n_out_nts / 16) + 2 is required -- an output
+ * of as many words as the input stream has, its two readable words included, always suffices -- else BRISK_HIP_ECAPACITY, nothing
+ * written (the counts are: the call can be repeated with room).  EINVAL, nothing written: an interval with start + len beyond its
+ * read (found on the device; the message names the first such read), a read table that does not ascend, null pointers.  The output
+ * may not overlap the input.  Every output word is stored once by a plain vector store; no source word past the last one that
+ * holds a kept nucleotide is read.  Needs no index state: works on any handle (sharded and entry-id ones included), on the handle's
+ * stream and under its lock; it returns when the output is complete. */
+int brisk_hip_extract_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                             const brisk_hip_read_interval *d_intervals,
+                             uint32_t *d_out_packed, uint64_t out_cap_words, uint64_t *d_out_starts /* n_reads+1 room */,
+                             uint64_t *d_out_index /* n_reads room, may be NULL: original index of each kept read */,
+                             uint64_t *n_out_reads, uint64_t *n_out_nts /* HOST */);
+/* brisk_hip_read_profile_packed, the rule, brisk_hip_extract_packed in one call: profile, trim, and the trimmed reads are ready for
+ * brisk_hip_insert_packed / _get_packed / _read_profile_packed without leaving the device.  The records (one internal batch at a
+ * time) and the intervals (8 bytes a read) live in scratch memory of the handle.  trim_reads takes HOST reads (layout of
+ * brisk_hip_get_reads) and returns only the intervals, out[n_reads] HOST: the caller slices its own strings.  Both inherit
+ * brisk_hip_read_profile_*: pending deferred inserts are completed first; EINVAL on a sharded index, on an entry-id index, on offsets
+ * that do not ascend; the answer does not depend on max_batch_reads, BRISK_PROFILE_BATCH, BRISK_PROFILE_SEG or on which kernels run. */
+int brisk_hip_trim_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                          uint32_t solid_min, const brisk_hip_select_rule *rule,
+                          uint32_t *d_out_packed, uint64_t out_cap_words, uint64_t *d_out_starts, uint64_t *d_out_index,
+                          uint64_t *n_out_reads, uint64_t *n_out_nts);
+int brisk_hip_trim_reads(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
+                         uint32_t solid_min, const brisk_hip_select_rule *rule, brisk_hip_read_interval *out /* HOST, n_reads */);
 
 /* point lookups of UNHASHED (kmer_s, minimizer_idx) pairs, as Brisk::get takes them.
  * HOST arrays; out_found[i] in {0,1}; out_data[i] valid when found. */
@@ -477,6 +536,9 @@ int brisk_hip_enumerate_ids(brisk_hip_index *h, uint64_t *cursor, uint64_t *out_
 
 /* ---- helpers on device buffers -------------------------------------------- */
 int brisk_hip_pack_ascii(brisk_hip_index *h, const char *d_bases, uint64_t n_bases, uint32_t *d_packed);
+/* the inverse: d_bases[i] = "ACTG"[code of nucleotide first_nt + i of the packed stream], i < n_nts (upper case; DEVICE buffers).
+ * Words past the one that holds nucleotide first_nt + n_nts - 1 are not read.  Queued on the handle's stream, as pack_ascii is. */
+int brisk_hip_unpack_ascii(brisk_hip_index *h, const uint32_t *d_packed, uint64_t first_nt, uint64_t n_nts, char *d_bases);
 /* synthetic reads of SURVEY.md 8(d), written packed; d_starts[n_reads+1] */
 int brisk_hip_synth_reads(brisk_hip_index *h, uint64_t genome_len, uint64_t first_read, uint64_t n_reads,
                           uint32_t read_len, uint64_t seed_g, uint64_t seed_r,
