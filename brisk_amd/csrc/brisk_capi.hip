@@ -1733,7 +1733,8 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
     P.kb = k - b;
     P.nw = (2 * (2 * k - m - b) + 63) / 64;
     P.stride = P.nw + 1;
-    // Partitions: by default up to 2^24 of them whatever b is -- a small b leaves few buckets, so records are routed
+    // Partitions: by default up to 2^24 of them whatever b is (2^25 with three class bits at m = 11, b >= 5: an extended routing id
+    // is never cut, below) -- a small b leaves few buckets, so records are routed
     // by the bucket id plus ext_bits more bits of the same hashed minimizer (at most what it has: 2m - 2b, and what
     // the record header has room for).  An explicit part_bits keeps plain bucket ranges.
     // A minimizer of fewer than 12 nts has fewer than 24 hash bits to give: the partitions of such an index are few and
@@ -1754,11 +1755,15 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
         if (P.cls_bits) P.cls_width = (P.w + 1 + (1u << P.cls_bits) - 1) >> P.cls_bits;
     }
     const u32 rbits = 2u * b + P.ext_bits;
-    P.part_bits = o.part_bits ? std::min<u32>(o.part_bits, 2u * b) : std::min<u32>(rbits, 24u);
+    // An extended routing id is never cut: the insert's bucket bitmap, its rebuild and the stats read a partition with ext_bits > 0
+    // as a slice of ONE bucket (shift == 0).  2b + ext_bits passes 24 only with BRISK_CLS_BITS=3 at m = 11, b >= 5 (25 bits:
+    // 2^25 partitions); with shift = 1 there, two classes of one bucket were counted as two buckets in nb_buckets.
+    P.part_bits = o.part_bits ? std::min<u32>(o.part_bits, 2u * b) : P.ext_bits ? rbits : std::min<u32>(rbits, 24u);
     P.shift = rbits - P.part_bits;
     // the entry key [routing id low bits | compacted | idx'] must fit 128 bits
     while (P.shift + 2 * P.kb + 6 > 128 && P.shift > 0) { P.shift--; P.part_bits++; }
-    if (P.shift + 2 * P.kb + 6 > 128 || P.part_bits > 30) {
+    // (ext_bits > 0 && shift > 0 cannot come out of the lines above; k_insert's bucket bits, k_bucket_bits_rebuild and k_stats rely on it)
+    if (P.shift + 2 * P.kb + 6 > 128 || P.part_bits > 30 || (P.ext_bits && P.shift)) {
         delete h;
         return BRISK_HIP_EUNSUPPORTED;
     }

@@ -555,7 +555,8 @@ class BriskHip:
         the header: k, m, b and count_mode as stored and part_bits = 0 if ext_bits > 0 else part_bits -- brisk_hip_create extends the routing id
         (ext_bits > 0) only when part_bits was left at its default of 0, and without an extension the stored part_bits is what an
         explicit part_bits gives (min(part_bits, 2b), 2^24 partitions at most by default).  cls_bits also depends on the environment
-        (BRISK_CLS_BITS): a file saved under another setting is refused by load (EINVAL, the field named).  **kw: further
+        (BRISK_CLS_BITS): a file saved under another setting is refused by load (EINVAL, the field named) -- and so is one saved under
+        BRISK_CLS_BITS=3 at m = 11, b >= 5 by a library from before such an index had 2^25 partitions (part_bits is named).  **kw: further
         constructor options (max_batch_reads, immediate_inserts, ...)."""
         info = snapshot_info(path)
         kw.setdefault("count_mode", {v: n for n, v in COUNT_MODES.items()}[info["count_mode"]])
