@@ -260,16 +260,17 @@ __global__ void __launch_bounds__(256) k_owner_hist(BriskParams P, const u64* __
 __global__ void __launch_bounds__(ROUTE_MAX_OWNERS) k_owner_offsets(u32 n_owners, u32 n_blocks, const unsigned long long* __restrict__ hist,
                                                                    u32* __restrict__ block_cnt, u32* __restrict__ off) {
     const u32 o = threadIdx.x;
-    if (o > n_owners) return;
+    if (o >= n_owners) return;
     u32 start = 0;
-    for (u32 j = 0; j < o && j < n_owners; j++) start += (u32)hist[j];
+    for (u32 j = 0; j < o; j++) start += (u32)hist[j];
     off[o] = start;
-    if (o == n_owners) return;
     for (u32 b = 0; b < n_blocks; b++) {
         const u32 c = block_cnt[(u64)b * n_owners + o];
         block_cnt[(u64)b * n_owners + o] = start;
         start += c;
     }
+    // the total comes from the last owner's thread: a block of ROUTE_MAX_OWNERS threads has no thread n_owners when n_owners is the maximum
+    if (o == n_owners - 1) off[n_owners] = start;
 }
 __global__ void __launch_bounds__(256) k_owner_scatter(BriskParams P, const u64* __restrict__ rec, u64 n_rec, u64 chunk,
                                                        const u32* __restrict__ block_off, u64* __restrict__ out,

@@ -361,7 +361,10 @@ class ShardedCounter:
 
     def stats(self) -> dict:
         """Brisk::stats of the whole sharded index: buckets, super-k-mers, entries and memory add up over the
-        owners (bucket ranges are disjoint), the largest bucket is the maximum."""
+        owners (bucket ranges are disjoint), the largest bucket is the maximum.  Where the routing id is
+        extended (layout["ext_bits"] > 0: 2b < 24) a bucket is 2^ext_bits partitions, and an owner boundary that is no multiple
+        of that cuts a bucket in two: nb_buckets then counts it once per owner that holds entries of it (an upper bound; exact
+        with a power-of-two number of equal owners up to 2^2b), and largest_bucket sees its parts.  Entries are never affected."""
         st = self.ix.stats()
         if self.world == 1:
             return st
