@@ -74,6 +74,8 @@ struct brisk_hip_index {
     double* d_coef = nullptr;
     double* d_tabs = nullptr;   // coef[128] + packed fixed-point decycling chunk tables (u64 bits), staged to LDS by k_scan2
     ScanCfg scfg{};
+    bool fresh = true;          // nothing has been inserted since create / clear: every partition is empty (k_insert_first's route).  Whatever may
+                                // put entries into the index clears it: inserts (deferred ones when they complete), merge, reallocate, snapshot load, upserts
     u32 insert_waves = 4096;    // most persistent k_insert waves any instantiation keeps resident (<= INSERT_SLOTS): sizes the arena reserve
     u32 scan_waves = 0;         // waves per k_scan2 block
     size_t scan_lds = 0;
@@ -93,6 +95,7 @@ struct brisk_hip_index {
     // scratch
     DevBuf route_buf;
     DevBuf bins;  // binned layout: n_parts bins of bin_cap records
+    DevBuf left;  // descriptor indices of the partitions k_insert_first left to k_insert_fast (n_touched of them at most)
     DevBuf huge;  // [0] number, [1..HUGE_LIST_CAP] descriptor indices of the batch's huge partitions (k_insert_huge)
     // Small insert batches are scanned at once and inserted later (flush_pending): their records collect here, their per-partition
     // counts in d_hist, until there are enough of them for the insert to work at its density, or a call needs the index.
@@ -494,6 +497,8 @@ int insert_records_impl(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
 int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool have_hist, const BinLayout* bl) {
     h->scan_hist_valid = false;  // d_hist is this batch's from here on
     if (n_rec == 0) return BRISK_HIP_OK;
+    const bool fresh = h->fresh;  // (a batch split after BRISK_HIP_ENOMEM takes the general route: conservative)
+    h->fresh = false;
     if (n_rec >= (1ull << 32)) return fail(h, BRISK_HIP_EINVAL, "more than 2^32-1 records in one batch");
     const BriskParams& P = h->P;
     int rc;
@@ -562,7 +567,7 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
     if ((rc = ensure_arena(h, h->h_small[3] + h->h_small[3] / 7 + (u64)h->insert_waves * ARENA_CHUNK))) return rc;
     {
         ProfScope ps(h, S_INSERT);
-        HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 8, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 16, h->stream));  // [6] the two work counters, [7] the left-over count
         // partitions of many records (few distinct minimizers: m <= 11) take the 512-instance kernel: half as many chunks, and
         // with them half as many passes over a partition's entries, outweigh its 2 waves per SIMD (k31/m11/b11: 48 -> 36 ms)
         const u32 batches = (n_touched + WI_BATCH - 1) / WI_BATCH;
@@ -571,19 +576,42 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         const RecSrc src{bl ? bl->bins : (u64*)h->parted.p, (const u64*)h->parted.p, bl ? bl->bin_cap : 0u};
         // persistent waves: as many as the device keeps resident (the kernel's time follows their number almost linearly)
         static const u32 wave_env = getenv("BRISK_INSERT_WAVES") ? (u32)atoi(getenv("BRISK_INSERT_WAVES")) : 0u;  // experiments
-        auto resident = [&](const void* fn) -> u32 {
+        const bool sat = h->count_mode == BRISK_HIP_COUNTS_SATURATE;
+        // cap_per_cu: a kernel built for at most so many waves (amdgpu_waves_per_eu's maximum).  The compiler holds the hardware to it
+        // through the register allotment in the kernel descriptor; the occupancy query works from the registers the code uses and
+        // would count waves that are never resident together (k_insert_first: 71 used, 80 allotted: 28 against 24 per CU).
+        auto resident = [&](const void* fn, int cap_per_cu = 0) -> u32 {
             int per_cu = 0, cus = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 16;
+            if (cap_per_cu && per_cu > cap_per_cu) per_cu = cap_per_cu;
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
             const u32 w = std::min<u32>((u32)per_cu * (u32)cus, h->insert_waves);
             static const bool dbg = getenv("BRISK_DEBUG_INSERT") != nullptr;
             if (dbg) fprintf(stderr, "[brisk_hip] k_insert: %d waves per CU x %d CUs resident, %u launched\n", per_cu, cus, wave_env ? std::min<u32>(w, wave_env) : w);
             return wave_env ? std::min<u32>(w, wave_env) : w;
         };
+        // The first batch into a fresh index: k_insert_first over all touched partitions, then k_insert_fast over those it left
+        // over (DESIGN.md section 4 finding 16).  Per call, not per partition: the flag is exact and costs no descriptor pass.
+        static const bool generic_only = getenv("BRISK_INSERT_GENERIC") != nullptr;  // A/B and tests: force the run-time body
+        static const bool lean_off = getenv("BRISK_INSERT_LEAN") && !strcmp(getenv("BRISK_INSERT_LEAN"), "0");  // A/B and tests: never take k_insert_first's route
+        const bool lean = fresh && !generic_only && !lean_off && !h->entry_ids && !big && P.nw == 3 && P.kb == 49 && P.shift >= 1 && P.shift <= 4;
+        if (lean) {
+            if ((rc = ensure(h, h->left, (size_t)n_touched * 4))) return rc;
+            static const bool dbg = getenv("BRISK_DEBUG_INSERT") != nullptr;
+            if (dbg) {
+                hipFuncAttributes fa{};
+                int per_cu = 0;
+                const void* fn = sat ? (const void*)k_insert_first<3, 49, 4, true> : (const void*)k_insert_first<3, 49, 4, false>;
+                if (hipFuncGetAttributes(&fa, fn) == hipSuccess && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) == hipSuccess) {
+                    fprintf(stderr, "[brisk_hip] k_insert_first: the occupancy query gives %d waves per CU, the kernel is built for at most %d\n", per_cu, 4 * WI_WAVES_PER_EU_FIRST_MAX);
+                    per_cu = std::min(per_cu, 4 * WI_WAVES_PER_EU_FIRST_MAX);  // (what resident() launches)
+                    fprintf(stderr, "[brisk_hip] k_insert_first: %d waves per CU, %d registers, %zu B of LDS, %zu B of scratch\n", per_cu, fa.numRegs, fa.sharedSizeBytes, fa.localSizeBytes);
+                }
+            }
+        }
         // instantiations with the record geometry (nw, k - b, routing-id bits kept in the key) as constants, for the
         // common parameter sets under the default partition layout; anything else takes the generic body
         // (every one of them twice: counts that wrap, and -- SAT -- counts that stop at 255; the mode is the handle's)
-        const bool sat = h->count_mode == BRISK_HIP_COUNTS_SATURATE;
 #define LAUNCH_INSERT_K(KERNEL, NW, KB, SH, SAT)                                                                                                                    \
     {                                                                                                                                                               \
         const dim3 grid(std::min<u32>(batches, resident((const void*)KERNEL<NW, KB, SH, SAT>)));                                                                  \
@@ -603,8 +631,28 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         else if (sat) LAUNCH_INSERT_K(k_insert_fast, NW, KB, SH, true)                                                                                              \
         else LAUNCH_INSERT_K(k_insert_fast, NW, KB, SH, false)                                                                                                      \
     }
-        static const bool generic_only = getenv("BRISK_INSERT_GENERIC") != nullptr;  // A/B and tests: force the run-time body
-        if (!generic_only && P.nw == 3 && P.kb == 49 && P.shift == 4) LAUNCH_INSERT_FAST(3, 49, 4)        // k63 m21 b14
+#define LAUNCH_INSERT_LEAN_K(SH, SAT)                                                                                                                               \
+    {                                                                                                                                                               \
+        u32* const wc = (u32*)(h->d_small + 6);                                                                                                                     \
+        u32* const n_left = (u32*)(h->d_small + 7);                                                                                                                 \
+        const dim3 grid(std::min<u32>(batches, resident((const void*)k_insert_first<3, 49, SH, SAT>, 4 * WI_WAVES_PER_EU_FIRST_MAX)));                                                            \
+        hipLaunchKernelGGL((k_insert_first<3, 49, SH, SAT>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix, wc,                \
+                           (u32*)h->left.p, n_left);                                                                                                                \
+        if ((rc = launch_check(h, "k_insert_first"))) return rc;                                                                                                    \
+        const dim3 grid2(std::min<u32>(batches, resident((const void*)k_insert_fast_listed<3, 49, SH, SAT>)));                                                     \
+        hipLaunchKernelGGL((k_insert_fast_listed<3, 49, SH, SAT>), grid2, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix, wc + 1,     \
+                           (const u32*)h->left.p, (const u32*)n_left);                                                                                              \
+    }
+#define LAUNCH_INSERT_LEAN(SH)                                                                                                                                      \
+    {                                                                                                                                                               \
+        if (sat) LAUNCH_INSERT_LEAN_K(SH, true)                                                                                                                     \
+        else LAUNCH_INSERT_LEAN_K(SH, false)                                                                                                                        \
+    }
+        if (lean && P.shift == 4) LAUNCH_INSERT_LEAN(4)
+        else if (lean && P.shift == 3) LAUNCH_INSERT_LEAN(3)
+        else if (lean && P.shift == 2) LAUNCH_INSERT_LEAN(2)
+        else if (lean) LAUNCH_INSERT_LEAN(1)
+        else if (!generic_only && P.nw == 3 && P.kb == 49 && P.shift == 4) LAUNCH_INSERT_FAST(3, 49, 4)        // k63 m21 b14
         else if (!generic_only && P.nw == 3 && P.kb == 49 && P.shift == 3) LAUNCH_INSERT_FAST(3, 49, 3)  // the same with 2^25..2^27 partitions:
         else if (!generic_only && P.nw == 3 && P.kb == 49 && P.shift == 2) LAUNCH_INSERT_FAST(3, 49, 2)  // jobs of 2..8 x 50 M reads per batch over
         else if (!generic_only && P.nw == 3 && P.kb == 49 && P.shift == 1) LAUNCH_INSERT_FAST(3, 49, 1)  // as many owners (brisk_hip_options.part_bits)
@@ -613,12 +661,23 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         else if (!generic_only && P.nw == 2 && P.kb == 17 && P.shift == 6) LAUNCH_INSERT_FAST(2, 17, 6)  // brisk_hip_part_bits_for_batch)
         else if (!generic_only && P.nw == 2 && P.kb == 20 && P.shift == 0) LAUNCH_INSERT_FAST(2, 20, 0)  // k31 m11 b11
         else LAUNCH_INSERT(0, 0, 0)
+#undef LAUNCH_INSERT_LEAN
+#undef LAUNCH_INSERT_LEAN_K
 #undef LAUNCH_INSERT_FAST
 #undef LAUNCH_INSERT
 #undef LAUNCH_INSERT_K
         if ((rc = launch_check(h, big ? "k_insert_big" : "k_insert"))) return rc;
-        if (h->trace) fprintf(stderr, "[brisk_hip] path: insert of %llu records (%s layout, histogram %s) into %u partitions: %s, %u partitions to k_insert_huge\n", (unsigned long long)n_rec,
-                              bl ? "binned" : "classic", have_hist ? "from the scan" : "counted here", n_touched, big ? "k_insert_big (in-place collapse for partitions of > 128 records)" : "k_insert", n_huge);
+        if (h->trace) {
+            std::string path = big ? "k_insert_big (in-place collapse for partitions of > 128 records)" : "k_insert";
+            if (lean) {  // (tracing only: the count is waited for)
+                u32 n_left = 0;
+                HIPCHK(h, hipMemcpyAsync(&n_left, h->d_small + 7, 4, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                path = "k_insert_first (fresh index): " + std::to_string(n_touched - n_huge - n_left) + " partitions lean, " + std::to_string(n_left) + " left over to k_insert";
+            }
+            fprintf(stderr, "[brisk_hip] path: insert of %llu records (%s layout, histogram %s) into %u partitions: %s, %u partitions to k_insert_huge\n", (unsigned long long)n_rec,
+                    bl ? "binned" : "classic", have_hist ? "from the scan" : "counted here", n_touched, path.c_str(), n_huge);
+        }
         if (n_huge) {
             if (sat) hipLaunchKernelGGL(k_insert_huge<true>, dim3(std::min<u32>(n_huge, 256u)), dim3(HG_THREADS), 0, h->stream, P, src, (const PartDesc*)h->desc.p,
                                         (const u32*)h->huge.p + 1, (const u32*)h->huge.p, h->ix);
@@ -1660,7 +1719,7 @@ int drain_profile(brisk_hip_index* h) {
 void free_all(brisk_hip_index* h) {
     hipStreamSynchronize(h->stream);  // nothing of ours may be in flight when the arena is unmapped
     auto fr = [](void* p) { if (p) hipFree(p); };
-    for (DevBuf* b : {&h->huge, &h->pend, &h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp, &h->enum_out,
+    for (DevBuf* b : {&h->huge, &h->left, &h->pend, &h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp, &h->enum_out,
                       &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->ext_iv, &h->ext_tmp, &h->ext_src})
         fr(b->p);
     fr(h->d_coef);
@@ -1866,12 +1925,14 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
             h->scan_v1 = v1 && v1[0] == '1';
         }
         {   // the persistent insert kernels: how many waves the device keeps resident, at most
-            const void* fns[] = {(const void*)k_insert<0, 0, 0>, (const void*)k_insert_big<0, 0, 0>, (const void*)k_insert_fast<3, 49, 4>, (const void*)k_insert_fast<2, 17, 4>,
+            const void* fns[] = {(const void*)k_insert<0, 0, 0>, (const void*)k_insert_big<0, 0, 0>, (const void*)k_insert_fast<3, 49, 4>, (const void*)k_insert_first<3, 49, 4>, (const void*)k_insert_fast<2, 17, 4>,
                                  (const void*)k_insert_fast<2, 20, 0>, (const void*)k_insert_big<3, 49, 4>, (const void*)k_insert_big<2, 17, 4>, (const void*)k_insert_big<2, 20, 0>};
             int most = 16;
             for (const void* fn : fns) {
                 int per_cu = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) == hipSuccess && per_cu > most) most = per_cu;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess) continue;
+                if (fn == (const void*)k_insert_first<3, 49, 4>) per_cu = std::min(per_cu, 4 * WI_WAVES_PER_EU_FIRST_MAX);  // (see resident() in insert_records_once)
+                if (per_cu > most) most = per_cu;
             }
             h->insert_waves = std::min<u32>((u32)most * (u32)prop.multiProcessorCount, INSERT_SLOTS);
         }
@@ -1970,6 +2031,7 @@ BRISK_API int brisk_hip_clear(brisk_hip_index* h) {
     h->arena_used_host = 0;
     h->nb_skmers = 0;
     h->dir_snapshot_valid = false;
+    h->fresh = true;
     h->n_pend = 0;  // records scanned and not yet inserted go with the index
     h->pend_hist_ok = true;
     return BRISK_HIP_OK;
@@ -2611,7 +2673,7 @@ BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t
     if (memory_bytes) {
         u64 m = h->arena_cap * (8ull * h->ix.key_words + 1) + h->n_parts * 16 + (h->n_buckets + 7) / 8 + (h->n_parts + 1) * 20;
         for (const DevBuf* b : {&h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp,
-                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->ext_iv, &h->ext_tmp, &h->ext_src})
+                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->ext_iv, &h->ext_tmp, &h->ext_src})
             m += b->bytes;
         *memory_bytes = m;
     }
@@ -2691,6 +2753,7 @@ BRISK_API int brisk_hip_reallocate(brisk_hip_index* from, brisk_hip_index* to) {
         if (n_rec != total) return fail(h, BRISK_HIP_EHIP, "reallocate: " + std::to_string(total) + " k-mers gave " + std::to_string(n_rec) + " records");
         hipLaunchKernelGGL(k_set_multiplicity, dim3(nblocks(n_rec, 256)), dim3(256), 0, h->stream, (u64*)h->staging.p, n_rec, h->P.stride, (const u32*)h->tags_a.p, d_cnt);
         if ((rc = launch_check(h, "k_set_multiplicity"))) return rc;
+        h->fresh = false;  // (records that carry counts: the general route)
         if ((rc = insert_records_impl(h, (const u64*)h->staging.p, n_rec, hist_ok))) return rc;
         p = q;
     }
@@ -2864,6 +2927,7 @@ BRISK_API int brisk_hip_merge(brisk_hip_index* dst, brisk_hip_index* src, uint64
         HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
         hipLaunchKernelGGL(k_dir_to_hist, dim3(nblocks(np, 256)), dim3(256), 0, h->stream, src->ix.dir, (u32)p, (u32)np, h->d_hist);
         if ((rc = launch_check(h, "k_dir_to_hist"))) return rc;
+        h->fresh = false;  // (records that carry counts: the general route)
         if ((rc = insert_records_impl(h, (const u64*)h->staging.p, total, true))) return rc;
         p = q;
     }
@@ -3166,6 +3230,7 @@ int save_impl(brisk_hip_index* h, int fd, uint64_t* entries_written) {
 int load_impl(brisk_hip_index* h, int fd, const brisk_hip_snapshot_info& s, bool room) {
     const u32 kw = h->ix.key_words;
     int rc;
+    h->fresh = false;
     // the whole arena at once, so that no block waits for a growth: exact for compact slices, an upper bound for slices with room
     const u64 arena_need = room ? s.n_entries + s.n_entries / 4 + 8 * s.n_partitions : s.n_entries;
     if (arena_need && (rc = ensure_arena(h, arena_need))) return rc;
@@ -3670,6 +3735,7 @@ BRISK_API int brisk_hip_upsert_kmers(brisk_hip_index* h, const uint64_t* kmer_lo
     std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
     if (int frc = enter(h)) return frc;
     int rc;
+    h->fresh = false;
     if (!h->arena_cap && (rc = ensure_arena(h, 1u << 16))) return rc;
     u64 *d_lo, *d_hi;
     uint8_t *d_idx, *d_new;

@@ -33,11 +33,11 @@
 // one atomic per phase and wave at the end.  Wall cycles of a wave, so they include what it waits for.
 #ifdef BRISK_PHASE_PROF
 __device__ unsigned long long g_phase[16];
-#define PHASE_DECL unsigned long long ph_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ph_last = __builtin_amdgcn_s_memtime(); u32 dbg_cnt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#define PHASE_DECL unsigned long long ph_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ph_last = __builtin_amdgcn_s_memtime(); u32 dbg_cnt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define PHASE(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph_acc[i] += t_ - ph_last; ph_last = t_; }  /* phase i ends here */
 __device__ unsigned long long g_cnt[16];
 #define PHASE_FLUSH { PHASE(10) if (threadIdx.x == 0) { _Pragma("unroll") for (int q_ = 0; q_ < 12; q_++) atomicAdd(&g_phase[q_], ph_acc[q_]); \
-                                                         _Pragma("unroll") for (int q_ = 0; q_ < 12; q_++) atomicAdd(&g_cnt[q_], (unsigned long long)dbg_cnt[q_]); } }
+                                                         _Pragma("unroll") for (int q_ = 0; q_ < 16; q_++) atomicAdd(&g_cnt[q_], (unsigned long long)dbg_cnt[q_]); } }
 #define CNT(i, v) dbg_cnt[i] += (v);
 #else
 #define PHASE_DECL
@@ -523,9 +523,13 @@ __device__ __forceinline__ bool fold_records(const FoldFrame& f, u32 nrec, u32 l
 // lanes and pays a v_readlane per use), and k-mers are cut out of 32-bit words (expand_and_dedupe_words).  NW == 0:
 // everything from P at run time.
 // SAT: the index's counts stop at 255 instead of wrapping (count8).
-template <u32 MAXI, u32 NW, u32 KB, u32 SHIFT, bool SAT>
-__device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc& src, const PartDesc* __restrict__ desc, u32 n_touched, const IndexDev& ix,
-                                            u32* __restrict__ work_counter) {
+// LISTED: the wave walks desc[list[0 .. *n_list)] instead of desc[0 .. n_touched): the partitions k_insert_first left over.  The
+// count is read from device memory, so the host need not wait for it.  A compile-time switch: the unlisted bodies are
+// instruction for instruction what they were.
+template <u32 MAXI, u32 NW, u32 KB, u32 SHIFT, bool SAT, bool LISTED = false>
+__device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc& src, const PartDesc* __restrict__ desc, u32 n_touched_all, const IndexDev& ix,
+                                            u32* __restrict__ work_counter, const u32* __restrict__ list = nullptr, const u32* __restrict__ n_list = nullptr) {
+    const u32 n_touched = LISTED ? min(*n_list, n_touched_all) : n_touched_all;
     u64* const rec = src.rec;  // the in-place collapse of the big-partition kernel (classic layout only)
     BriskParams P = PP;
     if (NW) {  // the fields the body reads, as constants
@@ -586,13 +590,13 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
         // A partition's descriptor comes by scalar loads (s_load_dwordx8: t and the array's address are wave-uniform, the array is
         // read-only).  Round 2 kept the batch's 64 descriptors in registers, one per lane, and broadcast one with eight v_readlane:
         // those were the eight registers the body spilled at 96 (10 spilled -> 3; 26.2 -> 25.9 ms per 50 M reads).
-        PartDesc d = desc[t0];
+        PartDesc d = desc[LISTED ? list[t0] : t0];
         RecRegs rr = load_part_recs(P, src, d.part, d.r_begin, d.r_begin, min(d.n_rec, (u32)WI_MAX_REC), lane);
 
         for (u32 t = t0; t < t_end; t++) {
             const u32 tn = t + 1;
             PartDesc dn{};
-            if (tn < t_end) dn = desc[tn];
+            if (tn < t_end) dn = desc[LISTED ? list[tn] : tn];
             // The next partition's records are requested when this partition is done, into rr.  Round 2 requested them at the top
             // of the current partition, into a second set of registers: the memory counter retires loads in issue order and the
             // compiler's wait in front of the first use of rr is vmcnt(0), so every partition began by sitting out the round trip
@@ -722,6 +726,12 @@ __device__ __forceinline__ void insert_body(const BriskParams& PP, const RecSrc&
                 CNT(9, raw_inst)
                 CNT(10, FOLD ? (u32)__popcll(__ballot(lane < nrec && my_n == 0 && raw_n != 0)) : 0u)
                 CNT(11, dbg_trips)
+                // (what k_insert_first would meet: a partition's instances after the fold, by slots of 64 per lane, and the
+                // partitions of more records than one chunk holds)
+                CNT(12, rc == d.r_begin && d.n_rec <= WI_MAX_REC && ninst > 64 && ninst <= 128 ? 1u : 0u)
+                CNT(13, rc == d.r_begin && d.n_rec <= WI_MAX_REC && ninst > 128 && ninst <= 192 ? 1u : 0u)
+                CNT(14, rc == d.r_begin && d.n_rec <= WI_MAX_REC && ninst > 192 ? 1u : 0u)
+                CNT(15, rc == d.r_begin && d.n_rec > WI_MAX_REC ? 1u : 0u)
                 // where this record's k-mers sit on the instance line: its own slots, or its head's from its idx0' on
                 const u32 m_first = FOLD ? (u32)__shfl(x - my_n, lead, 64) + lead_off : 0u;
                 // (a quarter full at most in instances, less in distinct keys: probe rounds are wave-wide -- every round costs all 64 lanes
@@ -1021,6 +1031,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVE
     static_assert(NW > 0, "compile-time record geometry");
     insert_body<WI_MAX_INST, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter);
 }
+// the same over a device-side list of descriptor indices (what k_insert_first left over; n_touched: the list's capacity)
+template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVES_PER_EU_FAST, 8))) k_insert_fast_listed(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
+                                                                                                               u32 n_touched, IndexDev ix, u32* __restrict__ work_counter,
+                                                                                                               const u32* __restrict__ list, const u32* __restrict__ n_list) {
+    insert_body<WI_MAX_INST, NW, KB, SHIFT, SAT, true>(P, src, desc, n_touched, ix, work_counter, list, n_list);
+}
 template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVES_PER_EU, 8))) k_insert(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
                                                u32 n_touched, IndexDev ix, u32* __restrict__ work_counter) {
@@ -1030,6 +1047,260 @@ template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) k_insert_big(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
                                                                                          u32 n_touched, IndexDev ix, u32* __restrict__ work_counter) {
     insert_body<2 * WI_MAX_INST, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter);
+}
+
+// ---- k_insert_first: the first fill of empty partitions (DESIGN.md section 4 finding 16).  The first batch into a fresh index
+// (every one-shot job, and the flagship job at every step) finds every partition empty and -- folded -- nearly every one within
+// one small chunk, yet insert_body keeps registers and LDS for four instance slots per lane, a stream over the existing entries,
+// MATCHED_BIT, the move to a larger slice and the chunk loop.  This body has none of them: NI_LEAN instance slots per lane,
+// one chunk, every slot a lane won is a new entry.  It is built from insert_body's pieces and yields, for a partition it takes,
+// exactly what insert_body yields: the same entries in the same order in a slice of the same capacity.  A partition it must not
+// take -- not empty, more than 64 records, more than 64 * NI_LEAN instances after the fold -- is left over: before anything
+// global is written for it, its descriptor index goes to a list that k_insert_fast then walks (one atomic per batch of WI_BATCH
+// partitions: the batch's left-over partitions are a 64-bit mask in scalar registers).
+#ifndef NI_LEAN
+#define NI_LEAN 2   // profiles/r13_insert_ninst.txt
+#endif
+#ifndef WI_WAVES_PER_EU_FIRST
+#define WI_WAVES_PER_EU_FIRST 6
+#endif
+#ifndef WI_WAVES_PER_EU_FIRST_MAX
+#define WI_WAVES_PER_EU_FIRST_MAX 6
+#endif
+template <u32 NIL, u32 NW>
+struct LeanLds {
+    static constexpr u32 MAXI = 64 * NIL, TABLE = 4 * MAXI;
+    static constexpr u32 REC_BYTES = (WI_MAX_REC * RecGeom<NW>::RS + 4) * 4;   // shifted record words, + 4: the last record's window
+    static constexpr u32 OFF_REC = 16 * MAXI;                                  // keys first (s_idiff over them)
+    static constexpr u32 REGION = REC_BYTES > 4 * TABLE ? REC_BYTES : 4 * TABLE;  // the probe table lies over the records
+    static constexpr u32 OFF_IREC = OFF_REC + REGION, OFF_IMULT = OFF_IREC + MAXI, BYTES = OFF_IMULT + MAXI;
+};
+__device__ __forceinline__ unsigned long long first_lane64(unsigned long long v) {
+    return ((unsigned long long)(u32)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)v);
+}
+template <u32 NIL, u32 NW, u32 KB, u32 SHIFT, bool SAT>
+__device__ __forceinline__ void insert_first_body(const BriskParams& P, const RecSrc& src, const PartDesc* __restrict__ desc, u32 n_touched, const IndexDev& ix,
+                                                  u32* __restrict__ work_counter, u32* __restrict__ left_list, u32* __restrict__ n_left) {
+    using L = LeanLds<NIL, NW>;
+    constexpr u32 MAXI = L::MAXI, TABLE = L::TABLE, RS = RecGeom<NW>::RS, INFO = RecGeom<NW>::INFO, KBITS = 2 * KB + 6;
+    constexpr u32 KW = KBITS + SHIFT <= 64 ? 1u : 2u;
+    static_assert(NIL == 2 || NIL == 3, "instance slots per lane");
+    static_assert(NW >= 3 && SHIFT < 5, "the folding k63 geometries: at most 16 buckets per partition");
+    static_assert(L::BYTES <= 13 * 512, "LDS per wave: 24 waves must fit a CU's 160 KiB");
+    static_assert(4 * MAXI <= 16 * MAXI, "the multiplicity steps lie over the keys");
+    __shared__ __attribute__((aligned(16))) unsigned char s_mem[L::BYTES];
+    u64* s_key = (u64*)s_mem;
+    u32* s_idiff = (u32*)s_mem;
+    u32* s_rw = (u32*)(s_mem + L::OFF_REC);
+    u32* s_tab = (u32*)(s_mem + L::OFF_REC);
+    uint8_t* s_irec = s_mem + L::OFF_IREC;
+    uint8_t* s_imult = s_mem + L::OFF_IMULT;
+
+    const u32 lane = threadIdx.x;
+    PHASE_DECL
+    // the wave's private arena chunk: wave-uniform, in scalar registers
+    unsigned long long acur = first_lane64(ix.slot_cur[blockIdx.x]), aend = first_lane64(ix.slot_end[blockIdx.x]), garbage = 0;
+    const u32 frame_end = P.suff_reduc + P.w + 1;
+
+    for (;;) {
+        u32 t0 = 0;
+        if (lane == 0) t0 = atomicAdd(work_counter, WI_BATCH);
+        t0 = (u32)__builtin_amdgcn_readfirstlane((int)t0);
+        if (t0 >= n_touched) break;
+        const u32 t_end = min(t0 + WI_BATCH, n_touched);
+        unsigned long long left_mask = 0;  // partitions t0 + i of this batch that are left to k_insert_fast (wave-uniform)
+        PartDesc d = desc[t0];
+        RecRegs rr = load_part_recs(P, src, d.part, d.r_begin, d.r_begin, min(d.n_rec, (u32)WI_MAX_REC), lane);
+
+        for (u32 t = t0; t < t_end; t++) {
+            const u32 tn = t + 1;
+            PartDesc dn{};
+            if (tn < t_end) dn = desc[tn];
+            // (the records of the next partition are requested at the end of this one, and must have landed on every path: insert_body)
+            asm volatile("" ::"v"(rr.w0), "v"(rr.w1), "v"(rr.w2), "v"(rr.w3), "v"(rr.w4));
+            do {
+                if (ix.huge_at && d.n_inst > ix.huge_at) break;  // k_insert_huge takes this one
+                CNT(0, 1)
+                if (d.n_exist | d.cap | (u32)(d.n_rec > WI_MAX_REC)) {
+                    left_mask |= 1ull << (t - t0);
+                    break;
+                }
+                PHASE(0)
+                const u32 part = d.part, nrec = d.n_rec;
+                const u64 my_hdr = NW == 3 ? rr.w3 : rr.w4;
+                const u32 raw_n = lane < nrec ? hdr_n(my_hdr) : 0;
+                const u32 my_mult = (my_hdr & HDR_HAS_MULT) ? (u32)(my_hdr >> 48) & 0xffu : 1u;
+                const u32 info_hi = (raw_n << 10) | (hdr_idx0(my_hdr) << 18) | ((hdr_bucket(my_hdr) & ((1u << SHIFT) - 1)) << 26);
+                const FoldFrame ff = fold_frame<NW, KB>(rr, my_hdr, raw_n, lane < nrec, frame_end, lane);
+                wave_sync();  // the previous partition has read its table
+                if (lane < nrec) store_rec_words<NW>(s_rw + lane * RS, rr, 0);
+                u32 lead = lane, lead_off = 0, dbg_trips = 0;
+                const bool dup = fold_records<NW>(ff, nrec, lane, &lead, &lead_off, &dbg_trips);
+                const u32 my_n = (lane < nrec && !dup) ? raw_n : 0;
+                const u32 x = wave_incl_scan(my_n, lane);
+                const u32 ninst = (u32)__builtin_amdgcn_readlane((int)x, 63);
+                if (ninst > MAXI) {  // (nothing but LDS has been written)
+                    left_mask |= 1ull << (t - t0);
+                    break;
+                }
+                PHASE(1)
+                CNT(1, 1)
+                const u32 m_first = (u32)__shfl(x - my_n, lead, 64) + lead_off;
+                u32 tsize = 128;
+                while (tsize < 4 * ninst && tsize < TABLE) tsize <<= 1;
+                {
+                    // instance -> record and every instance's multiplicity, as in insert_body; a lane owns NIL consecutive instances
+                    if (NIL == 2) ((uint16_t*)s_irec)[lane] = 0;
+                    else {
+#pragma unroll
+                        for (u32 q = 0; q < NIL; q++) s_irec[q * 64 + lane] = 0;
+                    }
+#pragma unroll
+                    for (u32 q = 0; q < NIL; q++) s_idiff[lane * NIL + q] = 0;
+                    wave_sync();
+                    if (my_n) s_irec[x - my_n] = (uint8_t)(lane + 1);
+                    if (lane < nrec) {
+                        atomicAdd(&s_idiff[m_first], my_mult);
+                        if (m_first + raw_n < ninst) atomicAdd(&s_idiff[m_first + raw_n], 0u - my_mult);
+                    }
+                    wave_sync();
+                    u32 mk[NIL], mv[NIL], run = 0, tot = 0;
+                    if (NIL == 2) {
+                        const u32 w = ((const uint16_t*)s_irec)[lane];
+                        mk[0] = w & 0xff;
+                        mk[1] = w >> 8;
+                    } else {
+#pragma unroll
+                        for (u32 q = 0; q < NIL; q++) mk[q] = s_irec[lane * NIL + q];
+                    }
+#pragma unroll
+                    for (u32 q = 0; q < NIL; q++) {
+                        run = op_max_u32(run, mk[q]);
+                        tot += s_idiff[lane * NIL + q];
+                        mv[q] = tot;
+                    }
+                    const u32 before = wave_incl_scan(tot, lane) - tot;
+                    u32 carry = wave_prev_lane(wave_incl_max_scan(run));  // the last mark before this lane's instances
+#pragma unroll
+                    for (u32 q = 0; q < NIL; q++) {
+                        carry = op_max_u32(carry, mk[q]);
+                        mk[q] = (carry - 1) & 0xff;  // marks are lane + 1; instances past the last record (none are read) may hold 0 - 1
+                        mv[q] = count8<SAT>(mv[q] + before) & 0xff;
+                    }
+                    if (NIL == 2) {
+                        ((uint16_t*)s_irec)[lane] = (uint16_t)(mk[0] | (mk[1] << 8));
+                        ((uint16_t*)s_imult)[lane] = (uint16_t)(mv[0] | (mv[1] << 8));
+                    } else {
+#pragma unroll
+                        for (u32 q = 0; q < NIL; q++) {
+                            s_irec[lane * NIL + q] = (uint8_t)mk[q];
+                            s_imult[lane * NIL + q] = (uint8_t)mv[q];
+                        }
+                    }
+                    // the records' info words: [first instance | n | idx0' | routing id low bits]
+                    if (lane < nrec) s_rw[lane * RS + INFO] = (x - my_n) | info_hi;
+                }
+                wave_sync();
+                PHASE(2)
+                CNT(3, (ninst + 63) / 64)
+                CNT(4, ninst)
+                CNT(5, nrec)
+                CNT(11, dbg_trips)
+                u32 dbg_r = 0;
+                LaneInst<NIL> li;
+                li.won = 0;
+                if (ninst <= 64) expand_and_dedupe_words<1, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
+                else if (NIL == 2 || ninst <= 128) expand_and_dedupe_words<2, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
+                else expand_and_dedupe_words<NIL, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
+                wave_sync();
+                CNT(8, dbg_r)
+                PHASE(3)
+                // ---- the new entries: every slot a lane created, ranked with one ballot per instance slot
+                u32 n_new = 0, new_rank[NIL], new_word[NIL];
+#pragma unroll
+                for (u32 it = 0; it < NIL; it++) {
+                    new_rank[it] = 0;
+                    new_word[it] = 0;
+                    if (it * 64 < ninst) {  // wave-uniform
+                        const bool made = (li.won >> it) & 1;
+                        if (made) new_word[it] = s_tab[li.hh[it]];
+                        const unsigned long long bal = __ballot(made);
+                        new_rank[it] = n_new + (u32)__popcll(bal & lanes_below(lane));
+                        n_new += (u32)__popcll(bal);
+                    }
+                }
+                wave_sync();
+#ifndef INSERT_NO_EARLY_WAIT
+                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the prefetched records, before this partition's stores (insert_body)
+#endif
+                PHASE(6)
+                CNT(7, n_new)
+                unsigned long long off = d.off;
+                u32 cap = 0;
+                if (n_new) {  // the slice insert_body takes for a fresh partition of one chunk, from the private chunk
+                    const unsigned long long want = grow_cap(n_new);  // <= grow_cap(64 * NI_LEAN): far below ARENA_CHUNK / 8
+                    if (acur + want > aend) {
+                        garbage += aend - acur;
+                        unsigned long long got = 0;
+                        if (lane == 0) got = atomicAdd(ix.cursor, (unsigned long long)ARENA_CHUNK);
+                        acur = first_lane64(got);
+                        aend = acur + ARENA_CHUNK;
+                    }
+                    if (acur + want > ix.arena_cap) {  // must not happen (the host reserves the bound): drop, flag
+                        if (lane == 0) atomicOr(ix.err, 2u);
+                        n_new = 0;
+                    } else {
+                        off = acur;
+                        acur += want;
+                        cap = (u32)want;
+                    }
+                }
+                PHASE(7)
+                u32 bm0 = 0;
+#pragma unroll
+                for (u32 it = 0; it < NIL; it++) {
+                    if (it * 64 < ninst && ((li.won >> it) & 1) && n_new) {
+                        const unsigned long long at = off + new_rank[it];
+                        store_key<KW>(ix, at, li.klo[it], li.khi[it]);
+                        ix.counts[at] = (uint8_t)count8<SAT>(new_word[it] >> WI_CNT_SHIFT);
+                        const u32 bl = SHIFT ? ((u32)shr128(mk128(li.klo[it], li.khi[it]), KBITS).lo & ((1u << SHIFT) - 1)) : 0;
+                        bm0 |= 1u << bl;
+                    }
+                }
+                PHASE(8)
+                bm0 = wave_or_all(bm0);
+                if (lane == 0) {
+                    ix.dir[part] = DirEnt{off, n_new, cap};
+                    // bucket occupancy bits (insert_body's epilogue, fewer than 32 buckets per partition)
+                    const u64 first = ((u64)part << SHIFT) >> P.ext_bits;
+                    const u32 bits = bm0 << (first & 31);
+                    if (bits && (!ix.bits_check || (ix.bucket_bits[first >> 5] & bits) != bits)) atomicOr(&ix.bucket_bits[first >> 5], bits);
+                }
+            } while (0);
+            d = dn;
+            if (tn < t_end) rr = load_part_recs(P, src, d.part, d.r_begin, d.r_begin, min(d.n_rec, (u32)WI_MAX_REC), lane);
+            PHASE(9)
+        }
+        if (left_mask) {  // wave-uniform
+            const u32 n = (u32)__popcll(left_mask);
+            u32 at = 0;
+            if (lane == 0) at = atomicAdd(n_left, n);
+            at = (u32)__builtin_amdgcn_readfirstlane((int)at);
+            if ((left_mask >> lane) & 1) left_list[at + (u32)__popcll(left_mask & lanes_below(lane))] = t0 + lane;
+        }
+    }
+    PHASE_FLUSH
+    if (lane == 0) {
+        ix.slot_cur[blockIdx.x] = acur;
+        ix.slot_end[blockIdx.x] = aend;
+        if (garbage) atomicAdd(&ix.stats[3], garbage);
+    }
+}
+template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVES_PER_EU_FIRST, WI_WAVES_PER_EU_FIRST_MAX))) k_insert_first(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
+                                                                                                          u32 n_touched, IndexDev ix, u32* __restrict__ work_counter,
+                                                                                                          u32* __restrict__ left_list, u32* __restrict__ n_left) {
+    insert_first_body<NI_LEAN, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter, left_list, n_left);
 }
 
 // bucket occupancy for partitions wider than 64 buckets (small part_bits): one pass over all entries

@@ -47,7 +47,8 @@ print("k_insert ms:", {n: round(v["ms"], 3) for n, v in prof.items() if v["launc
 for i, n in enumerate(names):
     print(f"{n:32s} {buf[i]:16d} {100.0 * buf[i] / tot:6.2f} %")
 cn = ["partitions", "chunks", "record-dedupe attempts", "expand its (x64 lanes)", "instances", "records", "append passes", "new entries", "CAS rounds x its",
-      "instances before the fold", "records folded", "fold rounds (heads)"]
+      "instances before the fold", "records folded", "fold rounds (heads)", "65..128 instances folded", "129..192 instances folded",
+      "> 192 instances folded", "> 64 records"]  # (the last four: partitions of at most 64 records by their first chunk; BRISK_INSERT_LEAN=0: all partitions)
 for i, n in enumerate(cn):
     print(f"{n:28s} {buf[16 + i]:14d}  per partition {buf[16 + i] / max(buf[16], 1):8.3f}")
 L.brisk_hip_debug_scan_counts(sbuf, 0)
