@@ -59,6 +59,32 @@ struct PendingEvent {
     hipEvent_t a, b;
 };
 
+// The small counters kernels hand to the host: one Counters on the device (h->d_ctr), one in pinned memory (h->h_ctr, with the host-only
+// values behind it).  A counter has one meaning and its own storage; a sub-struct is a group that one memset zeroes or one copy fetches
+// (zero_ctr, fetch_ctr, fetch_ctr_sync take the group's address on the device), as large as what its kernel writes:
+struct Counters {
+    struct Scan { unsigned long long n_rec; u32 overflow, pad; } scan;          // ScanOut::n_rec (records wanted, also beyond cap), ::overflow
+    struct Touched { u32 n_touched, pad; unsigned long long need; } touched;    // k_touched: partitions with records; k_need: arena slots they may take
+    struct Kmers { unsigned long long bound, n_long; } kmers;                   // k_count_kmers: k-mers; sequences beyond SCAN_LONG | offsets do not ascend << 63
+    struct Work { u32 wc[2], n_left, pad; } work;  // work counters of the persistent insert / query waves; k_insert_first: partitions left to k_insert_fast_listed
+    struct Plan { u32 n_long, n_vr; } plan;        // k_plan_chunks: long sequences, and the chunks they are cut into
+    u32 n_rerun, pad;                              // k_chunk_commit: chunks to re-scan this round
+    unsigned long long kept;                       // k_filter_records / k_query_filter / k_pos_filter: records that stand
+    unsigned long long n_ovf;                      // k_sum_regions: records beyond their bins
+    unsigned long long slice_sum;                  // k_sum_slices: records the histogram slices count
+    u32 upsert_done, pad2;                         // k_upsert: k-mers of the vector that are in
+    struct Result { unsigned long long w[3]; } result;  // k_prune, k_join: [0] entries removed; k_checksum: entries, sum of counts, digest
+};
+static_assert(sizeof(Counters::Scan) == sizeof(unsigned long long) + 2 * sizeof(u32) && sizeof(Counters::Touched) == 2 * sizeof(u32) + sizeof(unsigned long long), "ScanOut; k_touched, k_need");
+static_assert(sizeof(Counters::Kmers) == 2 * sizeof(unsigned long long) && sizeof(Counters::Result) == 3 * sizeof(unsigned long long), "k_count_kmers: out[0..1]; k_checksum: out[0..2]");
+static_assert(sizeof(Counters::Work) == 4 * sizeof(u32) && sizeof(Counters::Plan) == 2 * sizeof(u32), "32-bit counters throughout");
+struct PinnedCounters : Counters {  // host only; pinned because copies land in them or leave from them
+    u32 n_huge;                     // number of huge partitions, from h->huge
+    unsigned long long arena_used;  // copy of ix.cursor (on load: the cursor to upload)
+    unsigned long long n_rec_new;   // the record count compact_chunks uploads to scan.n_rec
+    unsigned long long prof[3];     // k_profile_count_long's counters, from prof_plan
+};
+
 }  // namespace
 
 struct brisk_hip_index {
@@ -119,8 +145,8 @@ struct brisk_hip_index {
     u32* d_touched = nullptr;              // n_parts
     u32* d_block_sums = nullptr;
     u32 n_scan_blocks = 0;
-    unsigned long long* d_small = nullptr;  // [0] n_rec [1] overflow(u32) [2] n_touched(u32) [3] need [4] kmers bound
-    unsigned long long* h_small = nullptr;  // pinned mirror
+    Counters* d_ctr = nullptr;              // the kernels' counters (struct Counters)
+    PinnedCounters* h_ctr = nullptr;        // where the host reads them: pinned, filled group by group (fetch_ctr)
     char* h_pin = nullptr;                  // pinned staging of the per-call API (one vector's k-mers in, ids out: one copy each way)
     u64 nb_skmers = 0;
     std::vector<u32> h_dir_cnt;  // enumeration snapshot
@@ -207,6 +233,13 @@ int launch_check(brisk_hip_index* h, const char* what) {
     }
     return BRISK_HIP_OK;
 }
+
+// a counter group of h->d_ctr (its address on the device): zero it on the stream; copy it to its place in h->h_ctr; copy and wait
+template <class G> hipError_t zero_ctr(brisk_hip_index* h, G* d_group) { return hipMemsetAsync(d_group, 0, sizeof(G), h->stream); }
+template <class G> hipError_t fetch_ctr(brisk_hip_index* h, G* d_group) {
+    return hipMemcpyAsync((char*)h->h_ctr + ((char*)d_group - (char*)h->d_ctr), d_group, sizeof(G), hipMemcpyDeviceToHost, h->stream);
+}
+template <class G> hipError_t fetch_ctr_sync(brisk_hip_index* h, G* d_group) { const hipError_t e = fetch_ctr(h, d_group); return e != hipSuccess ? e : hipStreamSynchronize(h->stream); }
 
 int vm_reserve(brisk_hip_index* h, VmBuf& b, size_t bytes) {
     hipMemAllocationProp prop{};
@@ -465,6 +498,12 @@ int list_touched(brisk_hip_index* h, u32* d_n) {
     hipLaunchKernelGGL(k_touched, dim3(nblocks(r.len, 1024 * TOUCHED_ITEMS)), dim3(1024), 0, h->stream, h->d_hist + r.lo, r.len, (u32)r.lo, h->d_touched, d_n);
     return launch_check(h, "k_touched");
 }
+// d_hist <- the per-partition histogram of the n records at d_rec
+int rebuild_hist(brisk_hip_index* h, const u64* d_rec, u64 n) {
+    HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
+    hipLaunchKernelGGL(k_part_hist, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->P, d_rec, n, h->d_hist);
+    return launch_check(h, "k_part_hist");
+}
 
 // records (unordered, all owned by this index) -> index.  If have_hist, d_hist
 // already holds this batch's per-partition histogram (the scan filled it).
@@ -520,10 +559,10 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (in_range != n_rec) return fail(h, BRISK_HIP_EINVAL, "insert_records: " + std::to_string(n_rec - in_range) + " records belong to other owners (route_records first)");
     }
-    HIPCHK(h, hipMemsetAsync(h->d_small + 2, 0, 16, h->stream));
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->touched));
     {
         ProfScope ps(h, S_TOUCHED);
-        if ((rc = list_touched(h, (u32*)(h->d_small + 2)))) return rc;
+        if ((rc = list_touched(h, &h->d_ctr->touched.n_touched))) return rc;
     }
     if (n_move) {
         if ((rc = ensure(h, h->parted, n_move * P.stride * 8))) return rc;
@@ -533,9 +572,8 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
                            (const u32*)nullptr, (u32*)nullptr, h->ix.err, bl ? bl->ovf_cnt : (const u32*)nullptr, bl ? bl->ovf_region_cap : 0u);
         if ((rc = launch_check(h, "k_scatter"))) return rc;
     }
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 2, h->d_small + 2, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const u32 n_touched = (u32)h->h_small[2];
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->touched.n_touched));
+    const u32 n_touched = h->h_ctr->touched.n_touched;
     if (n_touched == 0) return BRISK_HIP_OK;
     // partitions of more k-mer instances than this go to k_insert_huge, a workgroup each (0: none; entry-id indexes keep ids per entry,
     // which that kernel does not)
@@ -549,25 +587,25 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
             HIPCHK(h, hipMemsetAsync(h->huge.p, 0, 4, h->stream));
         }
         hipLaunchKernelGGL(k_need, dim3(std::min<u32>(nblocks(n_touched, 256), 2048)), dim3(256), 0, h->stream, h->d_hist, (bl && !n_move) ? (const u32*)nullptr : h->d_off,
-                           h->d_touched, n_touched, h->ix.dir, (PartDesc*)h->desc.p, h->d_small + 3, bl ? bl->bin_cap : 0u, huge_at, huge_at ? (u32*)h->huge.p : (u32*)nullptr,
+                           h->d_touched, n_touched, h->ix.dir, (PartDesc*)h->desc.p, &h->d_ctr->touched.need, bl ? bl->bin_cap : 0u, huge_at, huge_at ? (u32*)h->huge.p : (u32*)nullptr,
                            (u32)HUGE_LIST_CAP);
         if (int lrc = launch_check(h, "k_need")) return lrc;
     }
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 3, h->d_small + 3, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 5, h->ix.cursor, 8, hipMemcpyDeviceToHost, h->stream));
-    h->h_small[4] = 0;
-    if (huge_at) HIPCHK(h, hipMemcpyAsync(h->h_small + 4, h->huge.p, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, fetch_ctr(h, &h->d_ctr->touched.need));
+    HIPCHK(h, hipMemcpyAsync(&h->h_ctr->arena_used, h->ix.cursor, 8, hipMemcpyDeviceToHost, h->stream));
+    h->h_ctr->n_huge = 0;
+    if (huge_at) HIPCHK(h, hipMemcpyAsync(&h->h_ctr->n_huge, h->huge.p, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->arena_used_host = h->h_small[5];
+    h->arena_used_host = h->h_ctr->arena_used;
     // (more huge partitions than the list holds: none is diverted, the wave kernels take them all)
-    const u32 n_huge = (u32)h->h_small[4] <= HUGE_LIST_CAP ? (u32)h->h_small[4] : 0u;
+    const u32 n_huge = h->h_ctr->n_huge <= HUGE_LIST_CAP ? h->h_ctr->n_huge : 0u;
     h->ix.huge_at = n_huge ? huge_at : 0u;
     // worst case: every slice the batch may need, the tail a private chunk strands at each refill (< 1/8 of it), and
     // one partly used chunk per persistent wave
-    if ((rc = ensure_arena(h, h->h_small[3] + h->h_small[3] / 7 + (u64)h->insert_waves * ARENA_CHUNK))) return rc;
+    if ((rc = ensure_arena(h, h->h_ctr->touched.need + h->h_ctr->touched.need / 7 + (u64)h->insert_waves * ARENA_CHUNK))) return rc;
     {
         ProfScope ps(h, S_INSERT);
-        HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 16, h->stream));  // [6] the two work counters, [7] the left-over count
+        HIPCHK(h, zero_ctr(h, &h->d_ctr->work));
         // partitions of many records (few distinct minimizers: m <= 11) take the 512-instance kernel: half as many chunks, and
         // with them half as many passes over a partition's entries, outweigh its 2 waves per SIMD (k31/m11/b11: 48 -> 36 ms)
         const u32 batches = (n_touched + WI_BATCH - 1) / WI_BATCH;
@@ -616,7 +654,7 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
     {                                                                                                                                                               \
         const dim3 grid(std::min<u32>(batches, resident((const void*)KERNEL<NW, KB, SH, SAT>)));                                                                  \
         hipLaunchKernelGGL((KERNEL<NW, KB, SH, SAT>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix,                         \
-                           (u32*)(h->d_small + 6));                                                                                                                 \
+                           h->d_ctr->work.wc);                                                                                                                      \
     }
 #define LAUNCH_INSERT(NW, KB, SH)                                                                                                                                   \
     {                                                                                                                                                               \
@@ -633,8 +671,8 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
     }
 #define LAUNCH_INSERT_LEAN_K(SH, SAT)                                                                                                                               \
     {                                                                                                                                                               \
-        u32* const wc = (u32*)(h->d_small + 6);                                                                                                                     \
-        u32* const n_left = (u32*)(h->d_small + 7);                                                                                                                 \
+        u32* const wc = h->d_ctr->work.wc;                                                                                                                          \
+        u32* const n_left = &h->d_ctr->work.n_left;                                                                                                                 \
         const dim3 grid(std::min<u32>(batches, resident((const void*)k_insert_first<3, 49, SH, SAT>, 4 * WI_WAVES_PER_EU_FIRST_MAX)));                                                            \
         hipLaunchKernelGGL((k_insert_first<3, 49, SH, SAT>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix, wc,                \
                            (u32*)h->left.p, n_left);                                                                                                                \
@@ -670,9 +708,8 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         if (h->trace) {
             std::string path = big ? "k_insert_big (in-place collapse for partitions of > 128 records)" : "k_insert";
             if (lean) {  // (tracing only: the count is waited for)
-                u32 n_left = 0;
-                HIPCHK(h, hipMemcpyAsync(&n_left, h->d_small + 7, 4, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
+                HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->work.n_left));
+                const u32 n_left = h->h_ctr->work.n_left;
                 path = "k_insert_first (fresh index): " + std::to_string(n_touched - n_huge - n_left) + " partitions lean, " + std::to_string(n_left) + " left over to k_insert";
             }
             fprintf(stderr, "[brisk_hip] path: insert of %llu records (%s layout, histogram %s) into %u partitions: %s, %u partitions to k_insert_huge\n", (unsigned long long)n_rec,
@@ -691,7 +728,6 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
     return BRISK_HIP_OK;
 }
 
-// scan reads -> records in d_rec (cap records).  n_rec_out on host after a sync.
 // one scan launch over n_items reads (or virtual reads when cc.vreads is set); counters are NOT reset here
 // pos: per-position mode (out.ret receives the slot anchors, out.slot_base is set; always k_scan2)
 int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_items, const ScanOut& out, bool query_mode, bool plain,
@@ -734,216 +770,203 @@ int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
     return launch_check(h, "k_scan");
 }
 
-// Scan a batch into d_rec.  Long sequences (insert mode only) are scanned as chunks, checked at the
-// seams and, if a seam does not match, re-scanned whole; *hist_valid tells whether d_hist still
-// describes exactly the records in d_rec.
-// Per-position mode (d_anchor set, query_mode false; brisk_hip_get_kmers): the insert's records, d_anchor[i] the slot anchor of record i
-// (pos_anchor) from d_slot_base (k_slot_apply), d_tags[i] meaningless on return (the caller numbers the records).
-int scan_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u64* d_rec, u64 cap, bool with_hist,
-              bool query_mode, u32* d_tags, u64* n_rec_out, u64* d_ret = nullptr, u64 kmer_bound = 0, bool* hist_valid = nullptr, bool keep_hist = false,
-              u64* d_anchor = nullptr, const u64* d_slot_base = nullptr) {
-    const bool pos = d_anchor != nullptr;
-    if (hist_valid) *hist_valid = with_hist;
-    if (with_hist) {
-        h->scan_hist_valid = false;
-        if (!keep_hist) HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));  // (keep_hist: add to the pending records' counts)
-    }
-    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 16, h->stream));
-    ScanOut out{d_rec, cap, h->d_small, with_hist ? h->d_hist : nullptr, (u32*)(h->d_small + 1), d_tags, pos ? d_anchor : d_ret, nullptr, 0u, nullptr, 0u, nullptr};
-    const bool plain = !pos && (h->scan_v1 || d_ret);
-    int rc;
-    u32 n_vr = 0;
-    // long sequences are chunked in insert mode (no tags) and in query mode (read tags); not in sequence mode (plain)
-    const bool may_chunk = !plain && kmer_bound > SCAN_LONG && (pos || (query_mode ? d_tags != nullptr : !d_tags));
-    u64* d_cbase = nullptr;  // per-position mode: the slot base of every chunk's sequence (chunk records carry the chunk as their tag)
-    VRead *d_vr = nullptr, *d_rerun = nullptr;
-    ChunkState *d_spec = nullptr, *d_truth = nullptr;
-    u32 *d_status = nullptr, *d_cursor = nullptr, *d_stop = nullptr;
+// What one scan is asked for.  Sequence mode: whole vectors through the plain kernel, never chunked (brisk_hip_scan_sequence);
+// Position mode: the insert's records with their slot anchors (brisk_hip_get_kmers).  The mode says what travels with the records.
+enum class ScanMode { Insert, Query, Sequence, Position };
+struct ScanReq {
+    ScanMode mode;
+    const u32* d_packed; const u64* d_starts; u64 n_reads;  // the batch
+    u64* d_rec; u64 cap;                                     // where the records go, and how many fit
+    u64 kmer_bound = 0;  // count_kmers' bound; sequences of more than SCAN_LONG k-mers are scanned in chunks (0: none are)
+    bool with_hist = false, keep_hist = false;  // d_hist <- the records' per-partition histogram; keep: added to what it holds (the pending records' counts)
+    u32* d_tags = nullptr;  // Query: the read of record i; Sequence: the position of its first k-mer; Position: scratch (the caller numbers the records)
+    u64* d_side = nullptr;  // Sequence: the minimizer value of record i; Position: its slot anchor (pos_anchor) from d_slot_base (k_slot_apply)
+    const u64* d_slot_base = nullptr;
+};
+struct ScanRes {
+    u64 n_rec = 0;            // records the batch has (more than cap: BRISK_HIP_ECAPACITY is returned)
+    bool hist_valid = false;  // d_hist describes exactly the records in d_rec (false after re-scanned or cut chunks: rebuild_hist)
+};
+
+// Long sequences as chunks (virtual reads): the plan of one scan, its arrays carved out of chunk_buf.
+struct ChunkPlan {
+    u32 chunk = 0, n_vr = 0;  // steps per chunk; chunks (0: the batch has no long sequence)
     u64 cap_vr = 0;
+    VRead *vr = nullptr, *rerun = nullptr;
+    ChunkState *spec = nullptr, *truth = nullptr;
+    u32 *status = nullptr, *cursor = nullptr, *stop = nullptr;
+    u64* cbase = nullptr;  // per-position mode: the slot base of every chunk's sequence (chunk records carry the chunk as their tag)
+    // what the chunked launches left in d_rec: short reads' records in [0, n1), the speculative chunks' in [n1, n2), seeded re-scans' behind
+    u64 n1 = 0, n2 = 0, total_rerun = 0;
+    u32* ctags = nullptr;  // chunk index per record of the chunked launches (query mode: in the caller's tag array, read indices later)
+    u64* qret = nullptr;   // query mode: where a record's vector starts | its minimizer is 0 << 63
+};
+
+int plan_chunks(brisk_hip_index* h, const ScanReq& q, ChunkPlan* cp) {
     // chunk length: long enough to amortise the warm-up, short enough to give the device lanes to fill
-    u32 chunk = 4096;
-    while (chunk > 1024 && kmer_bound / chunk < (1u << 18)) chunk >>= 1;
-    if (may_chunk) {
-        cap_vr = kmer_bound / chunk + kmer_bound / SCAN_LONG + 2;
-        const u64 cap_long = kmer_bound / SCAN_LONG + 1;
-        const size_t bytes = 2 * cap_vr * sizeof(VRead) + (2 * cap_vr + 1) * sizeof(ChunkState) + 3 * cap_vr * 4 + cap_long * sizeof(LongRead) + (pos ? cap_vr * 8 + 8 : 0);
-        if ((rc = ensure(h, h->chunk_buf, bytes))) return rc;
-        d_vr = (VRead*)h->chunk_buf.p;
-        d_rerun = d_vr + cap_vr;
-        d_spec = (ChunkState*)(d_rerun + cap_vr);
-        d_truth = d_spec + cap_vr;
-        d_status = (u32*)(d_truth + cap_vr + 1);
-        d_cursor = d_status + cap_vr;
-        d_stop = d_cursor + cap_vr;
-        LongRead* d_long = (LongRead*)(d_stop + cap_vr + (cap_vr & 1));
-        if (pos) d_cbase = (u64*)(d_long + cap_long);
-        HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 16, h->stream));
-        hipLaunchKernelGGL(k_plan_chunks, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_starts, n_reads, h->P.k, chunk, (u32)cap_vr,
-                           (u32*)(h->d_small + 7), d_long, (u32*)(h->d_small + 6));
-        if (int lrc = launch_check(h, "k_plan_chunks")) return lrc;
-        HIPCHK(h, hipMemcpyAsync(h->h_small + 6, h->d_small + 6, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        const u32 n_long = (u32)h->h_small[6];
-        if (n_long) {
-            hipLaunchKernelGGL(k_fill_chunks, dim3(std::min<u32>(n_long, 65535u)), dim3(256), 0, h->stream, d_starts, (u32)h->P.k, (u32)h->P.w, chunk, d_long, n_long, d_vr);
-            if (int lrc = launch_check(h, "k_fill_chunks")) return lrc;
-        }
-        n_vr = (u32)h->h_small[7];
-        if (n_vr > cap_vr) return fail(h, BRISK_HIP_EHIP, "chunk plan exceeds its bound");
+    cp->chunk = 4096;
+    while (cp->chunk > 1024 && q.kmer_bound / cp->chunk < (1u << 18)) cp->chunk >>= 1;
+    const bool pos = q.mode == ScanMode::Position;
+    const u64 cap_vr = cp->cap_vr = q.kmer_bound / cp->chunk + q.kmer_bound / SCAN_LONG + 2;
+    const u64 cap_long = q.kmer_bound / SCAN_LONG + 1;
+    const size_t bytes = 2 * cap_vr * sizeof(VRead) + (2 * cap_vr + 1) * sizeof(ChunkState) + 3 * cap_vr * 4 + cap_long * sizeof(LongRead) + (pos ? cap_vr * 8 + 8 : 0);
+    if (int rc = ensure(h, h->chunk_buf, bytes)) return rc;
+    cp->vr = (VRead*)h->chunk_buf.p;
+    cp->rerun = cp->vr + cap_vr;
+    cp->spec = (ChunkState*)(cp->rerun + cap_vr);
+    cp->truth = cp->spec + cap_vr;
+    cp->status = (u32*)(cp->truth + cap_vr + 1);
+    cp->cursor = cp->status + cap_vr;
+    cp->stop = cp->cursor + cap_vr;
+    LongRead* d_long = (LongRead*)(cp->stop + cap_vr + (cap_vr & 1));
+    if (pos) cp->cbase = (u64*)(d_long + cap_long);
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->plan));
+    hipLaunchKernelGGL(k_plan_chunks, dim3(nblocks(q.n_reads, 256)), dim3(256), 0, h->stream, q.d_starts, q.n_reads, h->P.k, cp->chunk, (u32)cap_vr, &h->d_ctr->plan.n_vr,
+                       d_long, &h->d_ctr->plan.n_long);
+    if (int lrc = launch_check(h, "k_plan_chunks")) return lrc;
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->plan));
+    const u32 n_long = h->h_ctr->plan.n_long;
+    if (n_long) {
+        hipLaunchKernelGGL(k_fill_chunks, dim3(std::min<u32>(n_long, 65535u)), dim3(256), 0, h->stream, q.d_starts, (u32)h->P.k, (u32)h->P.w, cp->chunk, d_long, n_long, cp->vr);
+        if (int lrc = launch_check(h, "k_fill_chunks")) return lrc;
     }
-    ChunkCtl cc{nullptr, nullptr, nullptr, n_vr ? SCAN_LONG : 0u, d_slot_base};
-    if ((rc = launch_scan(h, d_packed, d_starts, n_reads, out, query_mode, plain, cc, pos))) return rc;
-    if (n_vr) {
-        // records of the short reads are in [0, n1); the chunked launch appends after them and tags its records with
-        // their chunk; seeded re-scans append after those
-        HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        const u64 n1 = std::min<u64>(h->h_small[0], cap);
-        u32* d_ctags = d_tags;  // chunk index per record of the chunked launches (query mode: in the caller's tag array, read indices later)
-        u64* d_qret = nullptr;  // query mode: where a record's vector starts | its minimizer is 0 << 63
-        if (pos) {
-            hipLaunchKernelGGL(k_chunk_slot_base, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, d_vr, n_vr, d_slot_base, d_cbase);
-            if (int lrc = launch_check(h, "k_chunk_slot_base")) return lrc;
-        } else if (!query_mode) {
-            if ((rc = ensure(h, h->tags_a, cap * 4))) return rc;
-            d_ctags = (u32*)h->tags_a.p;
-        } else {
-            if ((rc = ensure(h, h->seq_buf, cap * 8 + cap_vr * 8))) return rc;
-            d_qret = (u64*)h->seq_buf.p;
-        }
-        HIPCHK(h, hipMemsetAsync(d_spec, 0, (2 * cap_vr + 1) * sizeof(ChunkState) + 2 * cap_vr * 4, h->stream));  // states, status, cursor
-        HIPCHK(h, hipMemsetAsync(d_stop, 0xff, cap_vr * 4, h->stream));
-        ScanOut out2 = out;
-        out2.tag = d_ctags;
-        out2.ret = pos ? d_anchor : d_qret;
-        ChunkCtl c2{d_vr, d_spec, d_truth, 0u, d_cbase};
-        if ((rc = launch_scan(h, d_packed, d_starts, n_vr, out2, false, false, c2, pos))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        const u64 n2 = std::min<u64>(h->h_small[0], cap);
-        ScanOut out3 = out2;
-        out3.hist = nullptr;  // once a chunk is re-scanned the histogram is rebuilt from the final records
-        u64 total_rerun = 0;
-        u32 rounds = 0;
-        for (;; rounds++) {  // one round per mismatch along a sequence; no mismatch: one round
-            HIPCHK(h, hipMemsetAsync(h->d_small + 7, 0, 8, h->stream));
-            hipLaunchKernelGGL(k_chunk_match, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, d_vr, d_spec, d_truth, n_vr, d_cursor, d_stop);
-            hipLaunchKernelGGL(k_chunk_commit, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, d_vr, n_vr, chunk, (u32)h->P.k, (u32)h->P.w, d_starts, d_cursor,
-                               d_stop, d_status, d_rerun, (u32*)(h->d_small + 7));
-            hipLaunchKernelGGL(k_chunk_next, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, d_vr, n_vr, d_cursor, d_stop);
-            if (int lrc = launch_check(h, "k_chunk_match/commit/next")) return lrc;
-            HIPCHK(h, hipMemcpyAsync(h->h_small + 7, h->d_small + 7, 8, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            const u32 n_rerun = (u32)h->h_small[7];
-            if (!n_rerun) break;
-            total_rerun += n_rerun;
-            ChunkCtl c3{d_rerun, d_spec, d_truth, 0u, d_cbase};
-            if ((rc = launch_scan(h, d_packed, d_starts, n_rerun, out3, false, false, c3, pos))) return rc;
-        }
-        static const bool dbg_chunks = getenv("BRISK_DEBUG_CHUNKS") != nullptr;
-        if (dbg_chunks) fprintf(stderr, "[brisk_hip] chunked scan: %u chunks of %u steps, %llu seeded re-scans in %u rounds\n", n_vr, chunk,
-                                (unsigned long long)total_rerun, rounds);
-        if (pos && total_rerun) {
-            // drop what the re-scanned chunks emitted speculatively, anchors alongside; what the seeded scans emitted stays
-            HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (!(u32)h->h_small[1]) {
-                const u64 n3 = std::min<u64>(h->h_small[0], cap);
-                if ((rc = ensure(h, h->parted, (n3 - n1 + 1) * (h->P.stride * 8 + 8)))) return rc;
-                u64* stage = (u64*)h->parted.p;
-                u64* stage_anc = stage + (n3 - n1 + 1) * h->P.stride;
-                HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 8, h->stream));
-                hipLaunchKernelGGL(k_pos_filter, dim3(nblocks(n3 - n1, 256)), dim3(256), 0, h->stream, h->P, d_rec, d_anchor, d_ctags, n1, n2, n3, d_status, stage, stage_anc,
-                                   h->d_small + 6);
-                if (int lrc = launch_check(h, "k_pos_filter")) return lrc;
-                HIPCHK(h, hipMemcpyAsync(h->h_small + 6, h->d_small + 6, 8, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                const u64 kept = h->h_small[6];
-                if (kept) {
-                    HIPCHK(h, hipMemcpyAsync(d_rec + n1 * h->P.stride, stage, kept * h->P.stride * 8, hipMemcpyDeviceToDevice, h->stream));
-                    HIPCHK(h, hipMemcpyAsync(d_anchor + n1, stage_anc, kept * 8, hipMemcpyDeviceToDevice, h->stream));
-                }
-                h->h_small[6] = n1 + kept;  // pinned: stays untouched until the copy below has run
-                HIPCHK(h, hipMemcpyAsync(h->d_small, h->h_small + 6, 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-            }
-            if (hist_valid) *hist_valid = false;
-        } else if (pos) {
-            // no chunk was re-scanned: every record stands
-        } else if (query_mode) {
-            // stop every sequence where query_sequence stops it, drop the void records, tag the rest with their read
-            HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (!(u32)h->h_small[1]) {
-                const u64 n3 = std::min<u64>(h->h_small[0], cap);
-                unsigned long long* d_brk = (unsigned long long*)(d_qret + cap);
-                if ((rc = ensure(h, h->parted, (n3 - n1 + 1) * (h->P.stride * 8 + 4)))) return rc;
-                u64* stage = (u64*)h->parted.p;
-                u32* stage_tags = (u32*)(stage + (n3 - n1 + 1) * h->P.stride);
-                HIPCHK(h, hipMemsetAsync(d_brk, 0xff, cap_vr * 8, h->stream));
-                HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 8, h->stream));
-                if (n3 > n1) {
-                    hipLaunchKernelGGL(k_query_break, dim3(nblocks(n3 - n1, 256)), dim3(256), 0, h->stream, d_qret, d_ctags, n1, n2, n3, d_vr, d_status, d_starts, d_brk);
-                    hipLaunchKernelGGL(k_query_filter, dim3(nblocks(n3 - n1, 256)), dim3(256), 0, h->stream, h->P, d_rec, d_qret, d_ctags, n1, n2, n3, d_vr, d_status,
-                                       d_brk, stage, stage_tags, h->d_small + 6);
-                    if (int lrc = launch_check(h, "k_query_break/filter")) return lrc;
-                }
-                HIPCHK(h, hipMemcpyAsync(h->h_small + 6, h->d_small + 6, 8, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                const u64 kept = h->h_small[6];
-                if (kept) {
-                    HIPCHK(h, hipMemcpyAsync(d_rec + n1 * h->P.stride, stage, kept * h->P.stride * 8, hipMemcpyDeviceToDevice, h->stream));
-                    HIPCHK(h, hipMemcpyAsync(d_ctags + n1, stage_tags, kept * 4, hipMemcpyDeviceToDevice, h->stream));
-                }
-                h->h_small[6] = n1 + kept;  // pinned: stays untouched until the copy below has run
-                HIPCHK(h, hipMemcpyAsync(h->d_small, h->h_small + 6, 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-            }
-            if (hist_valid) *hist_valid = false;
-        } else if (total_rerun) {
-            HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (!(u32)h->h_small[1]) {
-                // drop what the re-scanned chunks emitted speculatively ([n1, n2)); what the seeded scans emitted ([n2, n3)) stays
-                const u64 n3 = std::min<u64>(h->h_small[0], cap);
-                if ((rc = ensure(h, h->parted, (n3 - n1 + 1) * h->P.stride * 8))) return rc;
-                HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 8, h->stream));
-                hipLaunchKernelGGL(k_filter_records, dim3(nblocks(n2 - n1, 256)), dim3(256), 0, h->stream, h->P, d_rec, (const u32*)h->tags_a.p, n1, n2, d_status,
-                                   (u64*)h->parted.p, h->d_small + 6);
-                if (int lrc = launch_check(h, "k_filter_records")) return lrc;
-                HIPCHK(h, hipMemcpyAsync(h->h_small + 6, h->d_small + 6, 8, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                const u64 kept = h->h_small[6];
-                char* stage = (char*)h->parted.p;
-                if (n3 > n2) HIPCHK(h, hipMemcpyAsync(stage + kept * h->P.stride * 8, d_rec + n2 * h->P.stride, (n3 - n2) * h->P.stride * 8, hipMemcpyDeviceToDevice, h->stream));
-                if (kept + n3 - n2) HIPCHK(h, hipMemcpyAsync(d_rec + n1 * h->P.stride, stage, (kept + n3 - n2) * h->P.stride * 8, hipMemcpyDeviceToDevice, h->stream));
-                h->h_small[6] = n1 + kept + (n3 - n2);  // pinned: stays untouched until the copy below has run
-                HIPCHK(h, hipMemcpyAsync(h->d_small, h->h_small + 6, 8, hipMemcpyHostToDevice, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-            }
-            if (hist_valid) *hist_valid = false;
-        }
-    }
-    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *n_rec_out = h->h_small[0];
-    if ((u32)h->h_small[1]) return BRISK_HIP_ECAPACITY;
+    cp->n_vr = h->h_ctr->plan.n_vr;
+    if (cp->n_vr > cap_vr) return fail(h, BRISK_HIP_EHIP, "chunk plan exceeds its bound");
     return BRISK_HIP_OK;
 }
 
+// The chunks' speculative launch behind the short reads' records, then rounds of match / commit / next with a seeded re-scan of the
+// chunks whose seam did not match (one round per mismatch along a sequence; no mismatch: one round).
+int scan_chunks(brisk_hip_index* h, const ScanReq& q, const ScanOut& out, ChunkPlan* cp) {
+    const bool pos = q.mode == ScanMode::Position;
+    const u32 n_vr = cp->n_vr;
+    int rc;
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->scan));
+    cp->n1 = std::min<u64>(h->h_ctr->scan.n_rec, q.cap);
+    cp->ctags = q.d_tags;
+    if (pos) {
+        hipLaunchKernelGGL(k_chunk_slot_base, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, cp->vr, n_vr, q.d_slot_base, cp->cbase);
+        if (int lrc = launch_check(h, "k_chunk_slot_base")) return lrc;
+    } else if (q.mode == ScanMode::Insert) {
+        if ((rc = ensure(h, h->tags_a, q.cap * 4))) return rc;
+        cp->ctags = (u32*)h->tags_a.p;
+    } else {
+        if ((rc = ensure(h, h->seq_buf, q.cap * 8 + cp->cap_vr * 8))) return rc;
+        cp->qret = (u64*)h->seq_buf.p;
+    }
+    HIPCHK(h, hipMemsetAsync(cp->spec, 0, (2 * cp->cap_vr + 1) * sizeof(ChunkState) + 2 * cp->cap_vr * 4, h->stream));  // states, status, cursor
+    HIPCHK(h, hipMemsetAsync(cp->stop, 0xff, cp->cap_vr * 4, h->stream));
+    ScanOut out2 = out;
+    out2.tag = cp->ctags;
+    out2.ret = pos ? q.d_side : cp->qret;
+    ChunkCtl c2{cp->vr, cp->spec, cp->truth, 0u, cp->cbase};
+    if ((rc = launch_scan(h, q.d_packed, q.d_starts, n_vr, out2, false, false, c2, pos))) return rc;
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->scan));
+    cp->n2 = std::min<u64>(h->h_ctr->scan.n_rec, q.cap);
+    ScanOut out3 = out2;
+    out3.hist = nullptr;  // once a chunk is re-scanned the histogram is rebuilt from the final records
+    u32 rounds = 0;
+    for (;; rounds++) {
+        HIPCHK(h, zero_ctr(h, &h->d_ctr->n_rerun));
+        hipLaunchKernelGGL(k_chunk_match, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, cp->vr, cp->spec, cp->truth, n_vr, cp->cursor, cp->stop);
+        hipLaunchKernelGGL(k_chunk_commit, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, cp->vr, n_vr, cp->chunk, (u32)h->P.k, (u32)h->P.w, q.d_starts, cp->cursor,
+                           cp->stop, cp->status, cp->rerun, &h->d_ctr->n_rerun);
+        hipLaunchKernelGGL(k_chunk_next, dim3(nblocks(n_vr, 256)), dim3(256), 0, h->stream, cp->vr, n_vr, cp->cursor, cp->stop);
+        if (int lrc = launch_check(h, "k_chunk_match/commit/next")) return lrc;
+        HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->n_rerun));
+        const u32 n_rerun = h->h_ctr->n_rerun;
+        if (!n_rerun) break;
+        cp->total_rerun += n_rerun;
+        ChunkCtl c3{cp->rerun, cp->spec, cp->truth, 0u, cp->cbase};
+        if ((rc = launch_scan(h, q.d_packed, q.d_starts, n_rerun, out3, false, false, c3, pos))) return rc;
+    }
+    static const bool dbg_chunks = getenv("BRISK_DEBUG_CHUNKS") != nullptr;
+    if (dbg_chunks) fprintf(stderr, "[brisk_hip] chunked scan: %u chunks of %u steps, %llu seeded re-scans in %u rounds\n", n_vr, cp->chunk,
+                            (unsigned long long)cp->total_rerun, rounds);
+    return BRISK_HIP_OK;
+}
+
+// The chunked records [n1, n3) closed up through a stage in `parted`, their side array alongside (query: tags, position: anchors).  Insert and
+// position mode: drop what the re-scanned chunks emitted speculatively in [n1, n2), keep what the seeded scans emitted in [n2, n3) (appended by copy;
+// k_pos_filter takes it along); nothing to do when no chunk was re-scanned.  Query mode: stop every sequence where query_sequence stops it, drop
+// the void records, tag the rest with their read.
+int compact_chunks(brisk_hip_index* h, const ScanReq& q, const ChunkPlan& cp, ScanRes* res) {
+    const bool ins = q.mode == ScanMode::Insert, qry = q.mode == ScanMode::Query;
+    if (!qry && !cp.total_rerun) return BRISK_HIP_OK;
+    res->hist_valid = false;
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->scan));
+    if (h->h_ctr->scan.overflow) return BRISK_HIP_OK;
+    const u64 n1 = cp.n1, n2 = cp.n2, n3 = std::min<u64>(h->h_ctr->scan.n_rec, q.cap), stride = h->P.stride;
+    const size_t side_bytes = ins ? 0 : qry ? 4 : 8;
+    if (int rc = ensure(h, h->parted, (n3 - n1 + 1) * (stride * 8 + side_bytes))) return rc;
+    u64* stage = (u64*)h->parted.p;
+    void* stage_side = stage + (n3 - n1 + 1) * stride;
+    unsigned long long* d_brk = qry ? (unsigned long long*)(cp.qret + q.cap) : nullptr;
+    if (qry) HIPCHK(h, hipMemsetAsync(d_brk, 0xff, cp.cap_vr * 8, h->stream));
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->kept));
+    if (ins) {  // reads [n1, n2): the speculative records whose chunk was not re-scanned go to the stage; [n2, n3) is appended by copy below
+        hipLaunchKernelGGL(k_filter_records, dim3(nblocks(n2 - n1, 256)), dim3(256), 0, h->stream, h->P, q.d_rec, (const u32*)cp.ctags, n1, n2, cp.status, stage, &h->d_ctr->kept);
+        if (int lrc = launch_check(h, "k_filter_records")) return lrc;
+    } else if (!qry) {  // reads [n1, n3): the same selection in [n1, n2), all of [n2, n3), each record with its anchor
+        hipLaunchKernelGGL(k_pos_filter, dim3(nblocks(n3 - n1, 256)), dim3(256), 0, h->stream, h->P, q.d_rec, q.d_side, cp.ctags, n1, n2, n3, cp.status, stage, (u64*)stage_side,
+                           &h->d_ctr->kept);
+        if (int lrc = launch_check(h, "k_pos_filter")) return lrc;
+    } else if (n3 > n1) {  // reads [n1, n3): where each sequence stops (d_brk), then the records before the stop that are not void, each with its read
+        hipLaunchKernelGGL(k_query_break, dim3(nblocks(n3 - n1, 256)), dim3(256), 0, h->stream, cp.qret, cp.ctags, n1, n2, n3, cp.vr, cp.status, q.d_starts, d_brk);
+        hipLaunchKernelGGL(k_query_filter, dim3(nblocks(n3 - n1, 256)), dim3(256), 0, h->stream, h->P, q.d_rec, cp.qret, cp.ctags, n1, n2, n3, cp.vr, cp.status, d_brk, stage,
+                           (u32*)stage_side, &h->d_ctr->kept);
+        if (int lrc = launch_check(h, "k_query_break/filter")) return lrc;
+    }
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->kept));
+    const u64 kept = h->h_ctr->kept, n_out = ins ? kept + (n3 - n2) : kept;
+    if (ins && n3 > n2) HIPCHK(h, hipMemcpyAsync(stage + kept * stride, q.d_rec + n2 * stride, (n3 - n2) * stride * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (n_out) HIPCHK(h, hipMemcpyAsync(q.d_rec + n1 * stride, stage, n_out * stride * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (qry && kept) HIPCHK(h, hipMemcpyAsync(cp.ctags + n1, stage_side, kept * 4, hipMemcpyDeviceToDevice, h->stream));
+    else if (!ins && kept) HIPCHK(h, hipMemcpyAsync(q.d_side + n1, stage_side, kept * 8, hipMemcpyDeviceToDevice, h->stream));
+    h->h_ctr->n_rec_new = n1 + n_out;  // pinned: stays untouched until the copy below has run
+    HIPCHK(h, hipMemcpyAsync(&h->d_ctr->scan.n_rec, &h->h_ctr->n_rec_new, 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// Scan a batch into q.d_rec.  Long sequences are scanned as chunks, checked at the seams and, where a seam does not match,
+// re-scanned from it; res->n_rec on the host after a sync.
+int scan_impl(brisk_hip_index* h, const ScanReq& q, ScanRes* res) {
+    const bool pos = q.mode == ScanMode::Position, seq = q.mode == ScanMode::Sequence;
+    res->hist_valid = q.with_hist;
+    if (q.with_hist) {
+        h->scan_hist_valid = false;
+        if (!q.keep_hist) HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
+    }
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->scan));
+    ScanOut out{q.d_rec, q.cap, &h->d_ctr->scan.n_rec, q.with_hist ? h->d_hist : nullptr, &h->d_ctr->scan.overflow, q.d_tags, q.d_side, nullptr, 0u, nullptr, 0u, nullptr};
+    const bool plain = seq || (!pos && h->scan_v1);  // the plain restatement kernel (sequence mode needs the minimizer values it carries)
+    int rc;
+    ChunkPlan cp;
+    if (!plain && q.kmer_bound > SCAN_LONG && (rc = plan_chunks(h, q, &cp))) return rc;
+    ChunkCtl cc{nullptr, nullptr, nullptr, cp.n_vr ? SCAN_LONG : 0u, q.d_slot_base};
+    if ((rc = launch_scan(h, q.d_packed, q.d_starts, q.n_reads, out, q.mode == ScanMode::Query, plain, cc, pos))) return rc;
+    if (cp.n_vr) {
+        if ((rc = scan_chunks(h, q, out, &cp))) return rc;
+        if ((rc = compact_chunks(h, q, cp, res))) return rc;
+    }
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->scan));
+    res->n_rec = h->h_ctr->scan.n_rec;
+    return h->h_ctr->scan.overflow ? BRISK_HIP_ECAPACITY : BRISK_HIP_OK;
+}
+
 int count_kmers(brisk_hip_index* h, const u64* d_starts, u64 n_reads, u64* out, u64* out_long = nullptr) {
-    HIPCHK(h, hipMemsetAsync(h->d_small + 4, 0, 16, h->stream));
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->kmers));
     {
         ProfScope ps(h, S_COUNT);
         const u32 grid = std::min<u32>(nblocks(n_reads, 256), 4096);
-        hipLaunchKernelGGL(k_count_kmers, dim3(grid ? grid : 1), dim3(256), 0, h->stream, d_starts, n_reads, h->P.k, h->d_small + 4);
+        hipLaunchKernelGGL(k_count_kmers, dim3(grid ? grid : 1), dim3(256), 0, h->stream, d_starts, n_reads, h->P.k, &h->d_ctr->kmers.bound);
         if (int lrc = launch_check(h, "k_count_kmers")) return lrc;
     }
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 4, h->d_small + 4, 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->h_small[5] >> 63) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i]): not a read table, or the buffer was overwritten while the call ran");
-    *out = h->h_small[4];
-    if (out_long) *out_long = h->h_small[5];
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->kmers));
+    if (h->h_ctr->kmers.n_long >> 63) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i]): not a read table, or the buffer was overwritten while the call ran");
+    *out = h->h_ctr->kmers.bound;
+    if (out_long) *out_long = h->h_ctr->kmers.n_long;
     return BRISK_HIP_OK;
 }
 
@@ -955,31 +978,41 @@ static u64 records_estimate(const brisk_hip_index* h, u64 bound, u64 n_reads) {
     return std::min<u64>(bound, est);
 }
 
-// scan a batch into the staging buffer, retrying once with the exact bound
-int scan_to_staging(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, bool with_hist, bool query_mode,
-                    u64* n_rec_out, bool* hist_valid = nullptr) {
-    int rc;
-    u64 bound = 0, in_long = 0;
-    if ((rc = count_kmers(h, d_starts, n_reads, &bound, &in_long))) return rc;
-    if (bound == 0) {
-        *n_rec_out = 0;
-        return BRISK_HIP_OK;
-    }
-    (void)in_long;
-    u64 cap = records_estimate(h, bound, n_reads);
+// Scan at the first guess (records_estimate) and, when that overflows, once more at the exact bound q.kmer_bound.  place(attempt, q)
+// makes room for q.cap records and says where they and what travels with them go; q is left as the last attempt had it.
+static const long scan_cap0 = getenv("BRISK_SCAN_CAP0") ? atol(getenv("BRISK_SCAN_CAP0")) : 0;  // tests: at most so many records at the first attempt, so that the second one runs
+template <class Place>
+int scan_retry(brisk_hip_index* h, ScanReq& q, Place place, ScanRes* res) {
+    const u64 est = records_estimate(h, q.kmer_bound, q.n_reads);
     for (int attempt = 0; attempt < 2; attempt++) {
-        if ((rc = ensure(h, h->staging, cap * h->P.stride * 8))) return rc;
-        u32* tags = nullptr;
-        if (query_mode) {
-            if ((rc = ensure(h, h->tags_a, cap * 4))) return rc;
-            tags = (u32*)h->tags_a.p;
-        }
-        rc = scan_impl(h, d_packed, d_starts, n_reads, (u64*)h->staging.p, cap, with_hist, query_mode, tags, n_rec_out, nullptr, bound, hist_valid);
-        if (rc == BRISK_HIP_OK && h->verify && !query_mode) return verify_records(h, (const u64*)h->staging.p, *n_rec_out, bound, "scan to staging");
+        q.cap = attempt ? q.kmer_bound : scan_cap0 > 0 ? std::min<u64>(est, (u64)scan_cap0) : est;
+        int rc = place(attempt, q);
+        if (rc == BRISK_HIP_OK) rc = scan_impl(h, q, res);
         if (rc != BRISK_HIP_ECAPACITY) return rc;
-        cap = bound;
     }
     return fail(h, BRISK_HIP_EHIP, "scan overflowed its exact bound");
+}
+
+// scan a batch (q: mode, reads, and in position mode the slot bases) into the staging buffer, with its histogram; what travels with
+// the records goes to tags_a (query and position mode) and h->anchors (position mode)
+int scan_to_staging(brisk_hip_index* h, ScanReq q, ScanRes* res) {
+    int rc;
+    *res = ScanRes{};
+    if ((rc = count_kmers(h, q.d_starts, q.n_reads, &q.kmer_bound))) return rc;
+    if (q.kmer_bound == 0) return BRISK_HIP_OK;
+    q.with_hist = true;
+    rc = scan_retry(h, q, [h](int, ScanReq& a) -> int {
+        int prc;
+        if ((prc = ensure(h, h->staging, a.cap * h->P.stride * 8))) return prc;
+        if (a.mode != ScanMode::Insert && (prc = ensure(h, h->tags_a, a.cap * 4))) return prc;
+        if (a.mode == ScanMode::Position && (prc = ensure(h, h->anchors, a.cap * 8))) return prc;
+        a.d_rec = (u64*)h->staging.p;
+        a.d_tags = a.mode != ScanMode::Insert ? (u32*)h->tags_a.p : nullptr;
+        a.d_side = a.mode == ScanMode::Position ? (u64*)h->anchors.p : nullptr;
+        return BRISK_HIP_OK;
+    }, res);
+    if (rc == BRISK_HIP_OK && h->verify && q.mode == ScanMode::Insert) return verify_records(h, (const u64*)h->staging.p, res->n_rec, q.kmer_bound, "scan to staging");
+    return rc;
 }
 
 // the parameter sets k_insert_fast / k_query_fast are instantiated for (the only kernels that read the binned layout in query mode)
@@ -1027,24 +1060,24 @@ int scan_binned(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
     if (pos && (rc = ensure(h, h->anchors, (h->n_parts * cap + ovf_cap) * 8))) return rc == BRISK_HIP_ENOMEM ? (h->err.clear(), BRISK_HIP_OK) : rc;
     h->scan_hist_valid = false;
     HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 16, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->d_small + 7, 0, 8, h->stream));
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->scan));
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->n_ovf));
     HIPCHK(h, hipMemsetAsync(h->d_ovf_cnt, 0, OVF_REGIONS * 4, h->stream));
-    ScanOut out{nullptr, 0, h->d_small, h->d_hist, (u32*)(h->d_small + 1), tags, pos ? (u64*)h->anchors.p : nullptr, (u64*)h->bins.p, (u32)cap, (u64*)h->staging.p,
+    ScanOut out{nullptr, 0, &h->d_ctr->scan.n_rec, h->d_hist, &h->d_ctr->scan.overflow, tags, pos ? (u64*)h->anchors.p : nullptr, (u64*)h->bins.p, (u32)cap, (u64*)h->staging.p,
                 ovf_region_cap, h->d_ovf_cnt};
     ChunkCtl cc{nullptr, nullptr, nullptr, 0u, pos_slot_base};
     if ((rc = launch_scan(h, d_packed, d_starts, n_reads, out, query_mode, false, cc, pos))) return rc;
-    hipLaunchKernelGGL(k_sum_regions, dim3(1), dim3(1024), 0, h->stream, h->d_ovf_cnt, ovf_region_cap, h->d_small + 7);
+    hipLaunchKernelGGL(k_sum_regions, dim3(1), dim3(1024), 0, h->stream, h->d_ovf_cnt, ovf_region_cap, &h->d_ctr->n_ovf);
     if ((rc = launch_check(h, "k_sum_regions"))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 7, h->d_small + 7, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if ((u32)h->h_small[1]) return BRISK_HIP_OK;  // more records beyond the bins than the overflow buffer holds: the classic path takes the batch
-    *n_rec_out = h->h_small[0];
+    HIPCHK(h, fetch_ctr(h, &h->d_ctr->scan));
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->n_ovf));
+    const u64 n_rec = h->h_ctr->scan.n_rec, n_ovf = h->h_ctr->n_ovf;
+    if (h->h_ctr->scan.overflow) return BRISK_HIP_OK;  // more records beyond the bins than the overflow buffer holds: the classic path takes the batch
+    *n_rec_out = n_rec;
     if (h->trace) fprintf(stderr, "[brisk_hip] path: binned scan of %llu reads: %llu records, bins of %llu, %llu records beyond their bins\n", (unsigned long long)n_reads,
-                          (unsigned long long)h->h_small[0], (unsigned long long)cap, (unsigned long long)h->h_small[7]);
-    *bl = BinLayout{(u64*)h->bins.p, (u32)cap, (u64*)h->staging.p, h->h_small[7], h->d_ovf_cnt, ovf_region_cap, tags};
-    if (h->verify && !query_mode && !pos && (rc = verify_hist(h, h->h_small[0], bound, "binned scan"))) return rc;
+                          (unsigned long long)n_rec, (unsigned long long)cap, (unsigned long long)n_ovf);
+    *bl = BinLayout{(u64*)h->bins.p, (u32)cap, (u64*)h->staging.p, n_ovf, h->d_ovf_cnt, ovf_region_cap, tags};
+    if (h->verify && !query_mode && !pos && (rc = verify_hist(h, n_rec, bound, "binned scan"))) return rc;
     *applied = true;
     return BRISK_HIP_OK;
 }
@@ -1111,43 +1144,42 @@ int defer_batch(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
     *deferred = false;
     if (!h->defer || h->entry_ids || h->scan_v1 || h->P.n_owners > 1) return BRISK_HIP_OK;
     int rc;
-    u64 bound = 0;
-    if ((rc = count_kmers(h, d_starts, n_reads, &bound))) return rc;
-    if (bound == 0) {
+    ScanReq q{ScanMode::Insert, d_packed, d_starts, n_reads};
+    if ((rc = count_kmers(h, d_starts, n_reads, &q.kmer_bound))) return rc;
+    if (q.kmer_bound == 0) {
         *deferred = true;  // nothing to insert
         return BRISK_HIP_OK;
     }
-    const u64 est = records_estimate(h, bound, n_reads);
-    if (est >= (u64)DEFER_DIRECT_AT * h->n_parts) return BRISK_HIP_OK;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        const u64 cap = attempt ? bound : est;
-        if ((rc = pend_reserve(h, cap))) {
-            if (rc != BRISK_HIP_ENOMEM) return rc;
-            // no room for the pending buffer: what is pending goes in now, and this batch takes the direct path, which needs none
-            h->err.clear();
-            return flush_pending(h);
-        }
-        u64 n_rec = 0;
-        bool hist_ok = true;
-        const bool with_hist = h->pend_hist_ok;
-        rc = scan_impl(h, d_packed, d_starts, n_reads, (u64*)h->pend.p + h->n_pend * h->P.stride, cap, with_hist, false, nullptr, &n_rec, nullptr, bound, &hist_ok,
-                       /*keep_hist=*/h->n_pend > 0);
-        if (rc == BRISK_HIP_ECAPACITY) {  // the first guess was too small: what it counted before it stopped is in d_hist
+    if (records_estimate(h, q.kmer_bound, n_reads) >= (u64)DEFER_DIRECT_AT * h->n_parts) return BRISK_HIP_OK;
+    bool no_room = false;
+    int attempts = 0;
+    ScanRes res;
+    rc = scan_retry(h, q, [&](int attempt, ScanReq& a) -> int {
+        attempts = attempt + 1;
+        if (attempt) {  // the first guess was too small: what it counted before it stopped is in d_hist
             h->pend_hist_ok = false;
             h->err.clear();
-            continue;
         }
-        if (rc) return rc;
-        if (h->verify && (rc = verify_records(h, (const u64*)h->pend.p + h->n_pend * h->P.stride, n_rec, bound, "deferred scan"))) return rc;
-        if (!with_hist || !hist_ok) h->pend_hist_ok = false;
-        if (h->trace) fprintf(stderr, "[brisk_hip] path: deferred scan of %llu reads (attempt %d): %llu records behind %llu pending ones, histogram %s\n", (unsigned long long)n_reads, attempt,
-                              (unsigned long long)n_rec, (unsigned long long)h->n_pend, h->pend_hist_ok ? "kept" : "to be recounted");
-        h->n_pend += n_rec;
-        *deferred = true;
-        if (h->n_pend >= (u64)DEFER_FLUSH_AT * h->n_parts) return flush_pending(h);
-        return BRISK_HIP_OK;
+        const int prc = pend_reserve(h, a.cap);
+        no_room = prc == BRISK_HIP_ENOMEM;
+        a.d_rec = (u64*)h->pend.p + h->n_pend * h->P.stride;
+        a.with_hist = h->pend_hist_ok;
+        a.keep_hist = h->n_pend > 0;
+        return prc;
+    }, &res);
+    if (no_room) {  // no room for the pending buffer: what is pending goes in now, and this batch takes the direct path, which needs none
+        h->err.clear();
+        return flush_pending(h);
     }
-    return fail(h, BRISK_HIP_EHIP, "scan overflowed its exact bound");
+    if (rc) return rc;
+    if (h->verify && (rc = verify_records(h, q.d_rec, res.n_rec, q.kmer_bound, "deferred scan"))) return rc;
+    if (!res.hist_valid) h->pend_hist_ok = false;
+    if (h->trace) fprintf(stderr, "[brisk_hip] path: deferred scan of %llu reads (attempt %d): %llu records behind %llu pending ones, histogram %s\n", (unsigned long long)n_reads, attempts - 1,
+                          (unsigned long long)res.n_rec, (unsigned long long)h->n_pend, h->pend_hist_ok ? "kept" : "to be recounted");
+    h->n_pend += res.n_rec;
+    *deferred = true;
+    if (h->n_pend >= (u64)DEFER_FLUSH_AT * h->n_parts) return flush_pending(h);
+    return BRISK_HIP_OK;
 }
 
 // what every entry point other than the inserts does first: the index as of all completed insert calls
@@ -1156,7 +1188,6 @@ static int enter(brisk_hip_index* h) { return flush_pending(h); }
 int insert_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads) {
     for (u64 r0 = 0; r0 < n_reads; r0 += h->max_batch_reads) {
         const u64 nb = std::min<u64>(h->max_batch_reads, n_reads - r0);
-        u64 n_rec = 0;
         int rc;
         bool done = false;
         if ((rc = defer_batch(h, d_packed, d_starts + r0, nb, &done))) return rc;
@@ -1165,9 +1196,9 @@ int insert_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_sta
         if ((rc = insert_packed_binned(h, d_packed, d_starts + r0, nb, &done))) return rc;
         if (h->trace) fprintf(stderr, "[brisk_hip] path: direct insert of %llu reads, %s\n", (unsigned long long)nb, done ? "records binned by the scan" : "records to staging, then k_scatter");
         if (done) continue;
-        bool hist_ok = true;
-        if ((rc = scan_to_staging(h, d_packed, d_starts + r0, nb, true, false, &n_rec, &hist_ok))) return rc;
-        if ((rc = insert_records_impl(h, (const u64*)h->staging.p, n_rec, hist_ok))) return rc;
+        ScanRes res;
+        if ((rc = scan_to_staging(h, {ScanMode::Insert, d_packed, d_starts + r0, nb}, &res))) return rc;
+        if ((rc = insert_records_impl(h, (const u64*)h->staging.p, res.n_rec, res.hist_valid))) return rc;
     }
     return BRISK_HIP_OK;
 }
@@ -1189,14 +1220,12 @@ int query_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_star
         if ((rc = scan_binned(h, d_packed, d_starts, n_reads, true, &binned, &bl, &n_rec))) return rc;
         if (binned) return n_rec ? query_records_impl(h, nullptr, nullptr, n_rec, d_sums, &bl) : BRISK_HIP_OK;
     }
-    bool hist_ok = true;
-    if ((rc = scan_to_staging(h, d_packed, d_starts, n_reads, true, true, &n_rec, &hist_ok))) return rc;
+    ScanRes res;
+    if ((rc = scan_to_staging(h, {ScanMode::Query, d_packed, d_starts, n_reads}, &res))) return rc;
+    n_rec = res.n_rec;
     if (n_rec == 0) return BRISK_HIP_OK;
-    if (!hist_ok) {  // long sequences were scanned in chunks and cut where the query stops: count the records that are left
-        HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
-        hipLaunchKernelGGL(k_part_hist, dim3(nblocks(n_rec, 256)), dim3(256), 0, h->stream, h->P, (const u64*)h->staging.p, n_rec, h->d_hist);
-        if (int lrc = launch_check(h, "k_part_hist")) return lrc;
-    }
+    // long sequences were scanned in chunks and cut where the query stops: count the records that are left
+    if (!res.hist_valid && (rc = rebuild_hist(h, (const u64*)h->staging.p, n_rec))) return rc;
     return query_records_impl(h, (const u64*)h->staging.p, (const u32*)h->tags_a.p, n_rec, d_sums);
 }
 
@@ -1208,8 +1237,8 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
     int rc;
     const u64 n_move = bl ? bl->n_ovf : n_rec;
     if (n_move && (rc = prefix_partitions(h, bl ? bl->bin_cap : 0u))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d_small + 2, 0, 8, h->stream));
-    if ((rc = list_touched(h, (u32*)(h->d_small + 2)))) return rc;
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->touched.n_touched));
+    if ((rc = list_touched(h, &h->d_ctr->touched.n_touched))) return rc;
     if (n_move) {
         ProfScope ps(h, S_SCATTER);
         if ((rc = ensure(h, h->parted, n_move * P.stride * 8))) return rc;
@@ -1218,14 +1247,14 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
         hipLaunchKernelGGL(k_scatter, dim3(nblocks(n_slots, 256)), dim3(256), 0, h->stream, P, bl ? (const u64*)bl->ovf : d_rec, n_move, h->d_cur32, (u64*)h->parted.p, 0,
                            bl ? bl->tags + h->n_parts * bl->bin_cap : d_tags, (u32*)h->tags_b.p, h->ix.err, bl ? bl->ovf_cnt : (const u32*)nullptr, bl ? bl->ovf_region_cap : 0u);
     }
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 2, h->d_small + 2, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 5, h->ix.cursor, 8, hipMemcpyDeviceToHost, h->stream));  // arena slots handed out so far
+    HIPCHK(h, fetch_ctr(h, &h->d_ctr->touched.n_touched));
+    HIPCHK(h, hipMemcpyAsync(&h->h_ctr->arena_used, h->ix.cursor, 8, hipMemcpyDeviceToHost, h->stream));  // arena slots handed out so far
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const u32 n_touched = (u32)h->h_small[2];
-    h->arena_used_host = h->h_small[5];
+    const u32 n_touched = h->h_ctr->touched.n_touched;
+    h->arena_used_host = h->h_ctr->arena_used;
     if (n_touched == 0) return BRISK_HIP_OK;
     if ((rc = ensure(h, h->desc, (size_t)n_touched * sizeof(PartDesc)))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d_small + 3, 0, 8, h->stream));
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->touched.need));
     // partitions whose entries x instances would keep one wave busy for long go to k_query_huge, a workgroup each
     static const long hq_env = getenv("BRISK_HUGE_QUERY_AT") ? atol(getenv("BRISK_HUGE_QUERY_AT")) : -1;  // entries; tests: 0 sends (nearly) everything there
     const u32 hq_at = hq_env >= 0 ? (u32)hq_env : 4096u;
@@ -1234,13 +1263,13 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
     {
         ProfScope ps(h, S_TOUCHED);
         hipLaunchKernelGGL(k_need, dim3(std::min<u32>(nblocks(n_touched, 256), 2048)), dim3(256), 0, h->stream, h->d_hist, (bl && !n_move) ? (const u32*)nullptr : h->d_off,
-                           h->d_touched, n_touched, h->ix.dir, (PartDesc*)h->desc.p, h->d_small + 3, bl ? bl->bin_cap : 0u, 0u, (u32*)h->huge.p, (u32)HUGE_LIST_CAP, hq_at,
+                           h->d_touched, n_touched, h->ix.dir, (PartDesc*)h->desc.p, &h->d_ctr->touched.need, bl ? bl->bin_cap : 0u, 0u, (u32*)h->huge.p, (u32)HUGE_LIST_CAP, hq_at,
                            hq_env >= 0 ? 0ull : 1ull << 26);
         if (int lrc = launch_check(h, "k_need")) return lrc;
     }
     {
         ProfScope ps(h, S_QUERY);
-        HIPCHK(h, hipMemsetAsync(h->d_small + 6, 0, 8, h->stream));
+        HIPCHK(h, zero_ctr(h, &h->d_ctr->work.wc));
         const u32 batches = (n_touched + WI_BATCH - 1) / WI_BATCH;
         const RecSrc src{bl ? bl->bins : (u64*)h->parted.p, (const u64*)h->parted.p, bl ? bl->bin_cap : 0u};
         const u32* tags_binned = bl ? bl->tags : nullptr;
@@ -1258,11 +1287,11 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
     do {                                                                                                                                                              \
         if (kout)                                                                                                                                                     \
             hipLaunchKernelGGL((k_query_fast<NW, KB, SH, ENT, true>), dim3(std::min<u32>(batches, resident((const void*)k_query_fast<NW, KB, SH, ENT, true>))), dim3(64), \
-                               0, h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6),  \
+                               0, h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, h->d_ctr->work.wc,  \
                                anchors, kout, kout_n);                                                                                                                \
         else                                                                                                                                                          \
             hipLaunchKernelGGL((k_query_fast<NW, KB, SH, ENT>), dim3(std::min<u32>(batches, resident((const void*)k_query_fast<NW, KB, SH, ENT>))), dim3(64), 0,        \
-                               h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6)); \
+                               h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, h->d_ctr->work.wc); \
     } while (0)
 #define LAUNCH_QUERY_FAST(NW, KB, SH)                     \
     {                                                     \
@@ -1282,10 +1311,10 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
         else if (bl) return fail(h, BRISK_HIP_EHIP, "binned query without a kernel for this geometry");
         else if (kout)
             hipLaunchKernelGGL(k_query<true>, dim3(std::min<u32>(batches, INSERT_SLOTS)), dim3(64), 0, h->stream, P, (const u64*)h->parted.p, (const u32*)h->tags_b.p,
-                               (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6), anchors, kout, kout_n);
+                               (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, h->d_ctr->work.wc, anchors, kout, kout_n);
         else
             hipLaunchKernelGGL(k_query<>, dim3(std::min<u32>(batches, INSERT_SLOTS)), dim3(64), 0, h->stream, P, (const u64*)h->parted.p, (const u32*)h->tags_b.p,
-                               (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, (u32*)(h->d_small + 6));
+                               (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, h->d_ctr->work.wc);
 #undef LAUNCH_QUERY_FAST
 #undef LAUNCH_QUERY_FAST_ENT
         if (int lrc = launch_check(h, "k_query")) return lrc;
@@ -1320,29 +1349,15 @@ int kmers_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_star
         if ((rc = scan_binned(h, d_packed, d_starts, n_reads, false, &binned, &bl, &n_rec, d_slot_base))) return rc;
         if (binned) return n_rec ? query_records_impl(h, nullptr, nullptr, n_rec, nullptr, &bl, (const u64*)h->anchors.p, d_out, n_slots) : BRISK_HIP_OK;
     }
-    u64 bound = 0;
-    if ((rc = count_kmers(h, d_starts, n_reads, &bound))) return rc;
-    if (bound == 0) return BRISK_HIP_OK;
-    u64 cap = records_estimate(h, bound, n_reads);
-    bool hist_ok = true;
-    for (int attempt = 0;; attempt++) {
-        if ((rc = ensure(h, h->staging, cap * h->P.stride * 8))) return rc;
-        if ((rc = ensure(h, h->tags_a, cap * 4))) return rc;
-        if ((rc = ensure(h, h->anchors, cap * 8))) return rc;
-        rc = scan_impl(h, d_packed, d_starts, n_reads, (u64*)h->staging.p, cap, true, false, (u32*)h->tags_a.p, &n_rec, nullptr, bound, &hist_ok, false,
-                       (u64*)h->anchors.p, d_slot_base);
-        if (rc != BRISK_HIP_ECAPACITY) break;
-        if (attempt) return fail(h, BRISK_HIP_EHIP, "scan overflowed its exact bound");
-        cap = bound;
-    }
-    if (rc) return rc;
+    ScanReq q{ScanMode::Position, d_packed, d_starts, n_reads};
+    q.d_slot_base = d_slot_base;
+    ScanRes res;
+    if ((rc = scan_to_staging(h, q, &res))) return rc;
+    n_rec = res.n_rec;
     if (n_rec == 0) return BRISK_HIP_OK;
     if (n_rec >= (1ull << 32)) return fail(h, BRISK_HIP_EINVAL, "more than 2^32-1 records in one batch: lower max_batch_reads");
-    if (!hist_ok) {  // re-scanned chunks: count the records that are left
-        HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
-        hipLaunchKernelGGL(k_part_hist, dim3(nblocks(n_rec, 256)), dim3(256), 0, h->stream, h->P, (const u64*)h->staging.p, n_rec, h->d_hist);
-        if (int lrc = launch_check(h, "k_part_hist")) return lrc;
-    }
+    // re-scanned chunks: count the records that are left
+    if (!res.hist_valid && (rc = rebuild_hist(h, (const u64*)h->staging.p, n_rec))) return rc;
     hipLaunchKernelGGL(k_iota, dim3(nblocks(n_rec, 256)), dim3(256), 0, h->stream, (u32*)h->tags_a.p, n_rec);
     if ((rc = launch_check(h, "k_iota"))) return rc;
     return query_records_impl(h, (const u64*)h->staging.p, (const u32*)h->tags_a.p, n_rec, nullptr, nullptr, (const u64*)h->anchors.p, d_out, n_slots);
@@ -1747,8 +1762,8 @@ void free_all(brisk_hip_index* h) {
     fr(h->d_cur32);
     fr(h->d_touched);
     fr(h->d_block_sums);
-    fr(h->d_small);
-    if (h->h_small) hipHostFree(h->h_small);
+    fr(h->d_ctr);
+    if (h->h_ctr) hipHostFree(h->h_ctr);
     if (h->h_pin) hipHostFree(h->h_pin);
     for (auto& pe : h->pending) {
         hipEventDestroy(pe.a);
@@ -1962,10 +1977,10 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
         HIPCHK(h, hipMemsetAsync(h->ix.err, 0, 8, h->stream));
         HIPCHK(h, hipMalloc((void**)&h->d_id_counter, 8));
         HIPCHK(h, hipMemsetAsync(h->d_id_counter, 0, 8, h->stream));
-        HIPCHK(h, hipMalloc((void**)&h->d_small, 64));
-        HIPCHK(h, hipHostMalloc((void**)&h->h_small, 64));
+        HIPCHK(h, hipMalloc((void**)&h->d_ctr, sizeof(Counters)));
+        HIPCHK(h, hipHostMalloc((void**)&h->h_ctr, sizeof(PinnedCounters)));
         HIPCHK(h, hipHostMalloc((void**)&h->h_pin, kPinBytes));
-        HIPCHK(h, hipMemsetAsync(h->d_small, 0, 64, h->stream));
+        HIPCHK(h, zero_ctr(h, h->d_ctr));
         {
             // reserve virtual ranges as large as the device's memory; physical pages follow demand
             size_t free_b = 0, total_b = 0;
@@ -2231,10 +2246,10 @@ static int profile_batch(brisk_hip_index* h, const u32* d_packed, const u64* d_s
     const u32 grid_reads = std::max<u32>(std::min<u32>(nblocks(n_reads, 256), 4096), 1);
     hipLaunchKernelGGL(k_profile_count_long, dim3(grid_reads), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, seg, d_ctr);
     if ((rc = launch_check(h, "k_profile_count_long"))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->h_small, d_ctr, 24, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_ctr->prof, d_ctr, 24, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const u64 n_segs = h->h_small[0], n_longs = h->h_small[1];
-    if (h->h_small[2]) return fail(h, BRISK_HIP_EINVAL, "read_profile: a read of more than 2^32-1 slots does not fit the record");
+    const u64 n_segs = h->h_ctr->prof[0], n_longs = h->h_ctr->prof[1];
+    if (h->h_ctr->prof[2]) return fail(h, BRISK_HIP_EINVAL, "read_profile: a read of more than 2^32-1 slots does not fit the record");
     if (n_slots) {
         if ((rc = ensure(h, h->kout_tmp, n_slots * 2))) return rc;
         HIPCHK(h, hipMemsetAsync(h->kout_tmp.p, 0, n_slots * 2, h->stream));
@@ -2615,6 +2630,21 @@ BRISK_API int brisk_hip_count_spectrum(brisk_hip_index* h, uint64_t out[256]) {
     return BRISK_HIP_OK;
 }
 
+// what follows a kernel that removed entries and counted them in result.w[0] (k_prune, k_join)
+static int after_removal(brisk_hip_index* h, uint64_t* removed) {
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->result.w[0]));
+    const u64 n_removed = h->h_ctr->result.w[0];
+    if (n_removed) {  // the directory changed: the enumeration snapshot is stale, and a bucket may have lost its last entry
+        h->dir_snapshot_valid = false;
+        HIPCHK(h, hipMemsetAsync(h->ix.bucket_bits, 0, ((h->n_buckets + 31) / 32) * 4, h->stream));
+        const u64 threads = h->P.shift ? h->n_parts * 64 : h->n_parts;
+        hipLaunchKernelGGL(k_bucket_bits_rebuild, dim3((u32)std::min<u64>(nblocks(threads, 256), 2048)), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts);
+        if (int rc = launch_check(h, "k_bucket_bits_rebuild")) return rc;
+    }
+    if (removed) *removed = n_removed;
+    return check_device_flags(h);
+}
+
 BRISK_API int brisk_hip_prune(brisk_hip_index* h, uint32_t min_count, uint32_t max_count, uint64_t* removed) {
     if (!h) return BRISK_HIP_EINVAL;
     if (min_count > max_count) return fail(h, BRISK_HIP_EINVAL, "prune: min_count > max_count");
@@ -2626,21 +2656,10 @@ BRISK_API int brisk_hip_prune(brisk_hip_index* h, uint32_t min_count, uint32_t m
     // (counts are bytes: a range wholly above 255 keeps nothing -- min 256, max 255 below -- and a bound above 255 is 255)
     const u32 lo = std::min<u32>(min_count, 256u), hi = std::min<u32>(max_count, 255u);
     int rc;
-    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 8, h->stream));
-    hipLaunchKernelGGL(k_prune, dim3((u32)std::min<u64>(nblocks(h->n_parts * 64, 256), 2048)), dim3(256), 0, h->stream, h->ix, (u32)h->n_parts, lo, hi, h->d_small);
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->result.w[0]));
+    hipLaunchKernelGGL(k_prune, dim3((u32)std::min<u64>(nblocks(h->n_parts * 64, 256), 2048)), dim3(256), 0, h->stream, h->ix, (u32)h->n_parts, lo, hi, h->d_ctr->result.w);
     if ((rc = launch_check(h, "k_prune"))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const u64 n_removed = h->h_small[0];
-    if (n_removed) {  // the directory changed: the enumeration snapshot is stale, and a bucket may have lost its last entry
-        h->dir_snapshot_valid = false;
-        HIPCHK(h, hipMemsetAsync(h->ix.bucket_bits, 0, ((h->n_buckets + 31) / 32) * 4, h->stream));
-        const u64 threads = h->P.shift ? h->n_parts * 64 : h->n_parts;
-        hipLaunchKernelGGL(k_bucket_bits_rebuild, dim3((u32)std::min<u64>(nblocks(threads, 256), 2048)), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts);
-        if ((rc = launch_check(h, "k_bucket_bits_rebuild"))) return rc;
-    }
-    if (removed) *removed = n_removed;
-    return check_device_flags(h);
+    return after_removal(h, removed);
 }
 
 BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t* nb_skmers, uint64_t* nb_kmers, uint64_t* memory_bytes,
@@ -2747,14 +2766,14 @@ BRISK_API int brisk_hip_reallocate(brisk_hip_index* from, brisk_hip_index* to) {
                            n_words, (u64*)h->starts_tmp.p);
         if ((rc = launch_check(h, "k_kmers_to_reads"))) return rc;
         // the scan as the query path runs it: its records carry the index of the read they came from (one record per read here)
-        u64 n_rec = 0;
-        bool hist_ok = true;
-        if ((rc = scan_to_staging(h, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, total, true, true, &n_rec, &hist_ok))) return rc;
+        ScanRes res;
+        if ((rc = scan_to_staging(h, {ScanMode::Query, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, total}, &res))) return rc;
+        const u64 n_rec = res.n_rec;
         if (n_rec != total) return fail(h, BRISK_HIP_EHIP, "reallocate: " + std::to_string(total) + " k-mers gave " + std::to_string(n_rec) + " records");
         hipLaunchKernelGGL(k_set_multiplicity, dim3(nblocks(n_rec, 256)), dim3(256), 0, h->stream, (u64*)h->staging.p, n_rec, h->P.stride, (const u32*)h->tags_a.p, d_cnt);
         if ((rc = launch_check(h, "k_set_multiplicity"))) return rc;
         h->fresh = false;  // (records that carry counts: the general route)
-        if ((rc = insert_records_impl(h, (const u64*)h->staging.p, n_rec, hist_ok))) return rc;
+        if ((rc = insert_records_impl(h, (const u64*)h->staging.p, n_rec, res.hist_valid))) return rc;
         p = q;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2817,23 +2836,12 @@ int launch_join(brisk_hip_index* h, brisk_hip_index* src, u32 op, u32 rule, unsi
 #undef LAUNCH_JOIN
     return launch_check(h, "k_join");
 }
-// intersect / subtract: the join, then what brisk_hip_prune does after a removal
+// intersect / subtract: the join, then what follows a removal
 int join_remove(brisk_hip_index* h, brisk_hip_index* src, u32 op, u32 rule, uint64_t* removed) {
     int rc;
-    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 8, h->stream));
-    if ((rc = launch_join(h, src, op, rule, h->d_small))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const u64 n_removed = h->h_small[0];
-    if (n_removed) {  // the directory changed: the enumeration snapshot is stale, and a bucket may have lost its last entry
-        h->dir_snapshot_valid = false;
-        HIPCHK(h, hipMemsetAsync(h->ix.bucket_bits, 0, ((h->n_buckets + 31) / 32) * 4, h->stream));
-        const u64 threads = h->P.shift ? h->n_parts * 64 : h->n_parts;
-        hipLaunchKernelGGL(k_bucket_bits_rebuild, dim3((u32)std::min<u64>(nblocks(threads, 256), 2048)), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts);
-        if ((rc = launch_check(h, "k_bucket_bits_rebuild"))) return rc;
-    }
-    if (removed) *removed = n_removed;
-    return check_device_flags(h);
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->result.w[0]));
+    if ((rc = launch_join(h, src, op, rule, h->d_ctr->result.w))) return rc;
+    return after_removal(h, removed);
 }
 // nb_kmers: the directory reduction of brisk_hip_stats
 int dir_entries(brisk_hip_index* h, u64* out) {
@@ -3121,21 +3129,27 @@ int snap_upload_tables(brisk_hip_index* h, const char* pin, const SnapBlock& bk,
     return BRISK_HIP_OK;
 }
 
+// entries, sum of counts and digest of the index -> h->h_ctr->result, there after the next synchronisation
+int checksum_async(brisk_hip_index* h) {
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->result));
+    hipLaunchKernelGGL(k_checksum, dim3(2048), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts, h->d_ctr->result.w);
+    if (int rc = launch_check(h, "k_checksum")) return rc;
+    HIPCHK(h, fetch_ctr(h, &h->d_ctr->result));
+    return BRISK_HIP_OK;
+}
+
 int save_impl(brisk_hip_index* h, int fd, uint64_t* entries_written) {
     const u32 kw = h->ix.key_words;
     int rc;
     // the digest and the partition sizes of the index as it is now
     u64 ck[3];
-    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 24, h->stream));
-    hipLaunchKernelGGL(k_checksum, dim3(2048), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts, h->d_small);
-    if ((rc = launch_check(h, "k_checksum"))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 24, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = checksum_async(h))) return rc;
     std::vector<u32> cnt(h->n_parts);
     hipLaunchKernelGGL(k_dir_counts, dim3(nblocks(h->n_parts, 256)), dim3(256), 0, h->stream, h->ix.dir, h->n_parts, h->d_cur32);  // (d_cur32: per-batch scratch, free between batches)
     if ((rc = launch_check(h, "k_dir_counts"))) return rc;
     HIPCHK(h, hipMemcpyAsync(cnt.data(), h->d_cur32, h->n_parts * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int i = 0; i < 3; i++) ck[i] = h->h_small[i];
+    for (int i = 0; i < 3; i++) ck[i] = h->h_ctr->result.w[i];
     // blocks of whole partitions: as many as stay within the limit, a larger partition on its own
     u64 limit = kSnapBlockEntries;
     if (const char* e = getenv("BRISK_SNAPSHOT_BLOCK")) {
@@ -3282,8 +3296,8 @@ int load_impl(brisk_hip_index* h, int fd, const brisk_hip_snapshot_info& s, bool
     }
     if (seen != s.n_entries || seen_pairs != s.n_partitions || file_pos != s.file_bytes) return fail(h, BRISK_HIP_EFORMAT, "load: the blocks do not add up to the header's counts");
     // the handle as one that inserted the entries: the bump cursor past the last slice, no private chunk, the bucket bitmap
-    h->h_small[0] = cursor;
-    HIPCHK(h, hipMemcpyAsync(h->ix.cursor, h->h_small, 8, hipMemcpyHostToDevice, h->stream));
+    h->h_ctr->arena_used = cursor;
+    HIPCHK(h, hipMemcpyAsync(h->ix.cursor, &h->h_ctr->arena_used, 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(h->ix.slot_cur, 0, INSERT_SLOTS * 8, h->stream));
     HIPCHK(h, hipMemsetAsync(h->ix.slot_end, 0, INSERT_SLOTS * 8, h->stream));
     h->arena_used_host = cursor;
@@ -3296,14 +3310,10 @@ int load_impl(brisk_hip_index* h, int fd, const brisk_hip_snapshot_info& s, bool
         if ((rc = launch_check(h, "k_bucket_bits_rebuild"))) return rc;
     }
     // verify: the digest of what is now in the index against the header's
-    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 24, h->stream));
-    hipLaunchKernelGGL(k_checksum, dim3(2048), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts, h->d_small);
-    if ((rc = launch_check(h, "k_checksum"))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // (the pinned word the cursor was copied from is free again)
-    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 24, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = checksum_async(h))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < 3; i++)
-        if (h->h_small[i] != s.checksum[i]) return fail(h, BRISK_HIP_EFORMAT, "load: digest mismatch: the entries are not the ones that were saved");
+        if (h->h_ctr->result.w[i] != s.checksum[i]) return fail(h, BRISK_HIP_EFORMAT, "load: digest mismatch: the entries are not the ones that were saved");
     return check_device_flags(h);
 }
 }  // namespace
@@ -3420,15 +3430,9 @@ BRISK_API int brisk_hip_checksum(brisk_hip_index* h, uint64_t out[3]) {
     HIPCHK(h, hipSetDevice(h->device));
     std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
     if (int frc = enter(h)) return frc;
-    HIPCHK(h, hipMemsetAsync(h->d_small, 0, 24, h->stream));
-    hipLaunchKernelGGL(k_checksum, dim3(2048), dim3(256), 0, h->stream, h->P, h->ix, (u32)h->n_parts, h->d_small);
-    int rc;
-    if ((rc = launch_check(h, "k_checksum"))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, 24, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = checksum_async(h)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    out[0] = h->h_small[0];
-    out[1] = h->h_small[1];
-    out[2] = h->h_small[2];
+    for (int i = 0; i < 3; i++) out[i] = h->h_ctr->result.w[i];
     return BRISK_HIP_OK;
 }
 
@@ -3458,26 +3462,20 @@ BRISK_API int brisk_hip_scan_packed(brisk_hip_index* h, const uint32_t* d_packed
         h->scan_hist_valid = true;
         return BRISK_HIP_OK;
     }
-    u64 n = 0;
-    u64 bound = 0;
-    int rc = count_kmers(h, d_starts, n_reads, &bound);
-    if (rc) return rc;
     // the per-partition histogram of what was scanned is kept: the owners of a sharded job need it (export_hist), also
     // when the job happens to have one owner
-    const bool want_hist = true;
-    bool hist_ok = false;
-    h->scan_hist_valid = false;
-    rc = scan_impl(h, d_packed, d_starts, n_reads, d_records, cap_records, want_hist, false, nullptr, &n, nullptr, bound, &hist_ok);
-    *n_records = n;
-    if (rc == BRISK_HIP_OK && want_hist) {
-        if (!hist_ok && n) {  // a long sequence was re-scanned in places: rebuild from the final records
-            HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
-            hipLaunchKernelGGL(k_part_hist, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->P, d_records, n, h->d_hist);
-            if (int lrc = launch_check(h, "k_part_hist")) return lrc;
-        }
-        h->scan_hist_valid = true;
-    }
-    return rc;
+    ScanReq q{ScanMode::Insert, d_packed, d_starts, n_reads, d_records, cap_records};
+    q.with_hist = true;
+    int rc = count_kmers(h, d_starts, n_reads, &q.kmer_bound);
+    if (rc) return rc;
+    ScanRes res;
+    rc = scan_impl(h, q, &res);
+    *n_records = res.n_rec;
+    if (rc) return rc;
+    // a long sequence was re-scanned in places: rebuild from the final records
+    if (!res.hist_valid && res.n_rec && (rc = rebuild_hist(h, d_records, res.n_rec))) return rc;
+    h->scan_hist_valid = true;
+    return BRISK_HIP_OK;
 }
 
 BRISK_API int brisk_hip_export_hist(brisk_hip_index* h, uint64_t* d_hist_out, uint64_t* partitions_per_owner) {
@@ -3537,13 +3535,12 @@ BRISK_API int brisk_hip_insert_records_hist(brisk_hip_index* h, const uint64_t* 
     if (!n_records) return BRISK_HIP_OK;
     const u64 p_lo = owner_first_partition(h, h->P.owner_rank), len = owner_first_partition(h, h->P.owner_rank + 1) - p_lo;
     HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->d_small + 4, 0, 8, h->stream));
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->slice_sum));
     hipLaunchKernelGGL(k_sum_slices, dim3(nblocks(len, 256)), dim3(256), 0, h->stream, (const unsigned long long*)d_hist_slices, n_slices, len, h->d_hist + p_lo,
-                       h->d_small + 4);
+                       &h->d_ctr->slice_sum);
     if (int lrc = launch_check(h, "k_sum_slices")) return lrc;
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 4, h->d_small + 4, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->h_small[4] != n_records) return fail(h, BRISK_HIP_EINVAL, "insert_records_hist: the histogram slices count " + std::to_string(h->h_small[4]) +
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->slice_sum));
+    if (h->h_ctr->slice_sum != n_records) return fail(h, BRISK_HIP_EINVAL, "insert_records_hist: the histogram slices count " + std::to_string(h->h_ctr->slice_sum) +
                                                                         " records, " + std::to_string(n_records) + " were handed over");
     return insert_records_impl(h, d_records, n_records, true);
 }
@@ -3615,11 +3612,13 @@ BRISK_API int brisk_hip_scan_query(brisk_hip_index* h, const uint32_t* d_packed,
     if (int frc = enter(h)) return frc;
     *n_records = 0;
     if (!n_reads) return BRISK_HIP_OK;
-    u64 n = 0, bound = 0;
-    int rc = count_kmers(h, d_starts, n_reads, &bound);
+    ScanReq q{ScanMode::Query, d_packed, d_starts, n_reads, d_records, cap_records};
+    q.d_tags = d_tags;
+    int rc = count_kmers(h, d_starts, n_reads, &q.kmer_bound);
     if (rc) return rc;
-    rc = scan_impl(h, d_packed, d_starts, n_reads, d_records, cap_records, false, true, d_tags, &n, nullptr, bound);
-    *n_records = n;
+    ScanRes res;
+    rc = scan_impl(h, q, &res);
+    *n_records = res.n_rec;
     return rc;
 }
 
@@ -3633,10 +3632,8 @@ BRISK_API int brisk_hip_query_records(brisk_hip_index* h, const uint64_t* d_reco
     int rc;
     if ((rc = ensure(h, h->tags_a, n_records * 4))) return rc;
     HIPCHK(h, hipMemsetAsync(d_sums, 0, n_records * 8, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->d_hist, 0, (h->n_parts + 1) * 8, h->stream));
     hipLaunchKernelGGL(k_iota, dim3(nblocks(n_records, 256)), dim3(256), 0, h->stream, (u32*)h->tags_a.p, n_records);
-    hipLaunchKernelGGL(k_part_hist, dim3(nblocks(n_records, 256)), dim3(256), 0, h->stream, h->P, d_records, n_records, h->d_hist);
-    if ((rc = launch_check(h, "k_part_hist"))) return rc;
+    if ((rc = rebuild_hist(h, d_records, n_records))) return rc;
     if ((rc = query_records_impl(h, d_records, (const u32*)h->tags_a.p, n_records, (unsigned long long*)d_sums))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return check_device_flags(h);
@@ -3670,10 +3667,12 @@ BRISK_API int brisk_hip_scan_sequence(brisk_hip_index* h, const char* bases, uin
         u64* d_lo = d_ret + nk;
         u64* d_hi = d_lo + nk * row;
         uint8_t* d_idx = (uint8_t*)(d_hi + nk * row);
-        u64 n_rec = 0;
-        if ((rc = scan_impl(h, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, 1, (u64*)h->staging.p, nk, false, false, (u32*)h->tags_a.p,
-                            &n_rec, d_ret)))
-            return rc;
+        ScanReq q{ScanMode::Sequence, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, 1, (u64*)h->staging.p, nk};
+        q.d_tags = (u32*)h->tags_a.p;
+        q.d_side = d_ret;
+        ScanRes res;
+        if ((rc = scan_impl(h, q, &res))) return rc;
+        const u64 n_rec = res.n_rec;
         if (!n_rec) return BRISK_HIP_OK;
         hipLaunchKernelGGL(k_expand_records, dim3((u32)n_rec), dim3(64), 0, h->stream, P, (const u64*)h->staging.p, (u32)n_rec, row, d_lo, d_hi, d_idx);
         if ((rc = launch_check(h, "k_expand_records"))) return rc;
@@ -3779,14 +3778,14 @@ BRISK_API int brisk_hip_upsert_kmers(brisk_hip_index* h, const uint64_t* kmer_lo
     if ((rc = upload_queries(h, kmer_lo, kmer_hi, minimizer_idx, n, &d_lo, &d_hi, &d_idx, &d_ids, &d_new))) return rc;
     while (done < n) {
         hipLaunchKernelGGL(k_upsert, dim3(1), dim3(64), 0, h->stream, h->P, h->ix, d_lo + done, d_hi + done, d_idx + done, (u32)(n - done),
-                           d_ids + done, d_new + done, h->d_id_counter, (u32*)(h->d_small + 7));
+                           d_ids + done, d_new + done, h->d_id_counter, &h->d_ctr->upsert_done);
         if ((rc = launch_check(h, "k_upsert"))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->h_small + 7, h->d_small + 7, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->h_small + 5, h->ix.cursor, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, fetch_ctr(h, &h->d_ctr->upsert_done));
+        HIPCHK(h, hipMemcpyAsync(&h->h_ctr->arena_used, h->ix.cursor, 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        const u32 step = (u32)h->h_small[7];
+        const u32 step = h->h_ctr->upsert_done;
         done += step;
-        h->arena_used_host = h->h_small[5];
+        h->arena_used_host = h->h_ctr->arena_used;
         if (done < n) {  // the arena is full: double it and go on with the rest of the vector
             if ((rc = ensure_arena(h, h->arena_cap))) return rc;
         }

@@ -508,7 +508,9 @@ int brisk_hip_set_owner_cuts(brisk_hip_index *h, const uint64_t *first_partition
  * carrying the tags along.  query_records: d_sums[i] = sum of the counts of record i's k-mers present in
  * THIS index (records whose buckets it owns), what Brisk::get_superkmer + the caller's loop add up
  * (brisk/Brisk.hpp:102-118, apps/counter.cpp:296-303).  A sharded get is scan_query -> route_tagged ->
- * all-to-all -> query_records on the owner -> all-to-all back -> per_read[tag] += sum. */
+ * all-to-all -> query_records on the owner -> all-to-all back -> per_read[tag] += sum.
+ * With BRISK_HIP_ECAPACITY, *n_records is an upper bound only: long sequences are scanned in chunks, and the records
+ * of chunks that are cut or scanned again are counted before they are dropped (brisk_hip_scan_bound always suffices). */
 int brisk_hip_scan_query(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
                          uint64_t *d_records, uint32_t *d_tags, uint64_t cap_records, uint64_t *n_records);
 int brisk_hip_route_tagged(brisk_hip_index *h, const uint64_t *d_records, const uint32_t *d_tags, uint64_t n_records,

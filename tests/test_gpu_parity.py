@@ -217,7 +217,10 @@ def test_kernel_variants_match_the_oracle(B):
     for extra in ({"BRISK_BINS": "2", "BRISK_QUERY_ENT": "256"}, {"BRISK_BINS": "64", "BRISK_QUERY_ENT": "128"}, {"BRISK_BINS": "0", "BRISK_DEFER": "0"},
                   {"BRISK_INSERT_GENERIC": "1", "BRISK_QUERY_GENERIC": "1", "BRISK_BINS": "0"},
                   # the workgroup-per-partition insert / query for every partition of more than 24 instances / 8 (0) entries, classic and binned records
-                  {"BRISK_HUGE_AT": "24", "BRISK_BINS": "0", "BRISK_HUGE_QUERY_AT": "8"}, {"BRISK_HUGE_AT": "24", "BRISK_BINS": "2", "BRISK_HUGE_QUERY_AT": "0"}):
+                  {"BRISK_HUGE_AT": "24", "BRISK_BINS": "0", "BRISK_HUGE_QUERY_AT": "8"}, {"BRISK_HUGE_AT": "24", "BRISK_BINS": "2", "BRISK_HUGE_QUERY_AT": "0"},
+                  # the scan's second attempt: the first one holds 8 records, so it overflows and the scan runs again at the exact bound -- into the
+                  # pending records (the two small batches are deferred; their histogram is recounted), and with no bins into staging
+                  {"BRISK_SCAN_CAP0": "8"}, {"BRISK_SCAN_CAP0": "8", "BRISK_BINS": "0"}):
         env = dict(os.environ, **extra)
         p = subprocess.run([sys.executable, worker], env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0 and p.stdout.strip().endswith("ok 12"), (extra, p.stdout[-2000:], p.stderr[-4000:])
@@ -788,6 +791,50 @@ def test_chromosome_length_sequences_are_scanned_in_chunks(B, O):
         ix.insert_records(d_rec.data_ptr(), n_rec)
         st = ix.stats()
         assert (oracle.multiset_lines(*ix.enumerate(), k), st["nb_kmers"], st["nb_buckets"]) == O.count(seqs, k, m, b)
+
+
+@pytest.mark.parametrize("k,m,b", [(63, 21, 14), (31, 11, 11)])
+def test_scan_refuses_a_small_record_buffer_and_the_handle_stays_usable(B, O, k, m, b):
+    """The records API with the caller's capacity: a buffer of 16 records (the random sequence alone gives hundreds) is refused with
+    ECAPACITY, in insert and in query mode, chunked launches and a seeded re-scan (the homopolymer) included; the same handle then
+    scans into a buffer of scan_bound records and gives the oracle's index and the oracle's answers."""
+    import torch
+    rng = random.Random(9)
+    rnd = lambda n: "".join(rng.choice("ACGT") for _ in range(n))
+    seqs = [rnd(8192 + 62 + 2000), "A" * 12_000] + [rnd(300) for _ in range(20)]
+    flat, offs = oracle.pack_reads(seqs)
+    h = O.index_new(k, m, b)
+    O.index_insert_reads(h, flat, offs)
+    want_q = O.index_query_reads(h, flat, offs)
+    O.index_free(h)
+    with B.BriskHip(k, m, b) as ix:
+        W = ix.record_words
+        d_bases = torch.from_numpy(flat).cuda()
+        d_packed = torch.zeros((len(flat) + 15) // 16 + 4, dtype=torch.int32, device="cuda")
+        d_starts = torch.from_numpy(offs.astype(np.int64)).cuda()
+        torch.cuda.synchronize()
+        ix.pack_ascii(d_bases.data_ptr(), len(flat), d_packed.data_ptr())
+        bound = ix.scan_bound(d_starts.data_ptr(), len(seqs))
+        d_rec = torch.zeros(bound * W, dtype=torch.int64, device="cuda")
+        d_tags = torch.zeros(bound, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        with pytest.raises(B.BriskHipError) as e:
+            ix.scan_packed(d_packed.data_ptr(), d_starts.data_ptr(), len(seqs), d_rec.data_ptr(), 16)
+        assert e.value.code == B.hipapi.ECAPACITY
+        n_rec = ix.scan_packed(d_packed.data_ptr(), d_starts.data_ptr(), len(seqs), d_rec.data_ptr(), bound)
+        ix.insert_records(d_rec.data_ptr(), n_rec)
+        st = ix.stats()
+        assert (oracle.multiset_lines(*ix.enumerate(), k), st["nb_kmers"], st["nb_buckets"]) == O.count(seqs, k, m, b)
+        with pytest.raises(B.BriskHipError) as e:
+            ix.scan_query(d_packed.data_ptr(), d_starts.data_ptr(), len(seqs), d_rec.data_ptr(), d_tags.data_ptr(), 16)
+        assert e.value.code == B.hipapi.ECAPACITY
+        nq = ix.scan_query(d_packed.data_ptr(), d_starts.data_ptr(), len(seqs), d_rec.data_ptr(), d_tags.data_ptr(), bound)
+        sums = torch.zeros(max(nq, 1), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        ix.query_records(d_rec.data_ptr(), nq, sums.data_ptr())
+        per_read = torch.zeros(len(seqs), dtype=torch.int64, device="cuda")
+        per_read.index_add_(0, d_tags[:nq].to(torch.int64), sums[:nq])
+        assert np.array_equal(per_read.cpu().numpy().astype(np.uint64), want_q)
 
 
 def test_per_call_api_entry_ids(B, O):

@@ -287,7 +287,8 @@ def test_kernel_variants_match_the_oracle(B):
     reads these settings once per process: one child process each (tests/kmer_query_worker.py)."""
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "kmer_query_worker.py")
     for extra in ({"BRISK_QUERY_GENERIC": "1"}, {"BRISK_BINS": "0"}, {"BRISK_BINS": "2", "BRISK_QUERY_ENT": "256"},
-                  {"BRISK_HUGE_QUERY_AT": "0"}, {"BRISK_HUGE_QUERY_AT": "0", "BRISK_BINS": "2"}, {"BRISK_HUGE_QUERY_AT": "8", "BRISK_BINS": "0"}):
+                  {"BRISK_HUGE_QUERY_AT": "0"}, {"BRISK_HUGE_QUERY_AT": "0", "BRISK_BINS": "2"}, {"BRISK_HUGE_QUERY_AT": "8", "BRISK_BINS": "0"},
+                  {"BRISK_SCAN_CAP0": "8", "BRISK_BINS": "0"}):  # the per-position scan to staging, overflowing at 8 records and run again at the exact bound
         env = dict(os.environ, **extra)
         p = subprocess.run([sys.executable, worker], env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0 and p.stdout.strip().endswith("ok 4"), (extra, p.stdout[-2000:], p.stderr[-4000:])

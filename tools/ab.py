@@ -4,7 +4,7 @@
 Variants live in tests/_v/libbrisk_ab_<NAME>.so (git-ignored, travel with gpurun).  Each is timed in its own process
 (the library is loaded once per process): synthetic reads resident on the device, one warm-up job, then two timed jobs;
 prints the per-kernel HIP-event times of the last job, the index digest (equal digests <=> equal multisets: a variant
-that changes results shows here) and the job's wall time."""
+that changes results shows here), the job's wall time and the launches per profile slot."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 vdir = os.path.join(ROOT, "tests", "_v")
@@ -55,7 +55,8 @@ if "--one" in sys.argv:
         wall = (time.perf_counter() - t0) * 1e3
         prof = ix.profile_read()
     ks = " ".join(f"{n} {v['ms']:.3f}" for n, v in prof.items() if v["launches"] and v["ms"] > 0.05)
-    print(f"{name:14s} wall {wall:8.3f} ms | {ks} | digest {ix.checksum()}", flush=True)
+    ls = " ".join(f"{n} {v['launches']}" for n, v in prof.items() if v["launches"])
+    print(f"{name:14s} wall {wall:8.3f} ms | {ks} | digest {ix.checksum()} | launches {ls}", flush=True)
     sys.exit(0)
 
 if "--run" in sys.argv:
