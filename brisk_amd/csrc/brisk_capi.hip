@@ -74,6 +74,7 @@ struct Counters {
     unsigned long long slice_sum;                  // k_sum_slices: records the histogram slices count
     u32 upsert_done, pad2;                         // k_upsert: k-mers of the vector that are in
     struct Result { unsigned long long w[3]; } result;  // k_prune, k_join: [0] entries removed; k_checksum: entries, sum of counts, digest
+    unsigned long long dbg_guard;                       // k_debug_keys: keys decided by the exact fold (class sum in the guard band)
 };
 static_assert(sizeof(Counters::Scan) == sizeof(unsigned long long) + 2 * sizeof(u32) && sizeof(Counters::Touched) == 2 * sizeof(u32) + sizeof(unsigned long long), "ScanOut; k_touched, k_need");
 static_assert(sizeof(Counters::Kmers) == 2 * sizeof(unsigned long long) && sizeof(Counters::Result) == 3 * sizeof(unsigned long long), "k_count_kmers: out[0..1]; k_checksum: out[0..2]");
@@ -100,6 +101,7 @@ struct brisk_hip_index {
     double* d_coef = nullptr;
     double* d_tabs = nullptr;   // coef[128] + packed fixed-point decycling chunk tables (u64 bits), staged to LDS by k_scan2
     ScanCfg scfg{};
+    u64 dbg_guard_last = 0;     // brisk_hip_debug_order_keys: keys of its last call that took the exact fold (brisk_hip_debug_guard_count)
     bool fresh = true;          // nothing has been inserted since create / clear: every partition is empty (k_insert_first's route).  Whatever may
                                 // put entries into the index clears it: inserts (deferred ones when they complete), merge, reallocate, snapshot load, upserts
     u32 insert_waves = 4096;    // most persistent k_insert waves any instantiation keeps resident (<= INSERT_SLOTS): sizes the arena reserve
@@ -747,7 +749,7 @@ int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
         // instantiations: {k and m compile-time for the common parameter sets (the class tables' layout folds into the
         // instructions), or from P with the chunk count unrolled (6: m 27..29, 4: m 17..19, 3: m 11..15 at CLS_W 5; else a loop)} x mode
 #define LAUNCH_SCAN2(NCH, MODE, KK, MM) \
-    hipLaunchKernelGGL((k_scan2<NCH, MODE, KK, MM>), grid, block, h->scan_lds, h->stream, h->P, h->scfg, d_packed, d_starts, n_items, h->d_tabs, out, cc)
+    hipLaunchKernelGGL((k_scan2<NCH, MODE, KK, MM>), grid, block, h->scan_lds - scan_fixed_tabs(MM) * 8, h->stream, h->P, h->scfg, d_packed, d_starts, n_items, h->d_tabs, out, cc)
 #define LAUNCH_SCAN2_MODES(NCH, KK, MM)                    \
     {                                                      \
         if (pos && cc.vreads) LAUNCH_SCAN2(NCH, 4, KK, MM);  \
@@ -1879,7 +1881,8 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
             // of a chunk in one u64 (layout and decoding: decy_class_fast in brisk_scan.hip).
             // R(x)      = sum_{i=0}^{m-2} coef[4(m-1-i) + nt_i(x)]          (Decycling.cpp:17-24)
             // R(rot(x)) = sum_{i=1}^{m-1} coef[4(m-i)   + nt_i(x)]          (rot: Decycling.cpp:41)
-            // word = a + b * 2^32 as one signed 64-bit integer, a / b = the chunk's share of R / R(rot) in units of 2^-24
+            // word = a + b * 2^32 as one signed 64-bit integer, a / b = the chunk's share of R / R(rot) in units of 2^-24; the entries
+            // of chunk 0 carry a bias of 2^31 in both halves, so that neither sum of an m-mer is ever negative
             ScanCfg& c = h->scfg;
             c.nlow = std::min<u32>(32, k);
             c.nlow1 = std::min<u32>(32, k - 1);
@@ -1901,7 +1904,8 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
                         if (i >= 1) bsum += coef_table[4 * (m - i) + nt];
                     }
                     const int64_t af = llround(std::ldexp(a, 24)), bf = llround(std::ldexp(bsum, 24));
-                    const u64 word = (u64)(af + bf * (int64_t(1) << 32));
+                    u64 word = (u64)af + ((u64)bf << 32);
+                    if (ch == 0) word += ((u64)CLS_BIAS << 32) + CLS_BIAS;  // both sums of an m-mer then carry 2^31 (decy_class_guarded)
                     memcpy(&tabs[128 + base + v], &word, 8);
                 }
             }
@@ -1929,12 +1933,18 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
             static size_t lds_attr = 0;
             if (h->scan_lds > lds_attr) {
                 lds_attr = h->scan_lds;
-#define SCAN2_FNS(NCH, KK, MM) (const void*)k_scan2<NCH, 0, KK, MM>, (const void*)k_scan2<NCH, 1, KK, MM>, (const void*)k_scan2<NCH, 2, KK, MM>, \
-                               (const void*)k_scan2<NCH, 3, KK, MM>, (const void*)k_scan2<NCH, 4, KK, MM>
-                const void* fns[] = {SCAN2_FNS(0, 0, 0), SCAN2_FNS(3, 0, 0), SCAN2_FNS(4, 0, 0), SCAN2_FNS(6, 0, 0), SCAN2_FNS(0, 31, 11), SCAN2_FNS(0, 31, 15), SCAN2_FNS(0, 63, 21),
-                                     (const void*)k_debug_keys};
+                // a function's bound on its dynamic part: what the largest handle needs, and never more than what its static part leaves
+                // (the bodies with a compile-time m hold their tables in a static array: scan_fixed_tabs)
+                struct FnLds { const void* fn; size_t fixed; };
+#define SCAN2_FNS(NCH, KK, MM) FnLds{(const void*)k_scan2<NCH, 0, KK, MM>, scan_fixed_tabs(MM) * 8}, FnLds{(const void*)k_scan2<NCH, 1, KK, MM>, scan_fixed_tabs(MM) * 8}, \
+                               FnLds{(const void*)k_scan2<NCH, 2, KK, MM>, scan_fixed_tabs(MM) * 8}, FnLds{(const void*)k_scan2<NCH, 3, KK, MM>, scan_fixed_tabs(MM) * 8}, \
+                               FnLds{(const void*)k_scan2<NCH, 4, KK, MM>, scan_fixed_tabs(MM) * 8}
+#define DEBUG_FN(NCH, MM) FnLds{(const void*)k_debug_keys<NCH, MM>, scan_fixed_tabs(MM) * 8}
+                const FnLds fns[] = {SCAN2_FNS(0, 0, 0), SCAN2_FNS(3, 0, 0), SCAN2_FNS(4, 0, 0), SCAN2_FNS(6, 0, 0), SCAN2_FNS(0, 31, 11), SCAN2_FNS(0, 31, 15), SCAN2_FNS(0, 63, 21),
+                                     DEBUG_FN(0, 0), DEBUG_FN(3, 0), DEBUG_FN(4, 0), DEBUG_FN(6, 0), DEBUG_FN(0, 11), DEBUG_FN(0, 15), DEBUG_FN(0, 21)};
+#undef DEBUG_FN
 #undef SCAN2_FNS
-                for (const void* fn : fns) HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_attr));
+                for (const FnLds& f : fns) HIPCHK(h, hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min(lds_attr, lds_max - f.fixed)));
             }
             const char* v1 = getenv("BRISK_SCAN_V1");
             h->scan_v1 = v1 && v1[0] == '1';
@@ -3868,10 +3878,30 @@ BRISK_API int brisk_hip_debug_order_keys(brisk_hip_index* h, const uint64_t* mme
     u64* d_k = d_x + n;
     HIPCHK(h, hipMemcpyAsync(d_x, mmers, n * 8, hipMemcpyHostToDevice, h->stream));
     const size_t lds = (size_t)h->scfg.n_tab * 8;
-    hipLaunchKernelGGL(k_debug_keys, dim3(nblocks(n, 256)), dim3(256), lds, h->stream, h->P, h->scfg, h->d_tabs, d_x, n, exact, d_k);
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->dbg_guard));
+    // the body the scan of this geometry runs (launch_scan's dispatch)
+#define LAUNCH_DEBUG_KEYS(NCH, MM) \
+    hipLaunchKernelGGL((k_debug_keys<NCH, MM>), dim3(nblocks(n, 256)), dim3(256), lds - scan_fixed_tabs(MM) * 8, h->stream, h->P, h->scfg, h->d_tabs, d_x, n, exact, d_k, &h->d_ctr->dbg_guard)
+    const u32 k = h->P.k, m = h->P.m;
+    if (k == 63 && m == 21) LAUNCH_DEBUG_KEYS(0, 21);
+    else if (k == 31 && m == 15) LAUNCH_DEBUG_KEYS(0, 15);
+    else if (k == 31 && m == 11) LAUNCH_DEBUG_KEYS(0, 11);
+    else if (h->scfg.nch == 6) LAUNCH_DEBUG_KEYS(6, 0);
+    else if (h->scfg.nch == 4) LAUNCH_DEBUG_KEYS(4, 0);
+    else if (h->scfg.nch == 3) LAUNCH_DEBUG_KEYS(3, 0);
+    else LAUNCH_DEBUG_KEYS(0, 0);
+#undef LAUNCH_DEBUG_KEYS
     if ((rc = launch_check(h, "k_debug_keys"))) return rc;
     HIPCHK(h, hipMemcpyAsync(keys, d_k, n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->dbg_guard));
+    h->dbg_guard_last = h->h_ctr->dbg_guard;
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_debug_guard_count(brisk_hip_index* h, uint64_t* n_guard) {
+    if (!h || !n_guard) return BRISK_HIP_EINVAL;
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    *n_guard = h->dbg_guard_last;
     return BRISK_HIP_OK;
 }
 

@@ -480,15 +480,35 @@ struct ScanCfg {
 // reference's order (decy_class).  Host side: brisk_hip_create in brisk_capi.hip.
 #define CLS_HI 21
 #define CLS_LO 12
+// bias of both class sums: the host adds it to both halves of every chunk-0 entry (brisk_hip_create), decy_class_guarded decodes with it
+#define CLS_BIAS 0x80000000u
 // NCH > 0: compile-time chunk count (unrolled look-ups); MM > 0: compile-time m, the whole layout folds into the instructions
+// doubles of LDS at a fixed address (a static array: the kernel's LDS begins with it) in the bodies with a compile-time m: coef[128] and
+// the chunk tables.  The byte offsets of cls_sums then meet table bases that are constants, and the base goes into the read's offset
+// field; behind the dynamic array's address -- a symbol until the code object is laid out -- every look-up kept an add of 0.  The
+// dynamic part of these bodies' LDS is the rest (host: launch_scan in brisk_capi.hip).  0: everything in the dynamic array.
+__host__ __device__ constexpr u32 scan_fixed_tabs(int MM) { return MM > 0 ? 128 + cls_base((u32)MM, cls_nch((u32)MM)) : 0u; }
 template <int NCH, int MM>
 __device__ __forceinline__ u64 cls_sums(u64 x, const ScanCfg& cfg, const u64* tabs) {
     u64 acc;
     if (MM > 0) {
+        // The chunk value is never formed: each chunk is extracted already multiplied by 8, as the byte offset into its table
+        // ((x >> (2 off - 3)) & (mask << 3): one funnel shift or shift, one and), and the table's own base is a constant that goes
+        // into the offset field of the ds_read_b64.  Nothing is left of the index-to-address shift-and-add per look-up.
         constexpr u32 mm = MM > 0 ? (u32)MM : 1u;
-        acc = tabs[(u32)x & ((1u << (2 * cls_width(mm, 0))) - 1)];
+        const char* tb = (const char*)tabs;
+        const u32 xl = (u32)x, xh = (u32)(x >> 32);
+        acc = *(const u64*)(tb + ((xl << 3) & (((1u << (2 * cls_width(mm, 0))) - 1) << 3)));
 #pragma unroll
-        for (u32 c = 1; c < cls_nch(mm); c++) acc += tabs[cls_base(mm, c) + ((u32)(x >> (2 * cls_off(mm, c))) & ((1u << (2 * cls_width(mm, c))) - 1))];
+        for (u32 c = 1; c < cls_nch(mm); c++) {
+            const u32 lo = 2 * cls_off(mm, c), wd = 2 * cls_width(mm, c), mk = ((1u << wd) - 1) << 3;  // lo >= 6: the first chunk has 3 nts or more
+            u32 bo;
+            if (lo + wd <= 32) bo = xl >> (lo - 3);
+            else if (lo >= 35) bo = xh >> (lo - 35);
+            else if (lo >= 32) bo = xh << (35 - lo);
+            else bo = (u32)(x >> (lo - 3));
+            acc += *(const u64*)(tb + 8 * cls_base(mm, c) + (bo & mk));
+        }
     } else if (NCH > 0) {
         acc = tabs[(u32)x & ((1u << ((cfg.chunk[0] >> 6) & 15)) - 1)];
 #pragma unroll
@@ -511,17 +531,26 @@ __device__ __forceinline__ u64 cls_sums(u64 x, const ScanCfg& cfg, const u64* ta
 template <int NCH, int MM>
 __device__ __forceinline__ u32 decy_class_guarded(u64 x, const ScanCfg& cfg, const u64* tabs, bool& guard) {
     const u64 acc = cls_sums<NCH, MM>(x, cfg, tabs);
-    const int a = (int)(u32)acc, b = (int)(u32)(acc >> 32) - (a >> 31);
-    const u32 ua = (u32)(a < 0 ? -a : a), ub = (u32)(b < 0 ? -b : b);
-    guard = guard | (ua - (CLS_LO + 1) <= (u32)(CLS_HI - CLS_LO - 2)) | (ub - (CLS_LO + 1) <= (u32)(CLS_HI - CLS_LO - 2));
+    // The host has added 2^31 to both halves of every chunk-0 entry: the low word is A + 2^31 and never negative as a part of the
+    // 64-bit sum (|A| < 2^31), so the high word is B + 2^31 with nothing borrowed.  |A| - (CLS_LO + 1) is one sum-of-absolute-
+    // differences against the bias; the band test of both sums is one minimum and one compare; the class compares are unsigned.
+    // Unit, thresholds and band are those of the argument above: an exact 0 (2^31 here) is CLS_LO + 1 away from the band.
+    // (The absolute difference as maximum minus minimum: that form reaches the instruction selector whole and becomes one v_sad_u32
+    // with the -(CLS_LO + 1) as its addend; written as a select of the two differences the compiler folds the constant into them first
+    // and ends with 18 instructions for these 10.  Inline assembly would do too, but is a convergent call to the loop unroller: the
+    // (k-1)-mer's pass then stays rolled.)
+    const u32 a = (u32)acc, b = (u32)(acc >> 32);
+    const u32 da = ((a > CLS_BIAS ? a : CLS_BIAS) - (a < CLS_BIAS ? a : CLS_BIAS)) + (0u - (CLS_LO + 1));
+    const u32 db = ((b > CLS_BIAS ? b : CLS_BIAS) - (b < CLS_BIAS ? b : CLS_BIAS)) + (0u - (CLS_LO + 1));
+    guard = guard | ((da < db ? da : db) <= (u32)(CLS_HI - CLS_LO - 2));
+    const bool c0 = a >= CLS_BIAS + CLS_HI && b <= CLS_BIAS + CLS_LO, c1 = a <= CLS_BIAS - CLS_HI && b >= CLS_BIAS - CLS_LO;
 #ifdef CLS_FORCE_GUARD  // test builds: every pass is repeated with the exact fold (the path a guard-band sum takes once in a blue moon)
     guard = true;
 #endif
-    const bool c0 = a >= CLS_HI && b <= CLS_LO, c1 = a <= -CLS_HI && b >= -CLS_LO;
     return c0 ? 0u : c1 ? 1u : 2u;
 }
 template <int NCH, int MM>
-__device__ __forceinline__ u32 decy_class_fast(u64 x, u32 m, const ScanCfg& cfg, const u64* tabs, const double* coef) {
+__device__ __forceinline__ u32 decy_class_fast(u64 x, u32 m, const ScanCfg& cfg, const u64* tabs, const double* coef, bool* took_guard = nullptr) {
 #ifdef SCAN_ATTR_NOCLASS  // attribution builds (tools/scan_attribution.py): wrong results, timing only
     return (u32)x & 1u;
 #endif
@@ -530,24 +559,37 @@ __device__ __forceinline__ u32 decy_class_fast(u64 x, u32 m, const ScanCfg& cfg,
     if (__ballot(guard)) {  // wave-uniform and practically never taken: no lane-level branch on the way of the others
         if (guard) cls = decy_class(x, m, coef);
     }
+    if (took_guard) *took_guard = guard;  // (k_debug_keys counts them)
     return cls;
 }
 template <int NCH = 0, int MM = 0>
-__device__ __forceinline__ u64 order_key_fast(u64 x, u32 m, u64 M, const ScanCfg& cfg, const u64* tabs, const double* coef) {
+__device__ __forceinline__ u64 order_key_fast(u64 x, u32 m, u64 M, const ScanCfg& cfg, const u64* tabs, const double* coef, bool* took_guard = nullptr) {
 #ifdef SCAN_ATTR_NOMIX
     return ((u64)decy_class_fast<NCH, MM>(x, m, cfg, tabs, coef) << 62) + (x ^ (x >> 7));
 #endif
-    return ((u64)decy_class_fast<NCH, MM>(x, m, cfg, tabs, coef) << 62) + mix2m(x, M);
+    return ((u64)decy_class_fast<NCH, MM>(x, m, cfg, tabs, coef, took_guard) << 62) + mix2m(x, M);
 }
 
+// The order keys of n m-mers, through the same order_key_fast<NCH, MM> the scan of this geometry runs (the host dispatches on (k, m) like
+// launch_scan); n_guard += the keys whose class sums lay in the guard band and were decided by the exact fold.
+template <int NCH, int MM>
 __global__ void __launch_bounds__(256) k_debug_keys(BriskParams P, ScanCfg cfg, const double* __restrict__ g_tabs, const u64* __restrict__ x, u64 n,
-                                                    int exact, u64* __restrict__ out) {
-    extern __shared__ double smem_d[];
+                                                    int exact, u64* __restrict__ out, unsigned long long* __restrict__ n_guard) {
+    extern __shared__ double smem_dyn[];
+    double* smem_d = smem_dyn;
+    if constexpr (scan_fixed_tabs(MM) > 0) {  // as in k_scan2
+        __shared__ double s_fix[scan_fixed_tabs(MM)];
+        smem_d = s_fix;
+    }
     for (u32 i = threadIdx.x; i < cfg.n_tab; i += blockDim.x) smem_d[i] = g_tabs[i];
     __syncthreads();
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = exact ? order_key(x[i], P.m, P.m_mask, smem_d) : order_key_fast(x[i], P.m, P.m_mask, cfg, (const u64*)(smem_d + 128), smem_d);
+    const u32 m = MM ? (u32)MM : P.m;
+    const u64 M = MM ? ((1ull << (2 * MM)) - 1) : P.m_mask;
+    bool g = false;
+    if (i < n) out[i] = exact ? order_key(x[i], m, M, smem_d) : order_key_fast<NCH, MM>(x[i], m, M, cfg, (const u64*)(smem_d + 128), smem_d, &g);
+    const unsigned long long gb = __ballot(g);
+    if ((threadIdx.x & 63) == 0 && gb) atomicAdd(n_guard, (unsigned long long)__popcll(gb));
 }
 
 // value of a wave-uniform lane, through SGPRs
@@ -1023,15 +1065,22 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
                                                 u64 n_reads, const double* __restrict__ g_tabs, ScanOut out, ChunkCtl cc) {
     constexpr bool VR = MODE == 2 || MODE == 4, query_mode = MODE == 1, POS = MODE >= 3;
     constexpr bool CLS = MM < 12;  // minimizer_idx classes in the routing id exist only where 2m < 24 (brisk_hip_create)
-    extern __shared__ double smem_d[];
-    const double* s_coef = smem_d;                        // 128
-    const u64* s_tabs = (const u64*)(smem_d + 128);       // the packed fixed-point chunk tables
+    extern __shared__ double smem_dyn[];
     const u32 tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const u32 n_tab = MM ? 128 + cls_base(MM ? MM : 1, cls_nch(MM ? MM : 1)) : cfg.n_tab;
+    double* smem_d = smem_dyn;         // coef[128], the chunk tables ...
+    double* smem_q = smem_dyn + n_tab; // ... and behind them what the waves write
+    if constexpr (scan_fixed_tabs(MM) > 0) {  // the tables at a fixed address, the dynamic array for the rest
+        __shared__ double s_fix[scan_fixed_tabs(MM)];
+        smem_d = s_fix;
+        smem_q = smem_dyn;
+    }
+    const double* s_coef = smem_d;                        // 128
+    const u64* s_tabs = (const u64*)(smem_d + 128);       // the packed fixed-point chunk tables
     for (u32 i = tid; i < n_tab; i += blockDim.x) smem_d[i] = g_tabs[i];
-    unsigned long long* s_wbase = (unsigned long long*)(smem_d + n_tab);      // block's slot base at the final flush
+    unsigned long long* s_wbase = (unsigned long long*)smem_q;                 // block's slot base at the final flush
     u32* s_wcnt = (u32*)(s_wbase + 1);                                         // [16] records left per wave
-    u64* q_ent = (u64*)(smem_d + n_tab + 9) + (size_t)wid * (cfg.qcap + 96);   // [qcap] the wave's emit queue
+    u64* q_ent = (u64*)(smem_q + 9) + (size_t)wid * (cfg.qcap + 96);           // [qcap] the wave's emit queue
     u64* s_q0 = q_ent + cfg.qcap;                  // [64] stream index of every lane's first nt
     u32* s_tag = (u32*)(s_q0 + 64);                // [64] every lane's tag (read index, or chunk slot)
 

@@ -112,7 +112,7 @@ SYMBOLS = [
     "brisk_hip_abi_version", "brisk_hip_create", "brisk_hip_destroy", "brisk_hip_clear", "brisk_hip_last_error", "brisk_hip_sync",
     "brisk_hip_get_layout", "brisk_hip_insert_reads", "brisk_hip_insert_packed", "brisk_hip_get_reads", "brisk_hip_lookup",
     "brisk_hip_enumerate", "brisk_hip_stats", "brisk_hip_memory_info", "brisk_hip_insert_slack", "brisk_hip_reallocate", "brisk_hip_checksum", "brisk_hip_scan_packed", "brisk_hip_scan_bound", "brisk_hip_route_records",
-    "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
+    "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_debug_guard_count", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
     "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune",
     "brisk_hip_read_profile_reads", "brisk_hip_read_profile_packed",
     "brisk_hip_select_intervals", "brisk_hip_extract_packed", "brisk_hip_trim_packed", "brisk_hip_trim_reads", "brisk_hip_unpack_ascii",
@@ -761,6 +761,13 @@ class BriskHip:
         out = np.zeros(max(len(x), 1), np.uint64)
         self._chk(self.L.brisk_hip_debug_order_keys(self.h, x, len(x), 1 if exact else 0, out))
         return out[: len(x)]
+
+    def debug_guard_count(self) -> int:
+        """Keys of the last debug_order_keys call whose class sums lay in the guard band (decided by the exact fold)."""
+        n = C.c_uint64(0)
+        self.L.brisk_hip_debug_guard_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]  # (bound on use: a test hook, not part of load())
+        self._chk(self.L.brisk_hip_debug_guard_count(self.h, C.byref(n)))
+        return int(n.value)
 
     # ---- measurement
     def profile_enable(self, on: bool = True):

@@ -97,6 +97,7 @@
  *   brisk_hip_synth_reads       no reference counterpart (benchmark input,
  *                               SURVEY.md 8(d))
  *   brisk_hip_debug_order_keys  bfc_hash_64 + DecyclingSet::memDouble in bulk
+ *   brisk_hip_debug_guard_count how many of them the exact fold decided
  *                               (brisk/hashing.cpp:8-19, brisk/Decycling.cpp:38-52); test hook
  */
 #ifndef BRISK_HIP_H
@@ -551,6 +552,11 @@ int brisk_hip_synth_reads(brisk_hip_index *h, uint64_t genome_len, uint64_t firs
  * code path the scan uses (table-driven class with guard band when exact == 0, the
  * plain FP64 fold when exact != 0).  HOST arrays. */
 int brisk_hip_debug_order_keys(brisk_hip_index *h, const uint64_t *mmers, uint64_t n, int exact, uint64_t *keys);
+/* The fast path runs the body the scan of the handle's geometry runs: where (k, m) has a scan with k and m as compile-time
+ * constants (63,21; 31,15; 31,11) that body's order key, else the run-time layout with the scan's chunk-count unrolling.
+ * brisk_hip_debug_guard_count: how many keys of the handle's LAST brisk_hip_debug_order_keys call had a class sum inside the
+ * guard band and were decided by the exact FP64 fold (0 after an exact != 0 call; all of them in a -DCLS_FORCE_GUARD build). */
+int brisk_hip_debug_guard_count(brisk_hip_index *h, uint64_t *n_guard);
 
 /* ---- measurement ----------------------------------------------------------- */
 /* With profiling on, every kernel launch is bracketed by HIP events on the

@@ -36,7 +36,11 @@ if "--one" in sys.argv:
     sys.path.insert(0, ROOT)
     import time
     import torch
+    import ctypes
     import brisk_amd
+    from brisk_amd import hipapi
+    L = ctypes.CDLL(lib(name))  # a library built from older sources (the parent's, as a base) lacks the test hooks added since
+    hipapi.SYMBOLS[:] = [s for s in hipapi.SYMBOLS if hasattr(L, s)]
     dev = torch.device("cuda", 0)
     d_packed = torch.zeros((reads * 150 + 15) // 16 + 4, dtype=torch.int32, device=dev)
     d_starts = torch.zeros(reads + 1, dtype=torch.int64, device=dev)
