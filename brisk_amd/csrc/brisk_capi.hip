@@ -84,6 +84,7 @@ struct PinnedCounters : Counters {  // host only; pinned because copies land in 
     unsigned long long arena_used;  // copy of ix.cursor (on load: the cursor to upload)
     unsigned long long n_rec_new;   // the record count compact_chunks uploads to scan.n_rec
     unsigned long long prof[3];     // k_profile_count_long's counters, from prof_plan
+    unsigned long long answers;     // the last word of a brisk_hip_record_kmers table: the answers of its records
 };
 
 }  // namespace
@@ -137,6 +138,7 @@ struct brisk_hip_index {
     DevBuf packed_tmp2, starts_tmp2;  // the second set of insert_reads_pipelined: one sub-batch is scanned while the next one arrives
     DevBuf anchors, slot_buf, kout_tmp;  // per-position mode (brisk_hip_get_kmers): records' slot anchors, the batch's slot bases, host-call output
     DevBuf prof_out, prof_plan;          // brisk_hip_read_profile_*: a host call's records; counters, long-read and segment lists, partials
+    DevBuf reck_buf;                     // brisk_hip_record_kmers: block sums
     DevBuf ext_iv, ext_tmp, ext_src;     // brisk_hip_extract_packed / _trim_*: a call's intervals; flags and block sums; the kept reads' source positions
     u32* d_ovf_cnt = nullptr;              // OVF_REGIONS counters of the binned scan's overflow area
     std::vector<u64> owner_cut;            // sharded index: owner o holds partitions [owner_cut[o], owner_cut[o + 1]) (n_owners + 1 entries)
@@ -1331,19 +1333,25 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
     return launch_check(h, "k_query_huge");
 }
 
-// Per-position query of one batch (brisk_hip_get_kmers): d_out[base_r + i] = 0x100 | count of the k-mer at nucleotide i of read r
-// when present; d_out (the batch's slots, base_0 = 0) zeroed by the caller.  The scan runs as for an insert (every k-mer, no query
-// stop) and gives every record the slot of its minimizer (pos_anchor); the probe kernels then write each k-mer's answer to its slot.
-int kmers_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, uint16_t* d_out, u64 n_slots) {
-    int rc;
+// slot_buf <- the slot bases of a batch's reads (k_slot_apply: slot_base[r] = base_r - starts[r]), the block sums behind them
+int slot_bases(brisk_hip_index* h, const u64* d_starts, u64 n_reads) {
     const u32 nb = nblocks(n_reads, 256 * SLOT_ITEMS);
-    if ((rc = ensure(h, h->slot_buf, (n_reads + nb + 1) * 8))) return rc;
+    if (int rc = ensure(h, h->slot_buf, (n_reads + nb + 1) * 8)) return rc;
     u64* d_slot_base = (u64*)h->slot_buf.p;
     u64* d_bsum = d_slot_base + n_reads;
     hipLaunchKernelGGL(k_slot_block, dim3(nb), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, d_bsum);
     hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bsum, nb);
     hipLaunchKernelGGL(k_slot_apply, dim3(nb), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, (const u64*)d_bsum, d_slot_base);
-    if ((rc = launch_check(h, "k_slot_block/top/apply"))) return rc;
+    return launch_check(h, "k_slot_block/top/apply");
+}
+
+// Per-position query of one batch (brisk_hip_get_kmers): d_out[base_r + i] = 0x100 | count of the k-mer at nucleotide i of read r
+// when present; d_out (the batch's slots, base_0 = 0) zeroed by the caller.  The scan runs as for an insert (every k-mer, no query
+// stop) and gives every record the slot of its minimizer (pos_anchor); the probe kernels then write each k-mer's answer to its slot.
+int kmers_packed_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, uint16_t* d_out, u64 n_slots) {
+    int rc;
+    if ((rc = slot_bases(h, d_starts, n_reads))) return rc;
+    u64* d_slot_base = (u64*)h->slot_buf.p;
     u64 n_rec = 0;
     {  // the scan bins the records, their own indices as tags and their anchors alongside
         BinLayout bl{};
@@ -1737,7 +1745,7 @@ void free_all(brisk_hip_index* h) {
     hipStreamSynchronize(h->stream);  // nothing of ours may be in flight when the arena is unmapped
     auto fr = [](void* p) { if (p) hipFree(p); };
     for (DevBuf* b : {&h->huge, &h->left, &h->pend, &h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp, &h->enum_out,
-                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->ext_iv, &h->ext_tmp, &h->ext_src})
+                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src})
         fr(b->p);
     fr(h->d_coef);
     fr(h->d_tabs);
@@ -2246,7 +2254,9 @@ struct BatchLimit {  // the handle's lock is held
 
 // One batch: its slots into kout_tmp (zeroed; kmers_packed_impl exactly as brisk_hip_get_kmers runs it), then one record per read into
 // d_out[0 .. n_reads).  n_slots: the batch's slots (count_kmers / host_slots).
-static int profile_batch(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u64 n_slots, u32 solid_min, ReadProfile* d_out) {
+// caller_slots (brisk_hip_profile_slots): the batch's slots are ext_slots, as the caller holds them; nothing is looked up, only the slot bases are made.
+static int profile_batch(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u64 n_slots, u32 solid_min, ReadProfile* d_out,
+                         bool caller_slots = false, const uint16_t* ext_slots = nullptr) {
     int rc;
     const u32 seg = profile_seg();
     // what the table holds: reads that need segments, and a read too long for the record's 32-bit fields
@@ -2260,14 +2270,16 @@ static int profile_batch(brisk_hip_index* h, const u32* d_packed, const u64* d_s
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const u64 n_segs = h->h_ctr->prof[0], n_longs = h->h_ctr->prof[1];
     if (h->h_ctr->prof[2]) return fail(h, BRISK_HIP_EINVAL, "read_profile: a read of more than 2^32-1 slots does not fit the record");
-    if (n_slots) {
+    if (caller_slots) {
+        if ((rc = slot_bases(h, d_starts, n_reads))) return rc;
+    } else if (n_slots) {
         if ((rc = ensure(h, h->kout_tmp, n_slots * 2))) return rc;
         HIPCHK(h, hipMemsetAsync(h->kout_tmp.p, 0, n_slots * 2, h->stream));
         if ((rc = kmers_packed_impl(h, d_packed, d_starts, n_reads, (uint16_t*)h->kout_tmp.p, n_slots))) return rc;
     } else {  // nothing to look up; the records still need the table's slot bases (all zero slots: never read)
         if ((rc = ensure(h, h->slot_buf, (n_reads + 1) * 8))) return rc;
     }
-    const uint16_t* d_slots = (const uint16_t*)h->kout_tmp.p;
+    const uint16_t* d_slots = caller_slots ? ext_slots : (const uint16_t*)h->kout_tmp.p;
     const u64* d_slot_base = (const u64*)h->slot_buf.p;
     {
         ProfScope ps(h, S_PROFILE);
@@ -2702,7 +2714,7 @@ BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t
     if (memory_bytes) {
         u64 m = h->arena_cap * (8ull * h->ix.key_words + 1) + h->n_parts * 16 + (h->n_buckets + 7) / 8 + (h->n_parts + 1) * 20;
         for (const DevBuf* b : {&h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp,
-                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->ext_iv, &h->ext_tmp, &h->ext_src})
+                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src})
             m += b->bytes;
         *memory_bytes = m;
     }
@@ -3647,6 +3659,144 @@ BRISK_API int brisk_hip_query_records(brisk_hip_index* h, const uint64_t* d_reco
     if ((rc = query_records_impl(h, d_records, (const u32*)h->tags_a.p, n_records, (unsigned long long*)d_sums))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return check_device_flags(h);
+}
+
+// ---- the per-position get cut at the same boundary (kernels: brisk_answers.hip) ----
+// scan_kmers -> route_tagged -> all-to-all -> record_kmers + answer_records on the owner -> all-to-all back -> record_kmers + place_answers
+BRISK_API int brisk_hip_scan_kmers(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint64_t* d_records, uint32_t* d_tags,
+                                   uint64_t* d_anchors, uint64_t cap_records, uint64_t* n_records, uint64_t* n_slots) {
+    if (!h || !n_records || !n_slots || (n_reads && (!d_packed || !d_starts)) || (cap_records && (!d_records || !d_tags || !d_anchors))) return BRISK_HIP_EINVAL;
+    if (n_reads >= (1ull << 32)) return fail(h, BRISK_HIP_EINVAL, "more than 2^32-1 reads in one query batch");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    *n_records = *n_slots = 0;
+    if (!n_reads) return BRISK_HIP_OK;
+    ScanReq q{ScanMode::Position, d_packed, d_starts, n_reads, d_records, cap_records};
+    q.d_tags = d_tags;
+    q.d_side = d_anchors;
+    int rc = count_kmers(h, d_starts, n_reads, &q.kmer_bound);
+    if (rc) return rc;
+    *n_slots = q.kmer_bound;
+    if (!q.kmer_bound) return BRISK_HIP_OK;
+    if ((rc = slot_bases(h, d_starts, n_reads))) return rc;
+    q.d_slot_base = (const u64*)h->slot_buf.p;
+    ScanRes res;
+    rc = scan_impl(h, q, &res);
+    *n_records = res.n_rec;
+    if (rc) return rc;
+    if (res.n_rec >= (1ull << 32)) return fail(h, BRISK_HIP_EINVAL, "more than 2^32-1 records in one batch");
+    if (res.n_rec) {  // the scan leaves chunk numbers in the tags of long sequences' records: record i's anchor is d_anchors[i]
+        hipLaunchKernelGGL(k_iota, dim3(nblocks(res.n_rec, 256)), dim3(256), 0, h->stream, d_tags, res.n_rec);
+        if ((rc = launch_check(h, "k_iota"))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// the lock is held: d_offsets[0 .. n_records] <- the exclusive prefix sum of the records' k-mer counts, queued on the stream
+static int record_kmers_impl(brisk_hip_index* h, const uint64_t* d_records, uint64_t n_records, uint64_t* d_offsets) {
+    if (!n_records) {
+        HIPCHK(h, hipMemsetAsync(d_offsets, 0, 8, h->stream));
+        return BRISK_HIP_OK;
+    }
+    const u32 nb = nblocks(n_records, 256 * RECK_ITEMS);
+    if (int rc = ensure(h, h->reck_buf, ((size_t)nb + 1) * 8)) return rc;
+    u64* d_bsum = (u64*)h->reck_buf.p;
+    hipLaunchKernelGGL(k_reck_block, dim3(nb), dim3(256), 0, h->stream, h->P, d_records, n_records, d_bsum);
+    hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bsum, nb);
+    hipLaunchKernelGGL(k_reck_apply, dim3(nb), dim3(256), 0, h->stream, h->P, d_records, n_records, (const u64*)d_bsum, d_offsets);
+    return launch_check(h, "k_reck_block/top/apply");
+}
+
+BRISK_API int brisk_hip_record_kmers(brisk_hip_index* h, const uint64_t* d_records, uint64_t n_records, uint64_t* d_offsets) {
+    if (!h || !d_offsets || (n_records && !d_records)) return BRISK_HIP_EINVAL;
+    if (n_records >= (1ull << 32)) return fail(h, BRISK_HIP_EINVAL, "more than 2^32-1 records in one batch");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    if (int rc = record_kmers_impl(h, d_records, n_records, d_offsets)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// the total behind a record_kmers table: d_offsets[n_records], on the host
+static int fetch_total(brisk_hip_index* h, const uint64_t* d_offsets, uint64_t n_records, u64* total) {
+    HIPCHK(h, hipMemcpyAsync(&h->h_ctr->answers, d_offsets + n_records, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *total = h->h_ctr->answers;
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_answer_records(brisk_hip_index* h, const uint64_t* d_records, uint64_t n_records, const uint64_t* d_offsets, uint16_t* d_answers) {
+    if (!h || (n_records && (!d_records || !d_offsets))) return BRISK_HIP_EINVAL;
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "answer_records on an entry-id index: DATA lives with the caller (find_kmers)");
+    if (n_records >= (1ull << 32)) return fail(h, BRISK_HIP_EINVAL, "more than 2^32-1 records in one batch");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    if (!n_records) return BRISK_HIP_OK;
+    int rc;
+    u64 total = 0;
+    if ((rc = fetch_total(h, d_offsets, n_records, &total))) return rc;
+    if (!total) return BRISK_HIP_OK;
+    if (!d_answers) return BRISK_HIP_EINVAL;
+    if ((rc = ensure(h, h->tags_a, n_records * 4))) return rc;
+    if ((rc = ensure(h, h->anchors, n_records * 8))) return rc;
+    HIPCHK(h, hipMemsetAsync(d_answers, 0, total * 2, h->stream));
+    hipLaunchKernelGGL(k_iota, dim3(nblocks(n_records, 256)), dim3(256), 0, h->stream, (u32*)h->tags_a.p, n_records);
+    // anchors that make pos_slot0 / pos_slot land k-mer j of record i at d_offsets[i] + j: the POS kernels run as they are
+    hipLaunchKernelGGL(k_answer_anchors, dim3(nblocks(n_records, 256)), dim3(256), 0, h->stream, h->P, d_records, n_records, d_offsets, (u64*)h->anchors.p);
+    if ((rc = launch_check(h, "k_iota / k_answer_anchors"))) return rc;
+    if ((rc = rebuild_hist(h, d_records, n_records))) return rc;
+    if ((rc = query_records_impl(h, d_records, (const u32*)h->tags_a.p, n_records, nullptr, nullptr, (const u64*)h->anchors.p, d_answers, total))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return check_device_flags(h);
+}
+
+BRISK_API int brisk_hip_place_answers(brisk_hip_index* h, const uint64_t* d_records, const uint32_t* d_tags, const uint64_t* d_anchors, uint64_t n_records,
+                                      const uint64_t* d_offsets, const uint16_t* d_answers, uint16_t* d_slots, uint64_t n_slots) {
+    if (!h || (n_records && (!d_records || !d_tags || !d_anchors || !d_offsets))) return BRISK_HIP_EINVAL;
+    if (n_records >= (1ull << 32)) return fail(h, BRISK_HIP_EINVAL, "more than 2^32-1 records in one batch");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    if (!n_records) return BRISK_HIP_OK;
+    int rc;
+    u64 total = 0;
+    if ((rc = fetch_total(h, d_offsets, n_records, &total))) return rc;
+    if (!total) return BRISK_HIP_OK;
+    if (!d_answers || !d_slots) return BRISK_HIP_EINVAL;
+    const u32 grid = (u32)std::min<u64>((n_records + 255) / 256, 8192);  // a wave per 64 records, grid-stride
+    hipLaunchKernelGGL(k_place_answers, dim3(grid), dim3(256), 0, h->stream, h->P, d_records, d_tags, d_anchors, n_records, d_offsets, d_answers, d_slots, n_slots, h->ix.err);
+    if ((rc = launch_check(h, "k_place_answers"))) return rc;
+    u32 e = 0;
+    HIPCHK(h, hipMemcpyAsync(&e, h->ix.err, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (e & 8u) {  // nothing was stored out of range and the index was not touched: the flag is taken back, the handle stays usable
+        e &= ~8u;
+        HIPCHK(h, hipMemcpyAsync(h->ix.err, &e, 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return fail(h, BRISK_HIP_EINVAL, "place_answers: a record's k-mers fall outside the " + std::to_string(n_slots) +
+                                             " slots: a broken anchor (not the anchors, tags and records of one brisk_hip_scan_kmers call, or n_slots too small)");
+    }
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_profile_slots(brisk_hip_index* h, const uint16_t* d_slots, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min,
+                                      brisk_hip_read_profile* d_out) {
+    if (!h || (n_reads && (!d_starts || !d_out))) return BRISK_HIP_EINVAL;
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    u64 ns = 0;
+    int rc;
+    if ((rc = count_kmers(h, d_starts, n_reads, &ns))) return rc;  // (EINVAL on a table that does not ascend)
+    if (ns && !d_slots) return BRISK_HIP_EINVAL;
+    if ((rc = profile_batch(h, nullptr, d_starts, n_reads, ns, solid_min, (ReadProfile*)d_out, true, d_slots))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
 }
 
 // ---- the per-call API under the C++ facade ----------------------------------------

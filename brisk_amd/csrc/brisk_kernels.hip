@@ -1,11 +1,12 @@
 // brisk_kernels.hip -- HIP kernels of the Brisk hot path for gfx950 (MI355X).
 //
-// One translation unit, eight parts:
+// One translation unit, nine parts:
 //   brisk_scan.hip       reads -> super-k-mer records (SuperKmerEnumerator::next, Kmers.cpp:522-603,
 //                        + hash_kmer_minimizer_inplace / get_compacted, Kmers.cpp:138-145,191-200); long sequences in chunks
 //   brisk_partition.hip  records -> partition order (histogram prefix, k_scatter) and -> owner order (multi-GPU routing)
 //   brisk_insert.hip     per partition: find-all, insert-missing, count++  (DenseMenuYo.hpp:248-310, counter.cpp:262-269)
 //   brisk_readout.hip    Brisk::get / get_superkmer / next / stats and the per-call upsert of the facade
+//   brisk_answers.hip    the per-position get across bucket-range shards: answer offsets, synthetic anchors, answers -> slots
 //   brisk_setops.hip     two indexes combined partition by partition: intersect / subtract / compare, entries -> records for merge
 //   brisk_snapshot.hip   the live entries of a partition range to and from a dense buffer: save / load of an index file
 //   brisk_profile.hip    the per-position answers of a batch reduced to one abundance record per read
@@ -22,6 +23,7 @@
 #include "brisk_partition.hip"
 #include "brisk_insert.hip"
 #include "brisk_readout.hip"
+#include "brisk_answers.hip"
 #include "brisk_setops.hip"
 #include "brisk_snapshot.hip"
 #include "brisk_profile.hip"

@@ -171,6 +171,47 @@ def return_sums(sums: torch.Tensor, recv_counts, send_counts, tags: torch.Tensor
     return per_read
 
 
+def answer_splits(offsets, counts) -> List[int]:
+    """Answers owed per group of records: `offsets` is a record_kmers table (exclusive prefix sum of the records' k-mer counts,
+    len(records) + 1 entries; a numpy array or a tensor) over records grouped as `counts` says (records per rank, rank 0 first);
+    the answers of a group are the difference of the table at its boundaries."""
+    bounds = np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))])
+    if isinstance(offsets, torch.Tensor):
+        at = offsets[torch.as_tensor(bounds, device=offsets.device)].cpu().numpy()
+    else:
+        at = np.asarray(offsets)[bounds]
+    return [int(v) for v in np.diff(at.astype(np.int64))]
+
+
+def return_answers(answers: torch.Tensor, offsets_in: torch.Tensor, recv_counts, offsets_out: torch.Tensor, send_counts, group=None) -> torch.Tensor:
+    """Return trip of a sharded per-k-mer get: the variable-length sibling of return_sums.  `answers` (int16 bits of the u16 slot
+    values, answer_records' output for the records this rank received, grouped by source rank) goes back to the ranks the records
+    came from; what comes back is in the order this rank sent its own records -- the layout its own record_kmers table
+    (`offsets_out`) describes, which is what place_answers takes.  Split sizes come from the two tables (answer_splits); nothing
+    else travels.  The bytes travel as uint8 (every backend moves those)."""
+    send = answer_splits(offsets_in, recv_counts)
+    recv = answer_splits(offsets_out, send_counts)
+    n_out, n_back = sum(send), sum(recv)
+    back = torch.empty(max(n_back, 1), dtype=torch.int16, device=answers.device)
+    src, dst = answers[:n_out].view(torch.uint8), back[:n_back].view(torch.uint8)
+    if answers.is_cuda and dist.get_backend(group) == "gloo":  # rehearsal: through host memory
+        host = torch.empty(n_back * 2, dtype=torch.uint8)
+        dist.all_to_all_single(host, src.cpu(), output_split_sizes=[2 * c for c in recv], input_split_sizes=[2 * c for c in send], group=group)
+        dst.copy_(host)
+        return back
+    dist.all_to_all_single(dst, src, output_split_sizes=[2 * c for c in recv], input_split_sizes=[2 * c for c in send], group=group)
+    return back
+
+
+def agree_batches(n_reads: int, batch_reads: int, device, group=None) -> int:
+    """How many batches of at most `batch_reads` reads a collective call runs, the same on every rank: what the LARGEST share
+    needs (one all-reduce(MAX), as agree_pieces); a rank with fewer reads runs empty batches."""
+    gloo = dist.get_backend(group) == "gloo"
+    most = torch.tensor([(int(n_reads) + batch_reads - 1) // batch_reads], dtype=torch.int64, device=torch.device("cpu") if gloo else device)
+    dist.all_reduce(most, op=dist.ReduceOp.MAX, group=group)
+    return int(most.item())
+
+
 def agree_pieces(n_reads: int, device, group=None, four_from: int = 1 << 22) -> int:
     """The piece count of one ShardedCounter.count_packed call, the same on every rank: every piece issues the same
     all-to-alls on every rank, so the count follows the LARGEST share (one all-reduce(MAX)), not the local one.
@@ -408,3 +449,112 @@ class ShardedCounter:
                     per_read.index_add_(0, tags_out[:n_rec].to(torch.int64), sums[:n_rec])
                 return per_read
             return return_sums(sums[:max(n_in, 1)], recv_counts, counts, tags_out, n_reads, self.group)
+
+    # ---- per-k-mer get, read profiles and trimming across the shards ------------------------------------------
+    def get_kmers_packed(self, d_packed: torch.Tensor, d_starts: torch.Tensor, n_reads: int, first_read: int = 0) -> torch.Tensor:
+        """The slots of brisk_hip_get_kmers_packed for this rank's reads [first_read, first_read + n_reads) (int16 tensor holding the
+        u16 values: 0 absent, 0x100 | count present), with the buckets spread over the ranks: the per-position scan here, the
+        records to their owners, each owner answers record by record into a compact buffer (answer_records), the answers travel
+        back (return_answers) and are moved to their slots (place_answers).  Only records go out and only answers come back.
+        COLLECTIVE, as get_packed: every rank calls it, with any number of reads (0 included)."""
+        ix, W = self.ix, self.W
+        starts_ptr = d_starts.data_ptr() + first_read * 8
+        with torch.cuda.stream(self.stream):
+            if self.world == 1:
+                st = d_starts[first_read: first_read + n_reads + 1]
+                n_slots = int(torch.clamp(st[1:] - st[:-1] - (ix.k - 1), min=0).sum().item()) if n_reads else 0
+                slots = torch.empty(max(n_slots, 1), dtype=torch.int16, device=self.dev)
+                self.stream.synchronize()
+                ix.get_kmers_packed(d_packed.data_ptr(), starts_ptr, n_reads, slots.data_ptr())
+                return slots[:n_slots]
+            cap = max(ix.scan_bound(starts_ptr, n_reads), 1)
+            rec = torch.empty(cap * W, dtype=torch.int64, device=self.dev)
+            tags = torch.empty(cap, dtype=torch.int32, device=self.dev)
+            anchors = torch.empty(cap, dtype=torch.int64, device=self.dev)
+            self.stream.synchronize()
+            n_rec, n_slots = ix.scan_kmers(d_packed.data_ptr(), starts_ptr, n_reads, rec.data_ptr(), tags.data_ptr(), anchors.data_ptr(), cap)
+            out = torch.empty(max(n_rec, 1) * W, dtype=torch.int64, device=self.dev)
+            tags_out = torch.empty(max(n_rec, 1), dtype=torch.int32, device=self.dev)
+            offs_out = torch.empty(n_rec + 1, dtype=torch.int64, device=self.dev)
+            self.stream.synchronize()
+            counts = [int(c) for c in ix.route_tagged(rec.data_ptr(), tags.data_ptr(), n_rec, out.data_ptr(), tags_out.data_ptr())]
+            ix.record_kmers(out.data_ptr(), n_rec, offs_out.data_ptr())
+            inbox, recv_counts = exchange_records(out, counts, W, self.group, None)
+            n_in = sum(recv_counts)
+            offs_in = torch.empty(n_in + 1, dtype=torch.int64, device=self.dev)
+            self.stream.synchronize()
+            ix.record_kmers(inbox.data_ptr(), n_in, offs_in.data_ptr())
+            answers = torch.empty(max(int(offs_in[n_in].item()), 1), dtype=torch.int16, device=self.dev)
+            self.stream.synchronize()
+            ix.answer_records(inbox.data_ptr(), n_in, offs_in.data_ptr(), answers.data_ptr())
+            back = return_answers(answers, offs_in, recv_counts, offs_out, counts, self.group)
+            slots = torch.empty(max(n_slots, 1), dtype=torch.int16, device=self.dev)
+            self.stream.synchronize()
+            ix.place_answers(out.data_ptr(), tags_out.data_ptr(), anchors.data_ptr(), n_rec, offs_out.data_ptr(), back.data_ptr(), slots.data_ptr(), n_slots)
+            return slots[:n_slots]
+
+    def read_profile_packed(self, d_packed: torch.Tensor, d_starts: torch.Tensor, n_reads: int, solid_min: int = 2, batch_reads: int = 1 << 22) -> torch.Tensor:
+        """brisk_hip_read_profile_packed across the shards: one record per read (uint8 tensor, n_reads x 32 bytes: READ_PROFILE_DTYPE).
+        The reads go in batches of `batch_reads`, so that slot memory is a batch's: the sharded get_kmers_packed of the batch, then
+        profile_slots over its slots.  COLLECTIVE: the batch count is agreed on with one all-reduce(MAX) (agree_batches); a rank
+        with fewer reads runs empty batches."""
+        ix = self.ix
+        out = torch.zeros((max(n_reads, 1), 32), dtype=torch.uint8, device=self.dev)
+        if self.world == 1:
+            with torch.cuda.stream(self.stream):
+                self.stream.synchronize()
+                ix.read_profile_packed(d_packed.data_ptr(), d_starts.data_ptr(), n_reads, out.data_ptr(), solid_min)
+            return out[:n_reads]
+        for i in range(agree_batches(n_reads, batch_reads, self.dev, self.group)):
+            lo = min(i * batch_reads, n_reads)
+            nb = min(batch_reads, n_reads - lo)
+            slots = self.get_kmers_packed(d_packed, d_starts, nb, first_read=lo)
+            if nb:
+                self.stream.synchronize()
+                ix.profile_slots(slots.data_ptr(), d_starts.data_ptr() + lo * 8, nb, out.data_ptr() + lo * 32, solid_min)
+        return out[:n_reads]
+
+    def trim_packed(self, d_packed: torch.Tensor, d_starts: torch.Tensor, n_reads: int, d_out_packed: int, out_cap_words: int, d_out_starts: int,
+                    d_out_index: Optional[int] = None, solid_min: int = 2, rule=None, batch_reads: int = 1 << 22) -> Tuple[int, int]:
+        """BriskHip.trim_packed across the shards: the profile (read_profile_packed above: COLLECTIVE), then the rule and the gather,
+        both local.  Outputs and return value as BriskHip.trim_packed: (kept reads, kept nucleotides)."""
+        import brisk_amd
+        ix = self.ix
+        rule = brisk_amd.select_rule("solid_run") if rule is None else rule
+        if self.world == 1:
+            with torch.cuda.stream(self.stream):
+                self.stream.synchronize()
+                return ix.trim_packed(d_packed.data_ptr(), d_starts.data_ptr(), n_reads, d_out_packed, out_cap_words, d_out_starts, d_out_index, solid_min, rule)
+        prof = self.read_profile_packed(d_packed, d_starts, n_reads, solid_min, batch_reads)
+        with torch.cuda.stream(self.stream):
+            iv = torch.empty((max(n_reads, 1), 8), dtype=torch.uint8, device=self.dev)
+            self.stream.synchronize()
+            ix.select_intervals(prof.data_ptr(), n_reads, rule, iv.data_ptr())
+            return ix.extract_packed(d_packed.data_ptr(), d_starts.data_ptr(), n_reads, iv.data_ptr(), d_out_packed, out_cap_words, d_out_starts, d_out_index)
+
+    def _gathered_u64(self, values) -> np.ndarray:
+        """every rank's uint64 values, one row per rank (the bits travel as int64)"""
+        mine = torch.from_numpy(np.asarray(values, dtype=np.uint64).view(np.int64).copy())
+        if dist.get_backend(self.group) != "gloo":
+            mine = mine.to(self.dev)
+        rows = [torch.empty_like(mine) for _ in range(self.world)]
+        dist.all_gather(rows, mine, group=self.group)
+        return np.stack([r.cpu().numpy().view(np.uint64) for r in rows])
+
+    def count_spectrum(self) -> np.ndarray:
+        """brisk_hip_count_spectrum of the whole sharded index: the owners' 256 bins added up (bucket ranges are disjoint).  COLLECTIVE."""
+        mine = self.ix.count_spectrum()
+        return mine if self.world == 1 else self._gathered_u64(mine).sum(axis=0, dtype=np.uint64)
+
+    def prune(self, min_count: int, max_count: int = 255) -> int:
+        """brisk_hip_prune on every owner's range; returns the entries removed over all owners.  COLLECTIVE."""
+        removed = self.ix.prune(min_count, max_count)
+        return removed if self.world == 1 else int(self._gathered_u64([removed]).sum())
+
+    def checksum(self) -> tuple:
+        """brisk_hip_checksum of the whole sharded index: entries and counts add up, the digests add up modulo 2^64.  COLLECTIVE."""
+        mine = self.ix.checksum()
+        if self.world == 1:
+            return mine
+        rows = self._gathered_u64(mine)
+        return int(rows[:, 0].sum()), int(rows[:, 1].sum()), int(sum(int(v) for v in rows[:, 2]) % (1 << 64))

@@ -34,7 +34,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU). In-tree output."""
     out = library_path()
     srcs = [os.path.join(HERE, "csrc", f) for f in ("brisk_capi.hip", "brisk_kernels.hip", "brisk_scan.hip", "brisk_partition.hip", "brisk_insert.hip",
-                                                    "brisk_readout.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_extract.hip", "brisk_device.h")]
+                                                    "brisk_readout.hip", "brisk_answers.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_extract.hip", "brisk_device.h")]
     srcs.append(os.path.join(ROOT, "include", "brisk_hip.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
@@ -115,6 +115,7 @@ SYMBOLS = [
     "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_debug_guard_count", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
     "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune",
     "brisk_hip_read_profile_reads", "brisk_hip_read_profile_packed",
+    "brisk_hip_scan_kmers", "brisk_hip_record_kmers", "brisk_hip_answer_records", "brisk_hip_place_answers", "brisk_hip_profile_slots",
     "brisk_hip_select_intervals", "brisk_hip_extract_packed", "brisk_hip_trim_packed", "brisk_hip_trim_reads", "brisk_hip_unpack_ascii",
     "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
     "brisk_hip_profile_enable",
@@ -175,6 +176,11 @@ def load() -> C.CDLL:
     L.brisk_hip_scan_query.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.brisk_hip_route_tagged.argtypes = [vp, vp, vp, u64, vp, vp, _u64p]
     L.brisk_hip_query_records.argtypes = [vp, vp, u64, vp]
+    L.brisk_hip_scan_kmers.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.brisk_hip_record_kmers.argtypes = [vp, vp, u64, vp]
+    L.brisk_hip_answer_records.argtypes = [vp, vp, u64, vp, vp]
+    L.brisk_hip_place_answers.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64]
+    L.brisk_hip_profile_slots.argtypes = [vp, vp, vp, u64, u32, vp]
     L.brisk_hip_pack_ascii.argtypes = [vp, vp, u64, vp]
     L.brisk_hip_synth_reads.argtypes = [vp, u64, u64, u64, u32, u64, u64, vp, vp]
     _u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
@@ -703,6 +709,32 @@ class BriskHip:
     def query_records(self, d_records: int, n: int, d_sums: int):
         """d_sums[i] (u64) = sum of the counts of record i's k-mers present in this index"""
         self._chk(self.L.brisk_hip_query_records(self.h, d_records, n, d_sums))
+
+    def scan_kmers(self, d_packed: int, d_starts: int, n_reads: int, d_records: int, d_tags: int, d_anchors: int, cap: int) -> Tuple[int, int]:
+        """per-position scan (brisk_hip_scan_kmers): records, a tag each (u32, index into the anchors) and the anchors (u64); returns
+        (records, slots of the batch)"""
+        n_rec, n_slots = C.c_uint64(), C.c_uint64()
+        rc = self.L.brisk_hip_scan_kmers(self.h, d_packed, d_starts, n_reads, d_records, d_tags, d_anchors, cap, C.byref(n_rec), C.byref(n_slots))
+        if rc == ECAPACITY:
+            raise BriskHipError(rc, f"scan needs {n_rec.value} records, cap {cap}")
+        self._chk(rc)
+        return n_rec.value, n_slots.value
+
+    def record_kmers(self, d_records: int, n: int, d_offsets: int):
+        """d_offsets[0 .. n] (u64) = exclusive prefix sum of the records' k-mer counts (brisk_hip_record_kmers)"""
+        self._chk(self.L.brisk_hip_record_kmers(self.h, d_records, n, d_offsets))
+
+    def answer_records(self, d_records: int, n: int, d_offsets: int, d_answers: int):
+        """owner side: d_answers[d_offsets[i] + j] (u16) = 0 or 0x100 | count for k-mer j of record i (brisk_hip_answer_records)"""
+        self._chk(self.L.brisk_hip_answer_records(self.h, d_records, n, d_offsets, d_answers))
+
+    def place_answers(self, d_records: int, d_tags: int, d_anchors: int, n: int, d_offsets: int, d_answers: int, d_slots: int, n_slots: int):
+        """asker side: the answers of the routed records to their slots (brisk_hip_place_answers)"""
+        self._chk(self.L.brisk_hip_place_answers(self.h, d_records, d_tags, d_anchors, n, d_offsets, d_answers, d_slots, n_slots))
+
+    def profile_slots(self, d_slots: int, d_starts: int, n_reads: int, d_out: int, solid_min: int = 2):
+        """read_profile_packed over slots the caller holds (brisk_hip_profile_slots)"""
+        self._chk(self.L.brisk_hip_profile_slots(self.h, d_slots, d_starts, n_reads, solid_min, d_out))
 
     def pack_ascii(self, d_bases: int, n_bases: int, d_packed: int):
         self._chk(self.L.brisk_hip_pack_ascii(self.h, d_bases, n_bases, d_packed))

@@ -86,6 +86,9 @@
  *   brisk_hip_scan_query / brisk_hip_route_tagged / brisk_hip_query_records
  *                               the query path (apps/counter.cpp:281-310, brisk/Brisk.hpp:102-118) cut at the
  *                               same boundary, for a get across bucket-range shards
+ *   brisk_hip_scan_kmers / brisk_hip_record_kmers / brisk_hip_answer_records / brisk_hip_place_answers / brisk_hip_profile_slots
+ *                               no reference counterpart (the reference is single-process): the per-k-mer get and the read profile cut
+ *                               at the same boundary, for brisk_hip_get_kmers and brisk_hip_read_profile_* across bucket-range shards
  *   brisk_hip_scan_sequence     SuperKmerEnumerator ctor + next() until empty (brisk/Kmers.cpp:509-603)
  *   brisk_hip_upsert_kmers      Brisk::insert_superkmer (brisk/Brisk.hpp:123-147) minus the DATA pointers,
  *                               which the facade forms from the returned ids
@@ -227,7 +230,8 @@ int brisk_hip_get_packed(brisk_hip_index *h, const uint32_t *d_packed, const uin
  * it depend on the context, so it is not always the identity of the k-mer enumerated on its own.  Every slot of every read is
  * answered: the stop of brisk_hip_get_reads at a returned minimizer of 0 (counter.cpp:304-306) belongs to that per-read sum,
  * not to get_superkmer.  Pending deferred inserts are completed first.  The answer does not depend on max_batch_reads, on how
- * the call is batched or on which kernels run.  EINVAL on a sharded index (n_owners > 1) and on an entry-id index. */
+ * the call is batched or on which kernels run.  EINVAL on a sharded index (n_owners > 1) and on an entry-id index.  Across shards the
+ * same slots come from brisk_hip_scan_kmers / _route_tagged / _record_kmers / _answer_records / _place_answers (below). */
 /* HOST reads (layout of brisk_hip_get_reads); out[cap] HOST.  BRISK_HIP_ECAPACITY, nothing written, if cap < total slots. */
 int brisk_hip_get_kmers(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
                         uint16_t *out, uint64_t cap);
@@ -251,7 +255,8 @@ int brisk_hip_get_kmers_packed(brisk_hip_index *h, const uint32_t *d_packed, con
  * written for one internal batch at a time into scratch memory of the handle and reduced there, so device memory grows with a
  * batch's slots (2 bytes each; a batch is at most min(max_batch_reads, BRISK_PROFILE_BATCH = 2^24) reads), not with the call's, and
  * the caller never allocates a slot array.  Reads of more than BRISK_PROFILE_SEG slots (environment, read once per process;
- * default 4096) are reduced in segments of that many slots and their partial results folded in order; the record is the same. */
+ * default 4096) are reduced in segments of that many slots and their partial results folded in order; the record is the same.
+ * Across shards the slots come from the round trip of brisk_hip_scan_kmers and brisk_hip_profile_slots reduces them (below). */
 typedef struct brisk_hip_read_profile {   /* 32 bytes, little-endian, no padding */
     uint32_t n_kmers;        /* slots of the read: max(0, len - k + 1) */
     uint32_t n_present;      /* slots whose k-mer is in the index */
@@ -316,7 +321,8 @@ int brisk_hip_extract_packed(brisk_hip_index *h, const uint32_t *d_packed, const
  * time) and the intervals (8 bytes a read) live in scratch memory of the handle.  trim_reads takes HOST reads (layout of
  * brisk_hip_get_reads) and returns only the intervals, out[n_reads] HOST: the caller slices its own strings.  Both inherit
  * brisk_hip_read_profile_*: pending deferred inserts are completed first; EINVAL on a sharded index, on an entry-id index, on offsets
- * that do not ascend; the answer does not depend on max_batch_reads, BRISK_PROFILE_BATCH, BRISK_PROFILE_SEG or on which kernels run. */
+ * that do not ascend; the answer does not depend on max_batch_reads, BRISK_PROFILE_BATCH, BRISK_PROFILE_SEG or on which kernels run.
+ * Across shards: brisk_hip_profile_slots over the slots of the brisk_hip_scan_kmers round trip, then select_intervals and extract_packed. */
 int brisk_hip_trim_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
                           uint32_t solid_min, const brisk_hip_select_rule *rule,
                           uint32_t *d_out_packed, uint64_t out_cap_words, uint64_t *d_out_starts, uint64_t *d_out_index,
@@ -517,6 +523,50 @@ int brisk_hip_scan_query(brisk_hip_index *h, const uint32_t *d_packed, const uin
 int brisk_hip_route_tagged(brisk_hip_index *h, const uint64_t *d_records, const uint32_t *d_tags, uint64_t n_records,
                            uint64_t *d_out, uint32_t *d_tags_out, uint64_t *counts);
 int brisk_hip_query_records(brisk_hip_index *h, const uint64_t *d_records, uint64_t n_records, uint64_t *d_sums);
+
+/* The per-k-mer get (brisk_hip_get_kmers) cut at the same boundary.  The owner of a bucket range does not hold the asker's slot array,
+ * so it answers into a compact buffer that travels back: record i's k-mers, in the record's own order (the order its key is built
+ * in: minimizer_idx rising), at offsets[i] .. offsets[i + 1], offsets being the exclusive prefix sum of the records' k-mer counts.
+ * Asker and owner compute the same table from the records alone (record_kmers), so only records travel out and only answers travel
+ * back -- no tags, no anchors: the asker keeps those and turns position-in-record into position-in-read itself.  A sharded
+ * per-k-mer get is scan_kmers -> route_tagged -> all-to-all -> record_kmers + answer_records on the owner -> all-to-all back (u16,
+ * split sizes = the differences of the asker's table at the owner boundaries) -> record_kmers + place_answers.  All five take the
+ * per-handle lock, run on the handle's stream, complete pending deferred inserts first and return when their output is complete. */
+/* The scan of brisk_hip_get_kmers_packed (every k-mer: no query stop at a returned minimizer of 0), cut at the record boundary as
+ * brisk_hip_scan_query is.  Per record i: the record, d_tags[i] = an index into d_anchors (route_tagged carries it along) and the
+ * record's slot anchor there (opaque: a slot of the batch's slot array, layout of brisk_hip_get_kmers_packed, plus an orientation
+ * bit).  *n_slots (HOST, 64-bit) = the batch's slots.  d_records, d_tags, d_anchors hold cap_records entries each; ECAPACITY and
+ * brisk_hip_scan_bound as for brisk_hip_scan_query.  Sequences of more than 8192 k-mers are scanned in chunks, as everywhere.
+ * Needs no index state: any handle serves, sharded ones included (the records' routing ids are the handle's layout's). */
+int brisk_hip_scan_kmers(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                         uint64_t *d_records, uint32_t *d_tags, uint64_t *d_anchors, uint64_t cap_records,
+                         uint64_t *n_records, uint64_t *n_slots);
+/* d_offsets[0 .. n_records] (DEVICE, u64) = the exclusive prefix sum of the records' k-mer counts; d_offsets[n_records] = their total.
+ * For records grouped by owner (route_tagged) the answers owed by owner o are the difference of the table at o's group boundaries.
+ * Any handle of the records' geometry.  At most 2^32 - 1 records. */
+int brisk_hip_record_kmers(brisk_hip_index *h, const uint64_t *d_records, uint64_t n_records, uint64_t *d_offsets);
+/* Owner side.  d_answers[d_offsets[i] + j] (DEVICE, u16, d_offsets[n_records] entries; d_offsets from record_kmers over the same
+ * records) = 0 when k-mer j of record i is absent from THIS index, 0x100 | count when present -- the slot values of
+ * brisk_hip_get_kmers.  Every one of the d_offsets[n_records] entries is written and nothing else is.  Records of other owners, the
+ * limit of 2^32 - 1 records and pending inserts: as for brisk_hip_query_records.  The probe kernels are those of
+ * brisk_hip_get_kmers (same selection, same environment switches), run under anchors made from d_offsets.  EINVAL on an entry-id index. */
+int brisk_hip_answer_records(brisk_hip_index *h, const uint64_t *d_records, uint64_t n_records, const uint64_t *d_offsets,
+                             uint16_t *d_answers);
+/* Asker side.  For the routed records (d_records, d_tags as route_tagged left them, or any contiguous piece of them with its own
+ * record_kmers table and the answers that came back for it) and the anchors of the scan_kmers call they come from:
+ * d_slots[slot of k-mer j of record i] = d_answers[d_offsets[i] + j], by plain vector stores.  Every slot of the batch belongs to
+ * exactly one k-mer of one record, so when every piece has been placed every slot has been written once; several calls may fill
+ * one slot array.  A slot >= n_slots is never stored: the call then returns EINVAL (a broken anchor: not the anchors of these
+ * records, or n_slots too small), the slots below n_slots hold what was placed, and the handle stays usable.  Any handle of the
+ * records' geometry. */
+int brisk_hip_place_answers(brisk_hip_index *h, const uint64_t *d_records, const uint32_t *d_tags, const uint64_t *d_anchors,
+                            uint64_t n_records, const uint64_t *d_offsets, const uint16_t *d_answers,
+                            uint16_t *d_slots, uint64_t n_slots);
+/* The reduction of brisk_hip_read_profile_packed over slots the caller holds (DEVICE; layout of brisk_hip_get_kmers_packed for the
+ * reads d_starts[0 .. n_reads] describes): d_out[r] = the record of read r.  Same records, same BRISK_PROFILE_SEG segment rule, same
+ * refusals (offsets that do not ascend, a read of more than 2^32 - 1 slots).  Needs no index state: any handle serves. */
+int brisk_hip_profile_slots(brisk_hip_index *h, const uint16_t *d_slots, const uint64_t *d_starts, uint64_t n_reads,
+                            uint32_t solid_min, brisk_hip_read_profile *d_out);
 
 /* ---- the per-call API under the C++ facade (entry-id mode) --------------------- */
 /* SuperKmerEnumerator over one clean sequence (len >= k): every vector next() would
