@@ -605,7 +605,8 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
     const u32 n_huge = h->h_ctr->n_huge <= HUGE_LIST_CAP ? h->h_ctr->n_huge : 0u;
     h->ix.huge_at = n_huge ? huge_at : 0u;
     // worst case: every slice the batch may need, the tail a private chunk strands at each refill (< 1/8 of it), and
-    // one partly used chunk per persistent wave
+    // one partly used chunk per persistent wave.  (k_insert_first asks its private chunk for grow_cap(192) = 248 entries at most,
+    // a small request like insert_body's below ARENA_CHUNK / 8: what a refill strands is within the seventh; asserted in the kernel)
     if ((rc = ensure_arena(h, h->h_ctr->touched.need + h->h_ctr->touched.need / 7 + (u64)h->insert_waves * ARENA_CHUNK))) return rc;
     {
         ProfScope ps(h, S_INSERT);
@@ -621,7 +622,8 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         const bool sat = h->count_mode == BRISK_HIP_COUNTS_SATURATE;
         // cap_per_cu: a kernel built for at most so many waves (amdgpu_waves_per_eu's maximum).  The compiler holds the hardware to it
         // through the register allotment in the kernel descriptor; the occupancy query works from the registers the code uses and
-        // would count waves that are never resident together (k_insert_first: 71 used, 80 allotted: 28 against 24 per CU).
+        // would count waves that are never resident together (k_insert_first with two slots: 71 used, 80 allotted: 28 against 24 per CU;
+        // with three it uses all 80, and its 5,776 B of LDS would still let 26 in).
         auto resident = [&](const void* fn, int cap_per_cu = 0) -> u32 {
             int per_cu = 0, cus = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 16;

@@ -1059,7 +1059,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8)))
 // global is written for it, its descriptor index goes to a list that k_insert_fast then walks (one atomic per batch of WI_BATCH
 // partitions: the batch's left-over partitions are a 64-bit mask in scalar registers).
 #ifndef NI_LEAN
-#define NI_LEAN 2   // profiles/r13_insert_ninst.txt
+#define NI_LEAN 3   // k_insert_first's default slot count: profiles/r13_insert_ninst.txt, r17_insert_ninst.txt (-DNI_LEAN=2: the two-slot kernel, for A/B)
 #endif
 #ifndef WI_WAVES_PER_EU_FIRST
 #define WI_WAVES_PER_EU_FIRST 6
@@ -1069,7 +1069,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8)))
 #endif
 template <u32 NIL, u32 NW>
 struct LeanLds {
-    static constexpr u32 MAXI = 64 * NIL, TABLE = 4 * MAXI;
+    // TABLE: the probe masks with tsize - 1, so a power of two.  512 slots are four per instance up to 128 instances and 2.7 at
+    // 192 (insert_body: two at 256); 4 * MAXI = 768 at three slots would let tsize double past it to 1024, 640 B beyond s_mem.
+    static constexpr u32 MAXI = 64 * NIL, TABLE = 512;
+    static_assert((TABLE & (TABLE - 1)) == 0 && TABLE >= 2 * MAXI && TABLE <= 4 * MAXI, "probe table: a power of two, at most half full");
     static constexpr u32 REC_BYTES = (WI_MAX_REC * RecGeom<NW>::RS + 4) * 4;   // shifted record words, + 4: the last record's window
     static constexpr u32 OFF_REC = 16 * MAXI;                                  // keys first (s_idiff over them)
     static constexpr u32 REGION = REC_BYTES > 4 * TABLE ? REC_BYTES : 4 * TABLE;  // the probe table lies over the records
@@ -1088,6 +1091,7 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
     static_assert(NW >= 3 && SHIFT < 5, "the folding k63 geometries: at most 16 buckets per partition");
     static_assert(L::BYTES <= 13 * 512, "LDS per wave: 24 waves must fit a CU's 160 KiB");
     static_assert(4 * MAXI <= 16 * MAXI, "the multiplicity steps lie over the keys");
+    static_assert(MAXI + (MAXI >> 2) + 8 <= ARENA_CHUNK / 8, "grow_cap(MAXI) is a small request: the host's arena reserve covers the tail a refill strands");
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[L::BYTES];
     u64* s_key = (u64*)s_mem;
     u32* s_idiff = (u32*)s_mem;
@@ -1238,7 +1242,7 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                 unsigned long long off = d.off;
                 u32 cap = 0;
                 if (n_new) {  // the slice insert_body takes for a fresh partition of one chunk, from the private chunk
-                    const unsigned long long want = grow_cap(n_new);  // <= grow_cap(64 * NI_LEAN): far below ARENA_CHUNK / 8
+                    const unsigned long long want = grow_cap(n_new);  // <= grow_cap(MAXI) = 248 at three slots: far below ARENA_CHUNK / 8 (asserted above)
                     if (acur + want > aend) {
                         garbage += aend - acur;
                         unsigned long long got = 0;
@@ -1296,11 +1300,11 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
         if (garbage) atomicAdd(&ix.stats[3], garbage);
     }
 }
-template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false>
+template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false, u32 NIL = NI_LEAN>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVES_PER_EU_FIRST, WI_WAVES_PER_EU_FIRST_MAX))) k_insert_first(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
                                                                                                           u32 n_touched, IndexDev ix, u32* __restrict__ work_counter,
                                                                                                           u32* __restrict__ left_list, u32* __restrict__ n_left) {
-    insert_first_body<NI_LEAN, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter, left_list, n_left);
+    insert_first_body<NIL, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter, left_list, n_left);
 }
 
 // bucket occupancy for partitions wider than 64 buckets (small part_bits): one pass over all entries
