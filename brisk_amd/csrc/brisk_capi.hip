@@ -133,7 +133,8 @@ struct brisk_hip_index {
     bool pend_hist_ok = true;   // d_hist counts exactly the pending records
     bool defer = true;          // brisk_hip_options.immediate_inserts == 0 and BRISK_DEFER != 0
     bool verify = false;        // BRISK_VERIFY=1 at create: every stage hand-over of the host paths is checked (verify_upload, verify_records)
-    bool trace = false;         // BRISK_TRACE=1 at create: one stderr line per batch saying which host path and which insert kernel took it
+    bool trace = false;         // BRISK_TRACE=1 at create: one stderr line per batch saying which host path and which insert kernel took it,
+                                // and one per arena growth part-way through a vector of brisk_hip_upsert_kmers (trace_upsert_resume)
     DevBuf staging, parted, desc, chunk_buf, tags_a, tags_b, packed_tmp, bases_tmp, starts_tmp, sums_tmp, enum_out, lookup_buf;
     DevBuf packed_tmp2, starts_tmp2;  // the second set of insert_reads_pipelined: one sub-batch is scanned while the next one arrives
     DevBuf anchors, slot_buf, kout_tmp;  // per-position mode (brisk_hip_get_kmers): records' slot anchors, the batch's slot bases, host-call output
@@ -3885,6 +3886,13 @@ static int upload_queries(brisk_hip_index* h, const uint64_t* lo, const uint64_t
     return BRISK_HIP_OK;
 }
 
+// BRISK_TRACE: k_upsert stopped for lack of arena behind `done` of the vector's n k-mers (0: at its first); the host grows the arena and resumes
+static void trace_upsert_resume(const brisk_hip_index* h, u32 done, u64 n) {
+    if (h->trace)
+        fprintf(stderr, "[brisk_hip] path: upsert resumed behind %u of %llu k-mers, arena full at %llu of %llu entries\n", done, (unsigned long long)n,
+                (unsigned long long)h->arena_used_host, (unsigned long long)h->arena_cap);
+}
+
 BRISK_API int brisk_hip_upsert_kmers(brisk_hip_index* h, const uint64_t* kmer_lo, const uint64_t* kmer_hi, const uint8_t* minimizer_idx, uint64_t n,
                                      uint32_t* ids, uint8_t* newly) {
     if (!h || (n && (!kmer_lo || !kmer_hi || !minimizer_idx || !ids || !newly)) || n > 255) return BRISK_HIP_EINVAL;
@@ -3935,6 +3943,7 @@ BRISK_API int brisk_hip_upsert_kmers(brisk_hip_index* h, const uint64_t* kmer_lo
         // the arena filled up part-way through the vector: the general path below grows it and goes on behind the k-mers that are in
         // (their ids and flags are where the general path's copy at the end finds them: same buffer, same layout)
         done = step;
+        trace_upsert_resume(h, done, n);
         if ((rc = ensure_arena(h, h->arena_cap))) return rc;
     }
     if ((rc = upload_queries(h, kmer_lo, kmer_hi, minimizer_idx, n, &d_lo, &d_hi, &d_idx, &d_ids, &d_new))) return rc;
@@ -3949,6 +3958,7 @@ BRISK_API int brisk_hip_upsert_kmers(brisk_hip_index* h, const uint64_t* kmer_lo
         done += step;
         h->arena_used_host = h->h_ctr->arena_used;
         if (done < n) {  // the arena is full: double it and go on with the rest of the vector
+            trace_upsert_resume(h, done, n);
             if ((rc = ensure_arena(h, h->arena_cap))) return rc;
         }
     }

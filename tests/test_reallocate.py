@@ -54,6 +54,62 @@ def _lines_to_counter(lines):
                                       # count in the header -- k_insert_big's in-place collapse must add those counts up, not count the records
                                       (31, 11, 4, 4), (41, 15, 10, 3)])
 def test_bulk_reallocate_matches_the_enumerator_at_the_new_m(O, k, m, b, pb):
+    _reallocate_and_check(O, k, m, b, 0, pb)
+
+
+def _target_layout(k, m, b, pb):
+    import geometry_edges as G
+    return G.layout(k, m + 2, b + 2, pb)
+
+
+# The key-layout boundary rows (tests/geometry_edges.py) whose (k, m + 2, b + 2) brisk_hip_create accepts:
+# (k, m, b, source part_bits, target part_bits).  brisk_hip_reallocate decodes every source entry (entry_hashed_kmer under the
+# source's layout), scans the k-mers as reads of k nucleotides at the target's geometry and inserts one-k-mer records that carry a
+# count: source and target differ in key words and in having classes.  Left out: (33, 31, 14), (63, 31, 2): m + 2 = 33 is no minimizer
+# size.  No row is dropped for _one_kmer: every entry of every row here yields one piece at m + 2 (asserted in _expected).
+EDGE_ROWS = [
+    (35, 13, 6, 0, 0),    # 64 -> 60 bits: one word to one word
+    (34, 11, 4, 0, 0),    # 66 -> 62 bits: two words to one; classes to none
+    (33, 11, 4, 0, 0),    # 64 -> 60 bits; classes to none
+    (32, 11, 3, 0, 0),    # k = 32: 64 -> 60 bits
+    (63, 21, 2, 0, 0),    # 128 -> 124 bits
+    (63, 5, 2, 0, 0),     # classes on both sides, 128 -> 124 bits
+    (62, 21, 1, 0, 0),    # b = 1 -> 3
+    (12, 5, 1, 0, 0),     # the smallest: 28 -> 24 bits, classes to none (a window of 6 k-mers has no classes)
+    (33, 11, 6, 6, 8),    # a routing field across the word boundary on the source side; exactly 64 bits in the target
+    (31, 11, 4, 2, 0),    # four big source partitions, straddling keys
+    (44, 23, 12, 0, 0),   # 2k - m = 65 -> 63: the 256-bit record builder to the 128-bit one
+    (35, 13, 6, 0, 3),    # eight target partitions: hundreds of one-k-mer records with header counts in each (k_insert_big's collapse);
+                          # the target key has 73 bits, its routing field across the word boundary
+    (63, 21, 2, 0, 2),    # the same at the ceiling: part_bits = 2 becomes 4, a 128-bit target key with a routing field
+]
+
+
+def test_edge_rows_sit_where_they_claim():
+    """CPU: the layouts the comments above name, from the formula"""
+    import geometry_edges as G
+    bits = lambda k, m, b, pb: (G.layout(k, m, b, pb)["key_bits"], G.layout(k, m, b, pb)["key_words"], G.layout(k, m, b, pb)["cls_bits"])
+    assert all(_target_layout(k, m, b, tpb) is not None and G.layout(k, m, b, spb) is not None for k, m, b, spb, tpb in EDGE_ROWS)
+    assert (bits(35, 13, 6, 0), bits(35, 15, 8, 0)) == ((64, 1, 0), (60, 1, 0))
+    assert (bits(34, 11, 4, 0), bits(34, 13, 6, 0)) == ((66, 2, 1), (62, 1, 0))
+    assert (bits(33, 11, 4, 0), bits(33, 13, 6, 0)) == ((64, 1, 1), (60, 1, 0))
+    assert (bits(63, 21, 2, 0), bits(63, 23, 4, 0)) == ((128, 2, 0), (124, 2, 0))
+    assert (bits(63, 5, 2, 0), bits(63, 7, 4, 0)) == ((128, 2, 1), (124, 2, 1))
+    assert (bits(12, 5, 1, 0), bits(12, 7, 3, 0)) == ((28, 1, 1), (24, 1, 0))
+    assert (bits(33, 11, 6, 6), bits(33, 13, 8, 8)) == ((66, 2, 0), (64, 1, 0))
+    L = _target_layout(63, 21, 2, 2)
+    assert (L["part_bits"], L["shift"], L["key_bits"]) == (4, 4, 128)
+    L = _target_layout(35, 13, 6, 3)
+    assert (L["part_bits"], L["key_bits"], L["straddle"]) == (3, 73, True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k,m,b,spb,tpb", EDGE_ROWS, ids=["k%dm%db%d-pb%d-to-pb%d" % row for row in EDGE_ROWS])
+def test_bulk_reallocate_at_the_key_layout_rows(O, k, m, b, spb, tpb):
+    _reallocate_and_check(O, k, m, b, spb, tpb)
+
+
+def _reallocate_and_check(O, k, m, b, spb, pb):
     import brisk_amd
     rng = random.Random(77)
     genome = "".join(rng.choice("ACGT") for _ in range(6000))
@@ -63,7 +119,7 @@ def test_bulk_reallocate_matches_the_enumerator_at_the_new_m(O, k, m, b, pb):
         s = genome[p:p + 150]
         reads.append(s if rng.random() < 0.5 else "".join(COMP[c] for c in reversed(s)))
     reads += ["A" * 120, "ACGT" * 40, "AC" * 70]  # low complexity: minimizer ties, entries that merge
-    with brisk_amd.BriskHip(k, m, b) as old, brisk_amd.BriskHip(k, m + 2, b + 2, part_bits=pb) as new:
+    with brisk_amd.BriskHip(k, m, b, part_bits=spb) as old, brisk_amd.BriskHip(k, m + 2, b + 2, part_bits=pb) as new:
         old.insert_reads(reads)
         before = oracle.multiset_lines(*old.enumerate(), k)
         assert max(int(l.split()[-1]) for l in before) > 20  # counts well above 1, even and odd
