@@ -66,7 +66,7 @@ struct Counters {
     struct Scan { unsigned long long n_rec; u32 overflow, pad; } scan;          // ScanOut::n_rec (records wanted, also beyond cap), ::overflow
     struct Touched { u32 n_touched, pad; unsigned long long need; } touched;    // k_touched: partitions with records; k_need: arena slots they may take
     struct Kmers { unsigned long long bound, n_long; } kmers;                   // k_count_kmers: k-mers; sequences beyond SCAN_LONG | offsets do not ascend << 63
-    struct Work { u32 wc[2], n_left, pad; } work;  // work counters of the persistent insert / query waves; k_insert_first: partitions left to k_insert_fast_listed
+    struct Work { u32 wc[2], n_left, n_clean; } work;  // work counters of the persistent insert / query waves; k_insert_first: partitions left to k_insert_fast_listed, and those it took table-free
     struct Plan { u32 n_long, n_vr; } plan;        // k_plan_chunks: long sequences, and the chunks they are cut into
     u32 n_rerun, pad;                              // k_chunk_commit: chunks to re-scan this round
     unsigned long long kept;                       // k_filter_records / k_query_filter / k_pos_filter: records that stand
@@ -639,6 +639,7 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         // over (DESIGN.md section 4 finding 16).  Per call, not per partition: the flag is exact and costs no descriptor pass.
         static const bool generic_only = getenv("BRISK_INSERT_GENERIC") != nullptr;  // A/B and tests: force the run-time body
         static const bool lean_off = getenv("BRISK_INSERT_LEAN") && !strcmp(getenv("BRISK_INSERT_LEAN"), "0");  // A/B and tests: never take k_insert_first's route
+        static const bool clean_off = getenv("BRISK_INSERT_CLEAN") && !strcmp(getenv("BRISK_INSERT_CLEAN"), "0");  // A/B and tests: k_insert_first's table path for every partition
         const bool lean = fresh && !generic_only && !lean_off && !h->entry_ids && !big && P.nw == 3 && P.kb == 49 && P.shift >= 1 && P.shift <= 4;
         if (lean) {
             if ((rc = ensure(h, h->left, (size_t)n_touched * 4))) return rc;
@@ -680,9 +681,10 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
     {                                                                                                                                                               \
         u32* const wc = h->d_ctr->work.wc;                                                                                                                          \
         u32* const n_left = &h->d_ctr->work.n_left;                                                                                                                 \
+        u32* const n_clean = clean_off ? nullptr : &h->d_ctr->work.n_clean;                                                                                         \
         const dim3 grid(std::min<u32>(batches, resident((const void*)k_insert_first<3, 49, SH, SAT>, 4 * WI_WAVES_PER_EU_FIRST_MAX)));                                                            \
         hipLaunchKernelGGL((k_insert_first<3, 49, SH, SAT>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix, wc,                \
-                           (u32*)h->left.p, n_left);                                                                                                                \
+                           (u32*)h->left.p, n_left, n_clean);                                                                                                       \
         if ((rc = launch_check(h, "k_insert_first"))) return rc;                                                                                                    \
         const dim3 grid2(std::min<u32>(batches, resident((const void*)k_insert_fast_listed<3, 49, SH, SAT>)));                                                     \
         hipLaunchKernelGGL((k_insert_fast_listed<3, 49, SH, SAT>), grid2, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix, wc + 1,     \
@@ -713,14 +715,15 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
 #undef LAUNCH_INSERT_K
         if ((rc = launch_check(h, big ? "k_insert_big" : "k_insert"))) return rc;
         if (h->trace) {
-            std::string path = big ? "k_insert_big (in-place collapse for partitions of > 128 records)" : "k_insert";
+            std::string path = big ? "k_insert_big (in-place collapse for partitions of > 128 records)" : "k_insert", tail;
             if (lean) {  // (tracing only: the count is waited for)
-                HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->work.n_left));
+                HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->work));
                 const u32 n_left = h->h_ctr->work.n_left;
                 path = "k_insert_first (fresh index): " + std::to_string(n_touched - n_huge - n_left) + " partitions lean, " + std::to_string(n_left) + " left over to k_insert";
+                tail = " (" + std::to_string(h->h_ctr->work.n_clean) + " table-free)";  // of the lean ones: the fold proved their instances distinct (finding 19)
             }
-            fprintf(stderr, "[brisk_hip] path: insert of %llu records (%s layout, histogram %s) into %u partitions: %s, %u partitions to k_insert_huge\n", (unsigned long long)n_rec,
-                    bl ? "binned" : "classic", have_hist ? "from the scan" : "counted here", n_touched, path.c_str(), n_huge);
+            fprintf(stderr, "[brisk_hip] path: insert of %llu records (%s layout, histogram %s) into %u partitions: %s, %u partitions to k_insert_huge%s\n", (unsigned long long)n_rec,
+                    bl ? "binned" : "classic", have_hist ? "from the scan" : "counted here", n_touched, path.c_str(), n_huge, tail.c_str());
         }
         if (n_huge) {
             if (sat) hipLaunchKernelGGL(k_insert_huge<true>, dim3(std::min<u32>(n_huge, 256u)), dim3(HG_THREADS), 0, h->stream, P, src, (const PartDesc*)h->desc.p,

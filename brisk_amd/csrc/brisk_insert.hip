@@ -306,12 +306,62 @@ struct LaneInst {
     u32 hh[NIMAX];
     u32 won;
 };
+// The entry key of instance i (i >= ninst: of the record's instance 0, never used) cut out of its record's words at `base`.
+template <u32 NW, u32 KB, u32 SHIFT>
+__device__ __forceinline__ void cut_key(const u32* base, u32 i, u32 ninst, u64* lo_out, u64* hi_out) {
+    constexpr u32 INFO = RecGeom<NW>::INFO, KBITS = 2 * KB + 6;
+    const u32 info = base[INFO];
+    const u32 j = i < ninst ? i - (info & 0x3ffu) : 0;
+    const u32 n = (info >> 10) & 0xffu;
+    const u32 s = 2 * (n - 1 - j);
+    const u32* wp = base + (s >> 5);
+    const u32 sh = s & 31;
+    const u32 w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3], w4 = wp[4];
+    u32 k0 = __builtin_amdgcn_alignbit(w1, w0, sh), k1 = __builtin_amdgcn_alignbit(w2, w1, sh);
+    u32 k2 = __builtin_amdgcn_alignbit(w3, w2, sh), k3 = __builtin_amdgcn_alignbit(w4, w3, sh);
+    k0 = (k0 & ~0x3fu) | (((info >> 18) & 0xffu) + j);  // idx' = idx0' + j (SuperKmerLight.hpp:98)
+    // keep the 2kb + 6 key bits, put the routing id's low bits on top
+    constexpr u32 m0 = KBITS >= 32 ? ~0u : (1u << KBITS) - 1, m1 = KBITS >= 64 ? ~0u : KBITS <= 32 ? 0u : (1u << (KBITS - 32)) - 1;
+    constexpr u32 m2 = KBITS >= 96 ? ~0u : KBITS <= 64 ? 0u : (1u << (KBITS - 64)) - 1, m3 = KBITS >= 128 ? ~0u : KBITS <= 96 ? 0u : (1u << (KBITS - 96)) - 1;
+    k0 &= m0; k1 &= m1; k2 &= m2; k3 &= m3;
+    u64 lo = ((u64)k1 << 32) | k0, hi = ((u64)k3 << 32) | k2;
+    if (SHIFT) {
+        const u64 rl = (info >> 26) & ((1u << SHIFT) - 1);
+        if (KBITS >= 64) hi |= rl << (KBITS - 64);
+        else {
+            lo |= rl << KBITS;
+            if (KBITS + SHIFT > 64) hi |= rl >> (64 - KBITS);
+        }
+    }
+    *lo_out = lo;
+    *hi_out = hi;
+}
+// The table-free sibling of expand_and_dedupe_words (k_insert_first, finding 19): the partition's instances are known to be
+// distinct, so every one of them is a new entry.  Keys only: no hash, nothing stored to LDS; li.won = the lane's slots in use.
+template <u32 NI, u32 NW, u32 KB, u32 SHIFT, u32 NIMAX>
+__device__ __forceinline__ void expand_words_distinct(u32 lane, u32 ninst, const u32* s_rw, const uint8_t* s_irec, LaneInst<NIMAX>& li) {
+    static_assert(NI <= NIMAX, "instances per lane");
+    u32 rix[NI];
+    u32 won = 0;
+#pragma unroll
+    for (u32 it = 0; it < NI; it++) {
+        const u32 i = it * 64 + lane;
+        rix[it] = s_irec[i < ninst ? i : 0];
+    }
+#pragma unroll
+    for (u32 it = 0; it < NI; it++) {
+        const u32 i = it * 64 + lane;
+        cut_key<NW, KB, SHIFT>(s_rw + rix[it] * RecGeom<NW>::RS, i, ninst, &li.klo[it], &li.khi[it]);
+        if (i < ninst) won |= 1u << it;
+    }
+    li.won = won;
+}
 // s_imult: every instance slot's multiplicity, mod 256 (SAT: clamped to 255; the chunk's records folded: section 4 finding 15)
 // (FOLD false: s_rmult, per record)
 template <u32 NI, u32 NW, u32 KB, u32 SHIFT, u32 NIMAX, bool FOLD, bool SAT>
 __device__ __forceinline__ void expand_and_dedupe_words(u32 lane, u32 ninst, u32 tsize, const u32* s_rw, const uint8_t* s_irec, const uint8_t* s_imult,
                                                         const u32* s_rmult, u64* s_key, u32* s_tab, u32* dbg_rounds, LaneInst<NIMAX>& li) {
-    constexpr u32 RS = RecGeom<NW>::RS, INFO = RecGeom<NW>::INFO, KBITS = 2 * KB + 6;
+    constexpr u32 RS = RecGeom<NW>::RS, KBITS = 2 * KB + 6;
     static_assert(KBITS + SHIFT <= 128 && SHIFT <= 6, "entry key: [routing id low bits | compacted k-mer | idx']");
     static_assert(NI <= NIMAX, "instances per lane");
     u64 (&klo)[NIMAX] = li.klo;
@@ -328,30 +378,8 @@ __device__ __forceinline__ void expand_and_dedupe_words(u32 lane, u32 ninst, u32
 #pragma unroll
     for (u32 it = 0; it < NI; it++) {
         const u32 i = it * 64 + lane;
-        const u32* base = s_rw + rix[it] * RS;
-        const u32 info = base[INFO];
-        const u32 j = i < ninst ? i - (info & 0x3ffu) : 0;
-        const u32 n = (info >> 10) & 0xffu;
-        const u32 s = 2 * (n - 1 - j);
-        const u32* wp = base + (s >> 5);
-        const u32 sh = s & 31;
-        const u32 w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3], w4 = wp[4];
-        u32 k0 = __builtin_amdgcn_alignbit(w1, w0, sh), k1 = __builtin_amdgcn_alignbit(w2, w1, sh);
-        u32 k2 = __builtin_amdgcn_alignbit(w3, w2, sh), k3 = __builtin_amdgcn_alignbit(w4, w3, sh);
-        k0 = (k0 & ~0x3fu) | (((info >> 18) & 0xffu) + j);  // idx' = idx0' + j (SuperKmerLight.hpp:98)
-        // keep the 2kb + 6 key bits, put the routing id's low bits on top
-        constexpr u32 m0 = KBITS >= 32 ? ~0u : (1u << KBITS) - 1, m1 = KBITS >= 64 ? ~0u : KBITS <= 32 ? 0u : (1u << (KBITS - 32)) - 1;
-        constexpr u32 m2 = KBITS >= 96 ? ~0u : KBITS <= 64 ? 0u : (1u << (KBITS - 64)) - 1, m3 = KBITS >= 128 ? ~0u : KBITS <= 96 ? 0u : (1u << (KBITS - 96)) - 1;
-        k0 &= m0; k1 &= m1; k2 &= m2; k3 &= m3;
-        u64 lo = ((u64)k1 << 32) | k0, hi = ((u64)k3 << 32) | k2;
-        if (SHIFT) {
-            const u64 rl = (info >> 26) & ((1u << SHIFT) - 1);
-            if (KBITS >= 64) hi |= rl << (KBITS - 64);
-            else {
-                lo |= rl << KBITS;
-                if (KBITS + SHIFT > 64) hi |= rl >> (64 - KBITS);
-            }
-        }
+        u64 lo, hi;
+        cut_key<NW, KB, SHIFT>(s_rw + rix[it] * RS, i, ninst, &lo, &hi);
         klo[it] = lo;
         khi[it] = hi;
         hh[it] = hash_key32(mk128(lo, hi)) & (tsize - 1);
@@ -479,10 +507,33 @@ __device__ __forceinline__ u64 readlane64(u64 v, u32 a) {
 // its head too), and every open record it contains folds into it.  Returns whether this lane's record folded; *lead: the
 // lane of its head (its own lane otherwise), *off: its idx0' minus the head's.  Identical records fold into the lowest lane
 // of them, so no separate record-level de-duplication is needed.
-template <u32 NW>
-__device__ __forceinline__ bool fold_records(const FoldFrame& f, u32 nrec, u32 lane, u32* lead, u32* off, u32* trips) {
+//
+// DETECT (k_insert_first, section 4 finding 19): *clean comes back true only where the rounds PROVE that no two k-mer instances
+// of the surviving records have equal keys.  Two records can share a key only if their routing ids are equal, their idx'
+// ranges intersect and their strings agree on a whole window of the intersection; every window of an idx' in
+// [suff_reduc, suff_reduc + w] covers the frame's nucleotides [w, k - b) (the core: fold_core), so records that differ there
+// share none.  The caller hands every record's `ck`, [routing id low bits | core] -- a partition's records differ in nothing
+// else of the routing id -- so "same routing id and core" is one 32-bit compare.  In the round of head A every record still
+// open after the containment test whose ck is A's and whose range meets A's clears *clean; so does a record still open after
+// the last round (those were never compared with each other), and one `unsure` on entry (outside the frame, or below
+// suff_reduc: the caller says).  Why that is enough: every pair of survivors was compared in the round in which the earlier of
+// the two was head (the later one was open then: a survivor closes only as a head), a folded record adds no instances, and
+// within one record the idx' differ.  The cost per round is one v_readlane and the compare; the lanes' findings add up in one
+// register, and one test after the rounds reads it.
+template <u32 KB, u32 CW>
+__device__ __forceinline__ u32 fold_core(const W4& u) {  // the frame bits [2 CW, 2 KB) every k-mer window covers (CW = k - m, KB = k - b)
+    constexpr u32 LO = 2 * CW, N = 2 * (KB - CW), WI = LO / 64, BI = LO % 64;
+    static_assert(CW < KB && N <= 28 && LO + N <= 256, "the core: the minimizer's nucleotides that are not cut out, m - b of them");
+    const u64 w[5] = {u.w0, u.w1, u.w2, u.w3, 0};
+    u64 v = w[WI] >> BI;
+    if (BI + N > 64) v |= w[WI + 1] << (64 - BI);
+    return (u32)v & ((1u << N) - 1);
+}
+template <u32 NW, bool DETECT = false>
+__device__ __forceinline__ bool fold_records(const FoldFrame& f, u32 nrec, u32 lane, u32* lead, u32* off, u32* trips, u32 ck = 0, bool unsure = false, bool* clean = nullptr) {
     u32 sv = lane < nrec ? f.s : 0;
     bool folded = false;
+    u32 dirty = unsure;
     *lead = lane;
     *off = 0;
     for (u32 t = 0; t < WI_FOLD_TRIPS; t++) {
@@ -510,7 +561,13 @@ __device__ __forceinline__ bool fold_records(const FoldFrame& f, u32 nrec, u32 l
                 *off = i0 - i0a;
             }
         }
+        if (DETECT) {  // (what is still open is neither the head nor contained in it)
+            const u32 differs = ck ^ (u32)__builtin_amdgcn_readlane((int)ck, (int)a);
+            const u32 meets = ((i0 - ea) & (i0a - e)) >> 31;  // 1: i0 < ea && i0a < e (all below 256)
+            dirty |= (differs == 0 && sv != 0) ? meets : 0u;
+        }
     }
+    if (DETECT) *clean = !__any((dirty | sv) != 0);
     return folded;
 }
 
@@ -1083,10 +1140,16 @@ __device__ __forceinline__ unsigned long long first_lane64(unsigned long long v)
 }
 template <u32 NIL, u32 NW, u32 KB, u32 SHIFT, bool SAT>
 __device__ __forceinline__ void insert_first_body(const BriskParams& P, const RecSrc& src, const PartDesc* __restrict__ desc, u32 n_touched, const IndexDev& ix,
-                                                  u32* __restrict__ work_counter, u32* __restrict__ left_list, u32* __restrict__ n_left) {
+                                                  u32* __restrict__ work_counter, u32* __restrict__ left_list, u32* __restrict__ n_left, u32* __restrict__ n_clean) {
     using L = LeanLds<NIL, NW>;
     constexpr u32 MAXI = L::MAXI, TABLE = L::TABLE, RS = RecGeom<NW>::RS, INFO = RecGeom<NW>::INFO, KBITS = 2 * KB + 6;
     constexpr u32 KW = KBITS + SHIFT <= 64 ? 1u : 2u;
+    // The table-free path (finding 19): where the fold proves that a partition's instances are all distinct (fold_records, DETECT),
+    // instance i is entry i with the multiplicity s_imult holds -- what the probe table yields for it, every instance winning its
+    // slot -- and hashing, the key copies in LDS, the table, its rounds and the ranking are left out.  The core mask is the
+    // flagship geometry's: k63 m21 b14 (any other m with k - b = 49 takes the table path); n_clean == nullptr switches the path off.
+    constexpr u32 CORE_K = 63, CORE_M = 21, CORE_B = 14, CW = CORE_K - CORE_M;
+    static_assert(KB == CORE_K - CORE_B, "fold_core: the core of k63 m21 b14");
     static_assert(NIL == 2 || NIL == 3, "instance slots per lane");
     static_assert(NW >= 3 && SHIFT < 5, "the folding k63 geometries: at most 16 buckets per partition");
     static_assert(L::BYTES <= 13 * 512, "LDS per wave: 24 waves must fit a CU's 160 KiB");
@@ -1105,6 +1168,8 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
     // the wave's private arena chunk: wave-uniform, in scalar registers
     unsigned long long acur = first_lane64(ix.slot_cur[blockIdx.x]), aend = first_lane64(ix.slot_end[blockIdx.x]), garbage = 0;
     const u32 frame_end = P.suff_reduc + P.w + 1;
+    // the idx' from which on a window covers the core; beyond every idx' (no record is sure, no partition table-free) where the path is off
+    const u32 core_from = (n_clean != nullptr && P.w == CW) ? P.suff_reduc : 0x100u;
 
     for (;;) {
         u32 t0 = 0;
@@ -1113,6 +1178,7 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
         if (t0 >= n_touched) break;
         const u32 t_end = min(t0 + WI_BATCH, n_touched);
         unsigned long long left_mask = 0;  // partitions t0 + i of this batch that are left to k_insert_fast (wave-uniform)
+        unsigned long long clean_mask = 0;  // those that took the table-free path (counted for the trace)
         PartDesc d = desc[t0];
         RecRegs rr = load_part_recs(P, src, d.part, d.r_begin, d.r_begin, min(d.n_rec, (u32)WI_MAX_REC), lane);
 
@@ -1139,7 +1205,14 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                 wave_sync();  // the previous partition has read its table
                 if (lane < nrec) store_rec_words<NW>(s_rw + lane * RS, rr, 0);
                 u32 lead = lane, lead_off = 0, dbg_trips = 0;
-                const bool dup = fold_records<NW>(ff, nrec, lane, &lead, &lead_off, &dbg_trips);
+                // (a record that takes no part in the fold, or reaches below suff_reduc: its windows may miss the core)
+                const bool unsure = lane < nrec && (ff.s == 0 || hdr_idx0(my_hdr) < core_from);
+                bool clean = false;
+                const u32 ck = ((hdr_bucket(my_hdr) & ((1u << SHIFT) - 1)) << (2 * (KB - CW))) | fold_core<KB, CW>(ff.u);
+                const bool dup = fold_records<NW, true>(ff, nrec, lane, &lead, &lead_off, &dbg_trips, ck, unsure, &clean);
+#ifdef INSERT_ATTR_NOTABLE  // attribution build: every partition taken goes down the table-free path.  Wrong results, timing only
+                clean = true;
+#endif
                 const u32 my_n = (lane < nrec && !dup) ? raw_n : 0;
                 const u32 x = wave_incl_scan(my_n, lane);
                 const u32 ninst = (u32)__builtin_amdgcn_readlane((int)x, 63);
@@ -1213,24 +1286,43 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                 u32 dbg_r = 0;
                 LaneInst<NIL> li;
                 li.won = 0;
-                if (ninst <= 64) expand_and_dedupe_words<1, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
-                else if (NIL == 2 || ninst <= 128) expand_and_dedupe_words<2, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
-                else expand_and_dedupe_words<NIL, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
-                wave_sync();
-                CNT(8, dbg_r)
-                PHASE(3)
-                // ---- the new entries: every slot a lane created, ranked with one ballot per instance slot
                 u32 n_new = 0, new_rank[NIL], new_word[NIL];
+                if (clean) {  // wave-uniform: the table-free path.  Instance i is entry i, its count what s_imult holds
+                    clean_mask |= 1ull << (t - t0);
+                    // (the lane as this path sees it, opaque: what is derived from it here is computed here, not kept in registers
+                    // from before the partition loop, where the table path's own addresses already fill the 80)
+                    u32 ln = lane;
+                    asm volatile("" : "+v"(ln));
+                    if (ninst <= 64) expand_words_distinct<1, NW, KB, SHIFT, NIL>(ln, ninst, s_rw, s_irec, li);
+                    else if (NIL == 2 || ninst <= 128) expand_words_distinct<2, NW, KB, SHIFT, NIL>(ln, ninst, s_rw, s_irec, li);
+                    else expand_words_distinct<NIL, NW, KB, SHIFT, NIL>(ln, ninst, s_rw, s_irec, li);
+                    n_new = ninst;
 #pragma unroll
-                for (u32 it = 0; it < NIL; it++) {
-                    new_rank[it] = 0;
-                    new_word[it] = 0;
-                    if (it * 64 < ninst) {  // wave-uniform
-                        const bool made = (li.won >> it) & 1;
-                        if (made) new_word[it] = s_tab[li.hh[it]];
-                        const unsigned long long bal = __ballot(made);
-                        new_rank[it] = n_new + (u32)__popcll(bal & lanes_below(lane));
-                        n_new += (u32)__popcll(bal);
+                    for (u32 it = 0; it < NIL; it++) {
+                        const u32 i = it * 64 + ln;
+                        new_rank[it] = i;
+                        new_word[it] = (u32)s_imult[i < ninst ? i : 0] << WI_CNT_SHIFT;
+                    }
+                    PHASE(3)
+                } else {
+                    if (ninst <= 64) expand_and_dedupe_words<1, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
+                    else if (NIL == 2 || ninst <= 128) expand_and_dedupe_words<2, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
+                    else expand_and_dedupe_words<NIL, NW, KB, SHIFT, NIL, true, SAT>(lane, ninst, tsize, s_rw, s_irec, s_imult, nullptr, s_key, s_tab, &dbg_r, li);
+                    wave_sync();
+                    CNT(8, dbg_r)
+                    PHASE(3)
+                    // ---- the new entries: every slot a lane created, ranked with one ballot per instance slot
+#pragma unroll
+                    for (u32 it = 0; it < NIL; it++) {
+                        new_rank[it] = 0;
+                        new_word[it] = 0;
+                        if (it * 64 < ninst) {  // wave-uniform
+                            const bool made = (li.won >> it) & 1;
+                            if (made) new_word[it] = s_tab[li.hh[it]];
+                            const unsigned long long bal = __ballot(made);
+                            new_rank[it] = n_new + (u32)__popcll(bal & lanes_below(lane));
+                            n_new += (u32)__popcll(bal);
+                        }
                     }
                 }
                 wave_sync();
@@ -1290,8 +1382,12 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
             u32 at = 0;
             if (lane == 0) at = atomicAdd(n_left, n);
             at = (u32)__builtin_amdgcn_readfirstlane((int)at);
-            if ((left_mask >> lane) & 1) left_list[at + (u32)__popcll(left_mask & lanes_below(lane))] = t0 + lane;
+            // (once per batch: from an opaque copy of the lane, so that 1 << lane is not kept in two registers across every partition)
+            u32 ln = lane;
+            asm volatile("" : "+v"(ln));
+            if ((left_mask >> ln) & 1) left_list[at + (u32)__popcll(left_mask & lanes_below(ln))] = t0 + ln;
         }
+        if (clean_mask && n_clean && lane == 0) atomicAdd(n_clean, (u32)__popcll(clean_mask));
     }
     PHASE_FLUSH
     if (lane == 0) {
@@ -1303,8 +1399,8 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
 template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false, u32 NIL = NI_LEAN>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVES_PER_EU_FIRST, WI_WAVES_PER_EU_FIRST_MAX))) k_insert_first(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
                                                                                                           u32 n_touched, IndexDev ix, u32* __restrict__ work_counter,
-                                                                                                          u32* __restrict__ left_list, u32* __restrict__ n_left) {
-    insert_first_body<NIL, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter, left_list, n_left);
+                                                                                                          u32* __restrict__ left_list, u32* __restrict__ n_left, u32* __restrict__ n_clean) {
+    insert_first_body<NIL, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter, left_list, n_left, n_clean);
 }
 
 // bucket occupancy for partitions wider than 64 buckets (small part_bits): one pass over all entries

@@ -1,6 +1,8 @@
 """A/B timing of library variants: the same sources compiled with different -D flags, timed on the same workload.
     python tools/ab.py --build NAME[:-DFLAG[,-DFLAG...]] ...     (here: hipcc cross-compiles, variants in parallel)
     python tools/ab.py --run K M B READS [NAME ...]                (GPU box: every built variant, or the named ones; BRISK_AB_PART_BITS=N: brisk_hip_options.part_bits)
+    python tools/ab.py --make-density K READS E                    (GPU box, once: error-bearing reads of tests/density_reads.py at rate E into tests/_v;
+                                                                    BRISK_AB_DENSITY=1 then makes --one / --run insert those from the host instead)
 Variants live in tests/_v/libbrisk_ab_<NAME>.so (git-ignored, travel with gpurun).  Each is timed in its own process
 (the library is loaded once per process): synthetic reads resident on the device, one warm-up job, then two timed jobs;
 prints the per-kernel HIP-event times of the last job, the index digest (equal digests <=> equal multisets: a variant
@@ -29,6 +31,22 @@ if "--build" in sys.argv:
         rc = max(rc, r)
     sys.exit(rc)
 
+def density_file(k, reads):
+    return os.path.join(vdir, f"ab_density_k{k}_{reads}.npz")
+
+
+if "--make-density" in sys.argv:
+    at = sys.argv.index("--make-density")
+    k, reads, e = int(sys.argv[at + 1]), int(sys.argv[at + 2]), float(sys.argv[at + 3])
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+    from density_reads import dense_reads
+    os.makedirs(vdir, exist_ok=True)
+    flat, offs = dense_reads(reads, k, reads * 10, 1, e=e)  # coverage 15 at 150 nt, as the synthetic job's
+    np.savez(density_file(k, reads), flat=flat, offs=offs)
+    print("density reads:", len(offs) - 1, "sequences,", len(flat), "bases, e =", e)
+    sys.exit(0)
+
 if "--one" in sys.argv:
     at = sys.argv.index("--one")
     name, k, m, b, reads = sys.argv[at + 1], *[int(x) for x in sys.argv[at + 2:at + 6]]
@@ -42,6 +60,11 @@ if "--one" in sys.argv:
     L = ctypes.CDLL(lib(name))  # a library built from older sources (the parent's, as a base) lacks the test hooks added since
     hipapi.SYMBOLS[:] = [s for s in hipapi.SYMBOLS if hasattr(L, s)]
     dev = torch.device("cuda", 0)
+    host = None
+    if os.environ.get("BRISK_AB_DENSITY"):
+        import numpy as np
+        z = np.load(density_file(k, reads))
+        host = (z["flat"], z["offs"])
     d_packed = torch.zeros((reads * 150 + 15) // 16 + 4, dtype=torch.int32, device=dev)
     d_starts = torch.zeros(reads + 1, dtype=torch.int64, device=dev)
     torch.cuda.synchronize()  # torch fills on its own stream, the library works on another: the fill must have landed
@@ -54,7 +77,10 @@ if "--one" in sys.argv:
         ix.profile_reset(); ix.profile_enable(True)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ix.insert_packed(d_packed.data_ptr(), d_starts.data_ptr(), reads)
+        if host is not None:
+            ix.insert_flat(*host)
+        else:
+            ix.insert_packed(d_packed.data_ptr(), d_starts.data_ptr(), reads)
         ix.sync()
         wall = (time.perf_counter() - t0) * 1e3
         prof = ix.profile_read()
