@@ -17,6 +17,12 @@
 //                    the first kept by --intersect) before --histo, --min-count / --max-count and the dump take effect; one line on stderr
 //                    per operation with the entries added / removed.  A FILE that is a snapshot (recognised by its magic) is loaded
 //                    (brisk_hip_load) instead of counted
+//   --filter-joint FILE --window SLO:SHI:OLO:OHI[:absent]   after --merge / --subtract / --intersect and before the prune: FILE becomes a
+//                    second index as theirs does, and the first keeps the entries whose count is in SLO..SHI and whose count in the second
+//                    is in OLO..OHI -- with ":absent" also those the second does not hold (brisk_hip_filter_joint); OLO > OHI: only those
+//   --joint FILE --joint-histo OUT   after load, set operations and a --min-count / --max-count prune: the joint count spectrum of the final
+//                    index and FILE's (brisk_hip_joint_spectrum): one line "state_self<TAB>state_other<TAB>entries" per non-zero bin,
+//                    ascending by self, then by other; a state is a stored count, or -1 for "not in that index", which sorts last
 //   --load FILE      start from the snapshot FILE (brisk_hip_load, slices with room to grow) instead of the empty index, and count FASTA on
 //                    top; a FASTA of "-" means no reads.  k m b must be the file's (exit status 2 otherwise)
 //   --save FILE      write the final index -- after counting, the set operations and, if given, --min-count / --max-count applied as
@@ -183,9 +189,13 @@ int main(int argc_in, char** argv_in) {
     bool saturate = false;
     const char* const setop_names[3] = {"--merge", "--subtract", "--intersect"};  // in the order they are applied
     const char* setop_file[3] = {nullptr, nullptr, nullptr};
+    const char* joint_file = nullptr;
+    const char* joint_histo = nullptr;
+    const char* filter_joint_file = nullptr;
+    const char* window_text = nullptr;
     static const char* const usage =
         "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] "
-        "[--subtract FILE] [--intersect FILE] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]] "
+        "[--subtract FILE] [--intersect FILE] [--filter-joint FILE --window SLO:SHI:OLO:OHI[:absent]] [--joint FILE --joint-histo OUT] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]] "
         "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]]; FASTA \"-\": no reads; a FILE may be a snapshot)\n"
         "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+";
     for (int i = 0; i < argc_in; i++) {
@@ -202,7 +212,8 @@ int main(int argc_in, char** argv_in) {
             if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
         const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count") ||
                                     !strcmp(argv_in[i], "--profile") || !strcmp(argv_in[i], "--solid") || !strcmp(argv_in[i], "--extract") || !strcmp(argv_in[i], "--rule") ||
-                                    !strcmp(argv_in[i], "--min-len"));
+                                    !strcmp(argv_in[i], "--min-len") || !strcmp(argv_in[i], "--joint") || !strcmp(argv_in[i], "--joint-histo") || !strcmp(argv_in[i], "--filter-joint") ||
+                                    !strcmp(argv_in[i], "--window"));
         if (!named) {
             args.push_back(argv_in[i]);
             continue;
@@ -218,6 +229,10 @@ int main(int argc_in, char** argv_in) {
         else if (!strcmp(opt, "--profile")) profile_file = argv_in[i];
         else if (!strcmp(opt, "--extract")) extract_file = argv_in[i];
         else if (!strcmp(opt, "--rule")) rule_text = argv_in[i];
+        else if (!strcmp(opt, "--joint")) joint_file = argv_in[i];
+        else if (!strcmp(opt, "--joint-histo")) joint_histo = argv_in[i];
+        else if (!strcmp(opt, "--filter-joint")) filter_joint_file = argv_in[i];
+        else if (!strcmp(opt, "--window")) window_text = argv_in[i];
         else if (!strcmp(opt, "--min-len")) {
             char* end = nullptr;
             min_len = strtol(argv_in[i], &end, 10);
@@ -255,8 +270,8 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop || save_file || load_file || profile_file || have_solid || saturate || extract_file || rule_text || min_len) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --save, --load, --profile, --solid, --extract, --rule and --min-len work on the device "
+    if ((histo || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || extract_file || rule_text || min_len) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule and --min-len work on the device "
                      "index: --bulk only" << std::endl;
         return 2;
     }
@@ -267,6 +282,31 @@ int main(int argc_in, char** argv_in) {
     if ((rule_text || min_len) && !extract_file) {
         std::cerr << "--rule and --min-len belong to --extract FILE" << std::endl;
         return 2;
+    }
+    if (!joint_file != !joint_histo) {
+        std::cerr << "--joint FILE and --joint-histo OUT come together" << std::endl;
+        return 2;
+    }
+    if (!filter_joint_file != !window_text) {
+        std::cerr << "--filter-joint FILE and --window SLO:SHI:OLO:OHI[:absent] come together" << std::endl;
+        return 2;
+    }
+    brisk_hip_joint_window window{};
+    if (window_text) {  // SLO:SHI:OLO:OHI or SLO:SHI:OLO:OHI:absent
+        unsigned long v[4] = {0, 0, 0, 0};
+        int used = 0;
+        const bool four = sscanf(window_text, "%lu:%lu:%lu:%lu%n", &v[0], &v[1], &v[2], &v[3], &used) == 4;
+        const char* tail = four ? window_text + used : "?";
+        const bool digits_only = strspn(window_text, "0123456789:") >= (size_t)used;  // (no sign, no blank: sscanf would take them)
+        if (!four || !digits_only || (*tail && strcmp(tail, ":absent")) || std::max(std::max(v[0], v[1]), std::max(v[2], v[3])) > 255 || v[0] > v[1] || (v[2] > v[3] && !*tail)) {
+            std::cerr << "--window: SLO:SHI:OLO:OHI[:absent] with counts 0..255, SLO <= SHI, and OLO <= OHI unless :absent is given; got " << window_text << std::endl;
+            return 2;
+        }
+        window.min_self = (uint32_t)v[0];
+        window.max_self = (uint32_t)v[1];
+        window.min_other = (uint32_t)v[2];
+        window.max_other = (uint32_t)v[3];
+        window.keep_absent = *tail ? 1 : 0;
     }
     brisk_hip_select_rule rule{};
     rule.struct_size = sizeof rule;
@@ -418,25 +458,32 @@ int main(int argc_in, char** argv_in) {
                     std::cout << "}}" << std::endl;
                 }
             }
-            for (int q = 0; q < 3; q++) {  // --merge, --subtract, --intersect: FILE counted into a second index, then combined on the device
-                if (!setop_file[q]) continue;
+            // FILE of a set operation counted (or, a snapshot, loaded) into a second index of the same parameters; 0 or the exit status
+            auto second_index = [&](const char* opt, const char* file, brisk_hip_index** out) -> int {
                 brisk_hip_index* other = nullptr;
-                rc = brisk_hip_create(&other, k, m, b, 1, params.dede->coef(), &o);
-                if (rc != BRISK_HIP_OK) {
-                    std::cerr << setop_names[q] << ": brisk_hip_create failed: " << rc << std::endl;
+                const int crc = brisk_hip_create(&other, k, m, b, 1, params.dede->coef(), &o);
+                if (crc != BRISK_HIP_OK) {
+                    std::cerr << opt << ": brisk_hip_create failed: " << crc << std::endl;
                     return 1;
                 }
-                if (is_snapshot(setop_file[q])) {  // the second index from its snapshot: compact, it only serves this operation
-                    if (int lrc = load_snapshot(other, setop_names[q], setop_file[q], k, m, b, BRISK_HIP_LOAD_COMPACT)) return lrc;
+                if (is_snapshot(file)) {  // the second index from its snapshot: compact, it only serves this operation
+                    if (int lrc = load_snapshot(other, opt, file, k, m, b, BRISK_HIP_LOAD_COMPACT)) return lrc;
                 } else {
-                    FastaBatcher batches(setop_file[q], batch_bases);
+                    FastaBatcher batches(file, batch_bases);
                     FastaBatch bt;
                     while (batches.next(bt))
-                        if ((rc = brisk_hip_insert_reads(other, bt.flat.data(), bt.offs.data(), bt.size())) != BRISK_HIP_OK) {
-                            std::cerr << setop_names[q] << ": " << brisk_hip_last_error(other) << std::endl;
+                        if (brisk_hip_insert_reads(other, bt.flat.data(), bt.offs.data(), bt.size()) != BRISK_HIP_OK) {
+                            std::cerr << opt << ": " << brisk_hip_last_error(other) << std::endl;
                             return 1;
                         }
                 }
+                *out = other;
+                return 0;
+            };
+            for (int q = 0; q < 3; q++) {  // --merge, --subtract, --intersect: FILE counted into a second index, then combined on the device
+                if (!setop_file[q]) continue;
+                brisk_hip_index* other = nullptr;
+                if (int src = second_index(setop_names[q], setop_file[q], &other)) return src;
                 uint64_t changed = 0;
                 rc = q == 0 ? brisk_hip_merge(h, other, &changed) : q == 1 ? brisk_hip_subtract(h, other, &changed) : brisk_hip_intersect(h, other, BRISK_HIP_COUNT_LEFT, &changed);
                 if (rc != BRISK_HIP_OK) {
@@ -447,13 +494,50 @@ int main(int argc_in, char** argv_in) {
                 brisk_hip_destroy(other);
                 brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
             }
-            if ((save_file || profile_file || extract_file) && have_range) {  // the final index: what the dump below shows is what the file holds and what the reads are profiled against
+            if (filter_joint_file) {
+                brisk_hip_index* other = nullptr;
+                if (int src = second_index("--filter-joint", filter_joint_file, &other)) return src;
+                uint64_t gone = 0;
+                if (brisk_hip_filter_joint(h, other, &window, &gone) != BRISK_HIP_OK) {
+                    std::cerr << "--filter-joint: " << brisk_hip_last_error(h) << std::endl;
+                    return 1;
+                }
+                std::cerr << "filter-joint " << filter_joint_file << " " << window_text << ": " << gone << " entries removed" << std::endl;
+                brisk_hip_destroy(other);
+                brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+            }
+            if ((save_file || profile_file || extract_file || joint_file) && have_range) {  // the final index: what the dump below shows is what the file holds and what the reads are profiled against
                 uint64_t gone = 0;
                 if (brisk_hip_prune(h, (uint32_t)min_count, (uint32_t)max_count, &gone) != BRISK_HIP_OK) {
-                    std::cerr << (save_file ? "--save" : profile_file ? "--profile" : "--extract") << ": prune: " << brisk_hip_last_error(h) << std::endl;
+                    std::cerr << (save_file ? "--save" : profile_file ? "--profile" : extract_file ? "--extract" : "--joint") << ": prune: " << brisk_hip_last_error(h) << std::endl;
                     return 1;
                 }
                 brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+            }
+            if (joint_file) {  // the final index against FILE's: one line per non-zero bin, absent (-1) last on both axes
+                brisk_hip_index* other = nullptr;
+                if (int src = second_index("--joint", joint_file, &other)) return src;
+                std::vector<uint64_t> joint((size_t)BRISK_HIP_JOINT_STATES * BRISK_HIP_JOINT_STATES);
+                if (brisk_hip_joint_spectrum(h, other, joint.data()) != BRISK_HIP_OK) {
+                    std::cerr << "--joint: " << brisk_hip_last_error(h) << std::endl;
+                    return 1;
+                }
+                brisk_hip_destroy(other);
+                std::ofstream out(joint_histo);
+                uint64_t bins = 0;
+                for (uint32_t sa = 0; sa < BRISK_HIP_JOINT_STATES; sa++)
+                    for (uint32_t sb = 0; sb < BRISK_HIP_JOINT_STATES; sb++) {
+                        const uint64_t n = joint[(size_t)sa * BRISK_HIP_JOINT_STATES + sb];
+                        if (!n) continue;
+                        out << (sa == BRISK_HIP_JOINT_ABSENT ? -1 : (int)sa) << "\t" << (sb == BRISK_HIP_JOINT_ABSENT ? -1 : (int)sb) << "\t" << n << "\n";
+                        bins++;
+                    }
+                out.close();
+                if (!out) {
+                    std::cerr << "--joint-histo " << joint_histo << ": write failed" << std::endl;
+                    return 1;
+                }
+                std::cerr << "joint " << joint_file << ": " << bins << " non-zero bins" << std::endl;
             }
             if (save_file) {
                 uint64_t written = 0;

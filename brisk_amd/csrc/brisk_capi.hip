@@ -2871,6 +2871,20 @@ int join_remove(brisk_hip_index* h, brisk_hip_index* src, u32 op, u32 rule, uint
     if ((rc = launch_join(h, src, op, rule, h->d_ctr->result.w))) return rc;
     return after_removal(h, removed);
 }
+int launch_joint(brisk_hip_index* h, brisk_hip_index* src, u32 op, const JointWindow& w, unsigned long long* d_out) {
+    // persistent waves, as many as launch_join's; the spectrum's come JS_WAVES to a block
+    const u32 waves = op == JOINT_SPECTRUM ? JS_WAVES : 1;
+    const dim3 grid((u32)((std::min<u64>(h->n_parts, 16384) + waves - 1) / waves)), block(64 * waves);
+#define LAUNCH_JOINT(OP)                                                                                                                         \
+    {                                                                                                                                            \
+        if (h->ix.key_words == 1) hipLaunchKernelGGL((k_joint<OP, 1>), grid, block, 0, h->stream, h->ix, src->ix, (u32)h->n_parts, w, d_out);  \
+        else hipLaunchKernelGGL((k_joint<OP, 2>), grid, block, 0, h->stream, h->ix, src->ix, (u32)h->n_parts, w, d_out);                       \
+    }
+    if (op == JOINT_FILTER) LAUNCH_JOINT(JOINT_FILTER)
+    else LAUNCH_JOINT(JOINT_SPECTRUM)
+#undef LAUNCH_JOINT
+    return launch_check(h, "k_joint");
+}
 // nb_kmers: the directory reduction of brisk_hip_stats
 int dir_entries(brisk_hip_index* h, u64* out) {
     HIPCHK(h, hipMemsetAsync(h->ix.stats, 0, 24, h->stream));
@@ -2917,6 +2931,57 @@ BRISK_API int brisk_hip_compare(brisk_hip_index* a, brisk_hip_index* b, uint64_t
     HIPCHK(h, hipMemcpyAsync(out, d_out, 6 * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BRISK_HIP_OK;
+}
+
+// The joint count spectrum: k_joint counts every entry of a -- rows 0..255, matched or (sa, absent) -- and k_spectrum counts b.
+// Row `absent` is what is left of b's spectrum once the matched pairs of each column are taken out: 256 subtractions on the
+// host, after the one copy (k_joint keeps match state per entry of a, and a scratch byte per entry of b would be arena-sized).
+BRISK_API int brisk_hip_joint_spectrum(brisk_hip_index* a, brisk_hip_index* b, uint64_t* out) {
+    if (!a || !b || a == b) return fail(a, BRISK_HIP_EINVAL, "joint_spectrum: two different handles are needed");
+    if (!out) return fail(a, BRISK_HIP_EINVAL, "joint_spectrum: out is null");
+    if (int rc = setop_enter(a, b, "joint_spectrum")) return rc;
+    std::lock_guard<std::recursive_mutex> lock_a(a->call_mu, std::adopt_lock), lock_b(b->call_mu, std::adopt_lock);
+    brisk_hip_index* h = a;
+    int rc;
+    const u64 S = BRISK_HIP_JOINT_STATES, n_bins = S * S;
+    if ((rc = ensure(h, h->enum_out, (n_bins + 256) * 8))) return rc;  // (enumeration scratch, free between calls)
+    unsigned long long* d_out = (unsigned long long*)h->enum_out.p;
+    unsigned long long* d_hist = d_out + n_bins;
+    HIPCHK(h, hipMemsetAsync(d_out, 0, (n_bins + 256) * 8, h->stream));
+    if ((rc = launch_joint(h, b, JOINT_SPECTRUM, JointWindow{0, 255, 0, 255, 1}, d_out))) return rc;
+    const u64 n_groups = (b->n_parts + 63) / 64;
+    hipLaunchKernelGGL(k_spectrum, dim3((u32)std::min<u64>(nblocks(n_groups, 4), 2048)), dim3(256), 0, h->stream, b->ix, (u32)b->n_parts, d_hist);
+    if ((rc = launch_check(h, "k_spectrum"))) return rc;
+    uint64_t spec_b[256];
+    HIPCHK(h, hipMemcpyAsync(out, d_out, n_bins * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(spec_b, d_hist, sizeof(spec_b), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (u64 sb = 0; sb < 256; sb++) {
+        uint64_t matched = 0;
+        for (u64 sa = 0; sa < 256; sa++) matched += out[sa * S + sb];
+        out[BRISK_HIP_JOINT_ABSENT * S + sb] = spec_b[sb] - matched;
+    }
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_filter_joint(brisk_hip_index* dst, brisk_hip_index* src, const brisk_hip_joint_window* w, uint64_t* removed) {
+    if (!dst || !src || dst == src) return fail(dst, BRISK_HIP_EINVAL, "filter_joint: two different handles are needed");
+    if (!w) return fail(dst, BRISK_HIP_EINVAL, "filter_joint: the window is null");
+    if (w->reserved) return fail(dst, BRISK_HIP_EINVAL, "filter_joint: reserved must be 0");
+    if (w->min_self > w->max_self) return fail(dst, BRISK_HIP_EINVAL, "filter_joint: min_self > max_self");
+    const bool no_present = w->min_other > w->max_other;
+    if (no_present && !w->keep_absent) return fail(dst, BRISK_HIP_EINVAL, "filter_joint: nothing can pass (min_other > max_other and keep_absent == 0)");
+    if (int rc = setop_enter(dst, src, "filter_joint")) return rc;
+    std::lock_guard<std::recursive_mutex> lock_dst(dst->call_mu, std::adopt_lock), lock_src(src->call_mu, std::adopt_lock);
+    if (removed) *removed = 0;
+    // (counts are bytes: a bound above 255 is 255)
+    const auto b255 = [](uint32_t v) { return std::min<u32>(v, 255u); };
+    const JointWindow jw{b255(w->min_self), b255(w->max_self), no_present ? 1u : b255(w->min_other), no_present ? 0u : b255(w->max_other), w->keep_absent ? 1u : 0u};
+    brisk_hip_index* h = dst;
+    int rc;
+    HIPCHK(h, zero_ctr(h, &h->d_ctr->result.w[0]));
+    if ((rc = launch_joint(h, src, JOINT_FILTER, jw, h->d_ctr->result.w))) return rc;
+    return after_removal(h, removed);
 }
 
 // merge: src's entries as one-k-mer records with their counts as multiplicities (k_entries_to_records), through dst's insert in

@@ -104,6 +104,14 @@ class _SnapshotInfo(C.Structure):
                [(n, C.c_uint64) for n in ("n_entries", "n_partitions", "nb_skmers")] + [("checksum", C.c_uint64 * 3), ("n_blocks", C.c_uint64), ("file_bytes", C.c_uint64), ("count_mode", C.c_uint32)]
 
 
+class _JointWindow(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("min_self", "max_self", "min_other", "max_other", "keep_absent", "reserved")]
+
+
+# brisk_hip_joint_spectrum: the state "not in that index", and the edge of the matrix
+JOINT_ABSENT = 256
+JOINT_STATES = 257
+
 _u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 
@@ -117,7 +125,7 @@ SYMBOLS = [
     "brisk_hip_read_profile_reads", "brisk_hip_read_profile_packed",
     "brisk_hip_scan_kmers", "brisk_hip_record_kmers", "brisk_hip_answer_records", "brisk_hip_place_answers", "brisk_hip_profile_slots",
     "brisk_hip_select_intervals", "brisk_hip_extract_packed", "brisk_hip_trim_packed", "brisk_hip_trim_reads", "brisk_hip_unpack_ascii",
-    "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
+    "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_joint_spectrum", "brisk_hip_filter_joint", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
     "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
 ]
@@ -195,6 +203,8 @@ def load() -> C.CDLL:
     L.brisk_hip_intersect.argtypes = [vp, vp, u32, C.POINTER(u64)]
     L.brisk_hip_subtract.argtypes = [vp, vp, C.POINTER(u64)]
     L.brisk_hip_compare.argtypes = [vp, vp, _u64p]
+    L.brisk_hip_joint_spectrum.argtypes = [vp, vp, vp]
+    L.brisk_hip_filter_joint.argtypes = [vp, vp, C.POINTER(_JointWindow), C.POINTER(u64)]
     L.brisk_hip_snapshot_info_read.argtypes = [C.c_char_p, C.POINTER(_SnapshotInfo)]
     L.brisk_hip_save.argtypes = [vp, C.c_char_p, C.POINTER(u64)]
     L.brisk_hip_load.argtypes = [vp, C.c_char_p, u32, C.POINTER(u64)]
@@ -316,6 +326,48 @@ def intervals_from_profile(profile, k: int, rule) -> np.ndarray:
     out["start"] = np.where(keep, start, 0)
     out["len"] = np.where(keep, length, 0)
     return out
+
+
+def joint_spectrum_from_entries(dump_a, dump_b) -> np.ndarray:
+    """BriskHip.joint_spectrum on the host, from two (lo, hi, minimizer_idx, count) tuples as BriskHip.enumerate returns them: the
+    definition, written out; no device needed.  The identity of an entry is (hi, lo, minimizer_idx) -- the same k-mer under two
+    minimizer positions is two identities -- and each dump holds an identity once."""
+    def keyed(dump):
+        lo, hi, idx, cnt = (np.asarray(x) for x in dump)
+        key = np.zeros(len(lo), np.dtype([("hi", "<u8"), ("lo", "<u8"), ("idx", "u1")]))
+        key["hi"], key["lo"], key["idx"] = hi, lo, idx
+        return key, cnt.astype(np.int64)
+    (ka, ca), (kb, cb) = keyed(dump_a), keyed(dump_b)
+    out = np.zeros((JOINT_STATES, JOINT_STATES), np.uint64)
+    _, ia, ib = np.intersect1d(ka, kb, assume_unique=True, return_indices=True)
+    in_b = np.full(len(ka), JOINT_ABSENT, np.int64)  # every entry of a: its state in b
+    in_b[ia] = cb[ib]
+    np.add.at(out, (ca, in_b), 1)
+    only_b = np.ones(len(kb), bool)
+    only_b[ib] = False
+    np.add.at(out, (np.full(int(only_b.sum()), JOINT_ABSENT), cb[only_b]), 1)
+    return out
+
+
+def joint_figures(joint, k: int, solid_min: int = 2) -> dict:
+    """The usual figures off a joint spectrum, `self` (rows) read as the assembly and `other` (columns) as the reads -- host
+    arithmetic only.  shared / only_self / only_other: entries in both, only in self, only in other.  completeness: the entries
+    of other with count >= solid_min that are present in self, over all entries of other with count >= solid_min (nan when there
+    are none).  error_rate = 1 - (1 - only_self / entries_of_self) ** (1 / k): the per-base error that would leave that share of
+    self's k-mers without support (nan for an empty self); qv = -10 log10(error_rate), inf at 0.  Everything counts DISTINCT
+    entries, not multiplicities: an entry seen 40 times weighs what an entry seen once does."""
+    J = np.asarray(joint)
+    if J.shape != (JOINT_STATES, JOINT_STATES):
+        raise ValueError(f"a joint spectrum is {JOINT_STATES} x {JOINT_STATES}, not {J.shape}")
+    A = JOINT_ABSENT
+    shared, only_self, only_other = int(J[:A, :A].sum()), int(J[:A, A].sum()), int(J[A, :A].sum())
+    lo = min(max(int(solid_min), 0), A)
+    solid, solid_in_self = int(J[:, lo:A].sum()), int(J[:A, lo:A].sum())
+    entries_self = shared + only_self
+    error_rate = 1.0 - (1.0 - only_self / entries_self) ** (1.0 / k) if entries_self else float("nan")
+    qv = float("inf") if error_rate == 0 else -10.0 * math.log10(error_rate) if error_rate > 0 else float("nan")
+    return dict(shared=shared, only_self=only_self, only_other=only_other, completeness=solid_in_self / solid if solid else float("nan"),
+                error_rate=error_rate, qv=qv)
 
 
 def snapshot_info(path) -> dict:
@@ -538,6 +590,31 @@ class BriskHip:
         out = np.zeros(6, np.uint64)
         self._chk(self.L.brisk_hip_compare(self.h, other.h, out))
         return dict(zip(("both", "only_self", "only_other", "sum_min", "sum_self", "sum_other"), (int(x) for x in out)))
+
+    def joint_spectrum(self, other: "BriskHip") -> np.ndarray:
+        """read-only: uint64[257, 257], J[sa, sb] = identities whose state here is sa and in `other` sb; a state is the stored
+        count (0..255) or JOINT_ABSENT = 256, "not in that index" (a wrapped count of 0 is present: state 0).  J[256, 256] is 0.
+        Rows 0..255 sum to self.count_spectrum(), columns 0..255 to other's; joint_figures reads completeness and QV off it."""
+        out = np.zeros((JOINT_STATES, JOINT_STATES), np.uint64)
+        self._chk(self.L.brisk_hip_joint_spectrum(self.h, other.h, out.ctypes.data))
+        return out
+
+    def filter_joint(self, other: "BriskHip", min_self: int = 0, max_self: int = 255, min_other: int = 0, max_other: int = 255, keep_absent: bool = False) -> int:
+        """keep the entries whose count here is in [min_self, max_self] and whose identity is in `other` with a count in
+        [min_other, max_other] -- or, with keep_absent, is not in `other` at all; counts stay; returns how many entries were
+        removed.  min_other > max_other: no entry that `other` holds passes (with keep_absent: subtract).  A bound above 255 means 255."""
+        bounds = (min_self, max_self, min_other, max_other)
+        for v in bounds:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError(f"a count bound must be a non-negative integer, not {v!r}")
+        if min_self > max_self:
+            raise ValueError("min_self > max_self")
+        if min_other > max_other and not keep_absent:
+            raise ValueError("nothing can pass: min_other > max_other and keep_absent is false")
+        w = _JointWindow(*(min(int(v), 0xffffffff) for v in bounds), 1 if keep_absent else 0, 0)
+        v = C.c_uint64()
+        self._chk(self.L.brisk_hip_filter_joint(self.h, other.h, C.byref(w), C.byref(v)))
+        return v.value
 
     # ---- snapshots (brisk_hip_save / brisk_hip_load): the index to a file and back, entries as stored
     def save(self, path) -> int:

@@ -67,6 +67,9 @@
  *   brisk_hip_merge / brisk_hip_intersect / brisk_hip_subtract / brisk_hip_compare
  *                               no reference counterpart (the reference holds one index; kmc_tools and jellyfish merge are
  *                               the usual tools): two indexes of one geometry combined on the device, partition by partition
+ *   brisk_hip_joint_spectrum / brisk_hip_filter_joint
+ *                               no reference counterpart (kat comp and Merqury's spectra-cn are the usual tools): the histogram
+ *                               of (count in a, count in b) with "absent" a state of its own, and the index filtered by both counts
  *   brisk_hip_save / brisk_hip_load / brisk_hip_snapshot_info_read
  *                               no reference counterpart (the reference's index lives as long as its process; jellyfish and KMC
  *                               keep their databases on disk): the directory and the live entries, as stored, to a file and back
@@ -429,6 +432,37 @@ int brisk_hip_subtract(brisk_hip_index *dst, brisk_hip_index *src, uint64_t *rem
 /* read-only. out[0] entries in both, out[1] only in a, out[2] only in b,
  * out[3] sum over shared of min(count_a, count_b), out[4] sum of count_a over shared, out[5] sum of count_b over shared */
 int brisk_hip_compare(brisk_hip_index *a, brisk_hip_index *b, uint64_t out[6]);
+
+/* ---- the joint count spectrum and the joint count-window filter ---- */
+/* Two more set operations: the same compatibility fields and messages, the same refusals (a null handle, dst == src, an
+ * entry-id index or a sharded handle on either side, a count_mode mismatch: EINVAL), the same two locks, pending deferred
+ * inserts of both handles completed first, src's stream synchronised before it is read.  Both compare STORED count bytes. */
+#define BRISK_HIP_JOINT_ABSENT 256u
+#define BRISK_HIP_JOINT_STATES 257u
+/* read-only. out is a HOST array of 257*257 uint64. out[sa*257 + sb] = number of identities whose state in a is sa and in b
+ * is sb. A state is the STORED count byte (0..255) of a present entry, or 256 = not in that index. A wrapped count of 0 is
+ * present with state 0, never state 256. out[256*257+256] = 0.  EINVAL if out is NULL.
+ * Both indexes are left bit for bit as they were.  Between saturating indexes bin 255 means "255 or more" on either axis and
+ * state 0 is never populated.  By construction: rows 0..255 sum to a's brisk_hip_count_spectrum and columns 0..255 to b's; the
+ * present x present block sums to brisk_hip_compare's out[0], and weighted by sa, by sb and by min(sa, sb) to its out[4],
+ * out[5] and out[3]; row 256 sums to its out[2], column 256 to its out[1]. */
+int brisk_hip_joint_spectrum(brisk_hip_index *a, brisk_hip_index *b, uint64_t *out);
+
+typedef struct brisk_hip_joint_window {
+    uint32_t min_self, max_self;    /* dst's stored count must lie in [min_self, max_self]; a bound above 255 means 255 */
+    uint32_t min_other, max_other;  /* an entry whose identity IS in src passes if src's stored count lies in this range;
+                                       min_other > max_other: no entry that is present in src passes */
+    uint32_t keep_absent;           /* non-zero: an entry whose identity is NOT in src passes the src side */
+    uint32_t reserved;              /* must be 0 */
+} brisk_hip_joint_window;
+/* dst keeps the entries that pass both sides, with their counts unchanged; *removed (may be NULL) = entries dst lost.
+ * Afterwards dst is exactly the index that holds the remaining entries, as after brisk_hip_intersect or brisk_hip_prune
+ * (stats, checksum, enumerate, lookup, every get, every later insert; survivors keep their storage order, slices their offset
+ * and capacity, nb_skmers stays); src is left bit for bit as it was.  EINVAL, checked before any device call, nothing changed
+ * and *removed not written: w is NULL, min_self > max_self, reserved != 0, or a window nothing can pass (min_other > max_other
+ * with keep_absent == 0).  In a saturating index a bound of 255 keeps everything seen at least 255 times.
+ * By construction: {0,255, 0,255, 0} is intersect(LEFT); {0,255, 1,0, 1} is subtract; {lo,hi, 0,255, 1} is prune(lo, hi). */
+int brisk_hip_filter_joint(brisk_hip_index *dst, brisk_hip_index *src, const brisk_hip_joint_window *w, uint64_t *removed);
 
 /* ---- snapshots: an index saved to a file and loaded back (no reference counterpart) ---- */
 /* An entry's stored key plus its partition number is its whole identity, so a snapshot is the directory and the live entries of
