@@ -658,8 +658,10 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         // instantiations with the record geometry (nw, k - b, routing-id bits kept in the key) as constants, for the
         // common parameter sets under the default partition layout; anything else takes the generic body
         // (every one of them twice: counts that wrap, and -- SAT -- counts that stop at 255; the mode is the handle's)
+        const char* body = "";  // (BRISK_TRACE: the kernel and its template arguments -- nw, k - b, shift; 0,0,0 is the run-time body)
 #define LAUNCH_INSERT_K(KERNEL, NW, KB, SH, SAT)                                                                                                                    \
     {                                                                                                                                                               \
+        body = #KERNEL "<" #NW "," #KB "," #SH;                                                                                                                     \
         const dim3 grid(std::min<u32>(batches, resident((const void*)KERNEL<NW, KB, SH, SAT>)));                                                                  \
         hipLaunchKernelGGL((KERNEL<NW, KB, SH, SAT>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix,                         \
                            h->d_ctr->work.wc);                                                                                                                      \
@@ -682,6 +684,7 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         u32* const wc = h->d_ctr->work.wc;                                                                                                                          \
         u32* const n_left = &h->d_ctr->work.n_left;                                                                                                                 \
         u32* const n_clean = clean_off ? nullptr : &h->d_ctr->work.n_clean;                                                                                         \
+        body = "k_insert_first<3,49," #SH;                                                                                                                          \
         const dim3 grid(std::min<u32>(batches, resident((const void*)k_insert_first<3, 49, SH, SAT>, 4 * WI_WAVES_PER_EU_FIRST_MAX)));                                                            \
         hipLaunchKernelGGL((k_insert_first<3, 49, SH, SAT>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix, wc,                \
                            (u32*)h->left.p, n_left, n_clean);                                                                                                       \
@@ -724,6 +727,7 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
             }
             fprintf(stderr, "[brisk_hip] path: insert of %llu records (%s layout, histogram %s) into %u partitions: %s, %u partitions to k_insert_huge%s\n", (unsigned long long)n_rec,
                     bl ? "binned" : "classic", have_hist ? "from the scan" : "counted here", n_touched, path.c_str(), n_huge, tail.c_str());
+            fprintf(stderr, "[brisk_hip] body: %s,%s>%s\n", body, sat ? "sat" : "wrap", lean ? ", then k_insert_fast_listed" : "");
         }
         if (n_huge) {
             if (sat) hipLaunchKernelGGL(k_insert_huge<true>, dim3(std::min<u32>(n_huge, 256u)), dim3(HG_THREADS), 0, h->stream, P, src, (const PartDesc*)h->desc.p,
@@ -1293,8 +1297,10 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
         // + 8: 135 slots per partition), which keeps twice the waves resident; else 256
         static const long ent_env = getenv("BRISK_QUERY_ENT") ? atol(getenv("BRISK_QUERY_ENT")) : 0;  // experiments and tests: 128 | 256
         const bool small = ent_env ? ent_env == 128 : h->arena_used_host / own_partitions(h).len <= 135;
+        const char* body = "k_query (run-time body)";  // (BRISK_TRACE)
 #define LAUNCH_QUERY_FAST_ENT(NW, KB, SH, ENT)                                                                                                                      \
     do {                                                                                                                                                              \
+        body = "k_query_fast<" #NW "," #KB "," #SH "," #ENT ">";                                                                                                    \
         if (kout)                                                                                                                                                     \
             hipLaunchKernelGGL((k_query_fast<NW, KB, SH, ENT, true>), dim3(std::min<u32>(batches, resident((const void*)k_query_fast<NW, KB, SH, ENT, true>))), dim3(64), \
                                0, h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p, n_touched, h->ix, d_sums, h->d_ctr->work.wc,  \
@@ -1328,6 +1334,7 @@ int query_records_impl(brisk_hip_index* h, const u64* d_rec, const u32* d_tags, 
 #undef LAUNCH_QUERY_FAST
 #undef LAUNCH_QUERY_FAST_ENT
         if (int lrc = launch_check(h, "k_query")) return lrc;
+        if (h->trace) fprintf(stderr, "[brisk_hip] body: %s%s\n", body, kout ? ", per k-mer" : "");
         // the listed partitions (none, as a rule: the kernel reads the list's length on the device and returns)
         if (kout)
             hipLaunchKernelGGL(k_query_huge<true>, dim3(256), dim3(HG_THREADS), 0, h->stream, P, src, tags_binned, (const u32*)h->tags_b.p, (const PartDesc*)h->desc.p,

@@ -276,6 +276,8 @@ class Oracle(_Lib):
         L.bo_key.argtypes = [C.c_uint64, C.c_uint, f64p]
         L.bo_mix_inv.restype = C.c_uint64
         L.bo_mix_inv.argtypes = [C.c_uint64, C.c_uint]
+        L.bo_mix.restype = C.c_uint64
+        L.bo_mix.argtypes = [C.c_uint64, C.c_uint]
         L.bo_record_words.restype = C.c_uint
         L.bo_record_words.argtypes = [C.c_uint, C.c_uint, C.c_uint]
         L.bo_records.restype = C.c_int64
@@ -341,6 +343,13 @@ class Oracle(_Lib):
 
     def mix_inv_many(self, xs: Iterable[int], m: int) -> np.ndarray:
         return np.array([self.lib.bo_mix_inv(int(x), m) for x in xs], dtype=np.uint64)
+
+    def mix(self, x: int, m: int) -> int:
+        """The invertible mixer on 2m bits: the hash that replaces a k-mer's minimizer in place."""
+        return int(self.lib.bo_mix(int(x), m))
+
+    def mix_inv(self, y: int, m: int) -> int:
+        return int(self.lib.bo_mix_inv(int(y), m))
 
     def records(self, h, seq: str | bytes, k: int, m: int, b: int):
         """Super-k-mer records of one read in the GPU exchange format."""
