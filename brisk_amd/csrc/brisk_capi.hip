@@ -1810,6 +1810,9 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
     *out = nullptr;
     // Parameters contract (parameters.hpp:19-22, Brisk.hpp:50-51, counter.cpp:32)
     if (!(b >= 1 && b <= m && m < k && k <= 63 && (m & 1) && m <= 31) || !coef_table) return BRISK_HIP_EINVAL;
+    // k - b < 4: the reference cannot build such an index (SuperKmerLight.hpp:62 computes a mask of 2 (k - b) - 8 bits, which
+    // underflows and aborts), so there is nothing to be bit-exact with
+    if (k - b < 4) return BRISK_HIP_EINVAL;
     if (b > 16) return BRISK_HIP_EUNSUPPORTED;  // bucket ids are 32-bit, as the reference's uint32_t directory (DenseMenuYo.hpp:37,105)
     brisk_hip_options o{};
     if (opt) memcpy(&o, opt, std::min<size_t>(opt->struct_size ? opt->struct_size : sizeof(o), sizeof(o)));

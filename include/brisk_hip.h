@@ -171,7 +171,11 @@ enum { BRISK_HIP_COUNTS_WRAP = 0, BRISK_HIP_COUNTS_SATURATE = 1 };
 /* ---- lifetime ----------------------------------------------------------- */
 /* coef_table: the 4*m doubles of DecyclingSet(m) computed on the HOST with libm
  * (brisk/Decycling.cpp:7-13); the device never evaluates sin().  data_bytes must
- * be 1 (the counter app's uint8_t DATA). */
+ * be 1 (the counter app's uint8_t DATA).
+ * The envelope: 1 <= b <= m < k <= 63, m odd and at most 31, k - b >= 4 (EINVAL otherwise); b <= 16 and an entry key
+ * [routing bits | compacted k-mer : 2(k-b) | idx' : 6] of at most 128 bits (EUNSUPPORTED otherwise).  k - b < 4 is EINVAL, not
+ * EUNSUPPORTED: the reference itself cannot build such an index (SuperKmerLight.hpp:62 makes a mask of 2 (k - b) - 8 bits,
+ * which underflows and aborts), so no result exists to agree with. */
 int brisk_hip_create(brisk_hip_index **out, uint8_t k, uint8_t m, uint8_t b, uint32_t data_bytes,
                      const double *coef_table, const brisk_hip_options *opt);
 int brisk_hip_destroy(brisk_hip_index *h);

@@ -1,5 +1,10 @@
 """Randomised parity soak: random (k, m, b), read sets with repeats and low-complexity stretches, random batch splits, readers in
-between; index and get against the oracle.  python tests/fuzz_parity.py SECONDS SEED   (test_randomised_parity_soak runs 25 s of it; 2,211 cases in 300 s on the MI355X: profiles/r02_fuzz.txt)"""
+between; index and get against the oracle.  python tests/fuzz_parity.py SECONDS SEED   (test_randomised_parity_soak runs 25 s of it; 2,211 cases in 300 s on the MI355X: profiles/r02_fuzz.txt)
+
+The geometry is drawn from the whole envelope of brisk_hip_create (order "v3"): m odd from 1 to 31, b from 1 to min(m, 16), k from
+m + 1 to 63; a case with k - b < 4 or a key of more than 128 bits is skipped.  Until then (order "v2") k was drawn first, from 12,
+m from 5 and b up to 14, so a seed's cases are no longer those that the records under profiles/ name: tools/replay_fuzz_case.py
+rebuilds those with --v2 (and the round-2 order with --v1)."""
 import collections, json, os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -95,12 +100,12 @@ case = -1
 vrng = random.Random(seed ^ 0x5eed)  # its own sequence: the cases stay those of the same seed without it
 while time.time() < t_end:
     case += 1
-    k = rng.randint(12, 63)
-    m = rng.choice([x for x in range(5, min(k - 1, 31) + 1, 2)])
-    b = rng.randint(1, min(m, 14))
+    m = rng.choice(range(1, 32, 2))
+    b = rng.randint(1, min(m, 16))
+    k = rng.randint(m + 1, 63)
     pb = rng.choice([0, 0, 0, rng.randint(1, min(2 * b, 20))])
-    if 2 * (k - b) + 6 > 128:
-        continue  # outside the library's envelope (EUNSUPPORTED): the entry key [compacted k-mer | idx'] must fit 128 bits
+    if 2 * (k - b) + 6 > 128 or k - b < 4:
+        continue  # outside the library's envelope: the entry key [compacted k-mer | idx'] must fit 128 bits (EUNSUPPORTED), and the reference cannot run with k - b < 4 (EINVAL)
     reads = rand_reads()
     immediate, splits, peeks = rng.random() < 0.3, [rng.choice([1, 7, 64, 300, 10**9]) for _ in range(4000)], [rng.random() < 0.1 for _ in range(4000)]
     qsel = sorted(rng.sample(range(len(reads)), min(len(reads), 60)))

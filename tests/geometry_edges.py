@@ -54,7 +54,45 @@ PROPERTY = [
     lambda L: L["nw"] == 1 and L["cls_bits"] == 1 and L["key_words"] == 1,
 ]
 
+# The corners of brisk_hip_create's envelope: 1 <= b <= m < k <= 63, m odd and at most 31, b <= 16,
+# k - b >= 4, a key of at most 128 bits.  Same fields; every row is created with the default part_bits.
+CORNERS = [
+    Row(63, 31, 16, 0, 108, 2, 8, 3, "32-bit bucket ids under a two-word key"),
+    Row(33, 17, 16, 0, 48, 1, 8, 2, "32-bit bucket ids, one word, k > 32"),
+    Row(32, 31, 16, 0, 46, 1, 8, 1, "k = m + 1 at k = 32, nw = 1, b = 16"),
+    Row(31, 15, 15, 0, 44, 1, 6, 1, "2b = 30, min-queue scan"),
+    Row(47, 23, 15, 0, 76, 2, 6, 2, "b = 15, two words"),
+    Row(20, 17, 16, 0, 22, 1, 8, 1, "k - b = 4 at b = 16"),
+    Row(19, 15, 15, 0, 20, 1, 6, 1, "k - b = 4 at b = 15"),
+    Row(9, 5, 5, 0, 14, 1, 0, 1, "k - b = 4, the smallest key"),
+    Row(16, 15, 7, 0, 24, 1, 0, 1, "k = m + 1 with an extended routing id"),
+    Row(63, 3, 2, 0, 128, 2, 0, 4, "m = 3 at the ceiling, window of 61"),
+    Row(10, 3, 1, 0, 24, 1, 0, 1, "m = 3, small k"),
+    Row(21, 3, 3, 0, 42, 1, 0, 2, "m = b: suff_reduc = 0, the class bit is the only extension"),
+    Row(31, 1, 1, 0, 66, 2, 0, 2, "m = 1: eight partitions of thousands of entries, a window of 31"),
+]
+
+# (part_bits, ext_bits, cls_bits) of every corner, from the layout formula, and what the row is there for
+CORNER_PROPERTY = [
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (24, 0, 0) and L["b"] == 16 and L["key_words"] == 2 and L["shift"] == 8,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (24, 0, 0) and L["b"] == 16 and L["key_words"] == 1 and L["k"] > 32,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (24, 0, 0) and L["k"] == L["m"] + 1 == 32 and L["nw"] == 1 and L["shift"] == 8,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (24, 0, 0) and 2 * L["b"] == 30 and L["min_queue"] and L["shift"] == 6,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (24, 0, 0) and L["b"] == 15 and L["key_words"] == 2,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (24, 0, 0) and L["k"] - L["b"] == 4 and L["b"] == 16,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (24, 0, 0) and L["k"] - L["b"] == 4 and L["b"] == 15,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (10, 0, 0) and L["k"] - L["b"] == 4 and L["key_bits"] == 14,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (24, 10, 0) and L["k"] == L["m"] + 1,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (7, 3, 1) and L["m"] == 3 and L["key_bits"] == 128 and L["k"] - L["m"] + 1 == 61,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (7, 5, 1) and L["m"] == 3 and L["nw"] == 1,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (7, 1, 1) and L["m"] == L["b"] == 3 and (L["m"] - L["b"] + 1) // 2 == 0,
+    lambda L: (L["part_bits"], L["ext_bits"], L["cls_bits"]) == (3, 1, 1) and L["m"] == 1 and L["k"] - L["m"] + 1 == 31,
+]
+
 SATURATE_ROWS = [0, 3, 4, 7]  # the 64-bit, 66-bit, straddling and 128-bit keys
+SATURATE_CORNERS = [0, 11]  # (63, 31, 16) and (21, 3, 3)
+SHARDED_CORNERS = [0, 3, 9]  # (63, 31, 16), (31, 15, 15), (63, 3, 2): the owner of a 32-bit, of a 30-bit and of an extended routing id
+PERCALL_CORNERS = [1, 11]  # (33, 17, 16) and (21, 3, 3)
 CLS_EXTRA = [Row(31, 11, 11, 0, 46, 1, 0, 2, "the class geometry of the other tests"), Row(63, 11, 4, 0, 124, 2, 0, 4, "classes under a two-word key")]
 
 
@@ -67,8 +105,10 @@ def opts(r):
 
 
 def layout(k, m, b, part_bits=0, cls_env=-1):
-    """brisk_hip_create's geometry: None where it refuses (EUNSUPPORTED).  cls_env: BRISK_CLS_BITS, -1 when unset."""
+    """brisk_hip_create's geometry: None where it refuses (EUNSUPPORTED; EINVAL for k - b < 4).  cls_env: BRISK_CLS_BITS, -1 when unset."""
     w, kb = k - m, k - b
+    if kb < 4:
+        return None
     L = dict(k=k, m=m, b=b, requested_part_bits=part_bits, nw=(2 * (2 * k - m - b) + 63) // 64, ext_bits=0, cls_bits=0, cls_width=1)
     if not part_bits and 2 * b < 24:
         if 2 * m < 24 and w + 1 >= 8:
@@ -121,9 +161,59 @@ def read_sets(r):
     seed = r.k * 10000 + r.m * 100 + r.b
     a, b = two_samples(seed, glen=GLEN, n_a=400, n_b=260)
     rng = random.Random(seed + 1)
+    if r.m == 1:
+        # A one-nucleotide minimizer ties at almost every window, so which (k-mer, minimizer_idx) a k-mer is stored under depends
+        # on the read around it: two samples of one genome share next to nothing.  B takes whole reads of A instead -- every
+        # second drawn read, with other repeat factors than A has -- and keeps its own reads of the genome's last third.
+        own = [s for s in b[:260] if s not in a]
+        b = a[0:400:2] + a[0:100:2] * 2 + own[:130] + own[:30] * 3 + SPECIAL * 2
     a = a + ["".join(rng.choice("ACGT") for _ in range(rng.randint(1, 400))) for _ in range(30)]
+    if min(len(s) for s in a) >= r.k:  # k of 10 or less: the ragged reads happen to have none shorter than k
+        a = a + ["".join(rng.choice("ACGT") for _ in range(n)) for n in (r.k - 1, r.k // 2, 1)]
     c = a[40:100] + b[10:60] + ["".join(rng.choice("ACGT") for _ in range(150)) for _ in range(40)]
     return a, b, c
+
+
+def queries_of(reads_a, reads_b, reads_c, n_queries=(70, 50, 30)):
+    """the reads a row is queried with: reads of A (present), of B (half of them absent), of C's random tail (absent), the
+    low-complexity set"""
+    na, nb_, nc = n_queries
+    return [q.upper() for q in reads_a[:na] + reads_a[-12:] + reads_b[:nb_] + reads_c[-nc:] + SPECIAL]
+
+
+# ---- the reference's own answers (tests/golden/envelope_reference.json, written by tests/golden/make_golden.py envelope) -----------
+def all_rows():
+    return TABLE + CORNERS
+
+
+def sums_md5(sums):
+    """md5 of per-read sums as little-endian uint64 words (make_golden.stream_md5 of one array)"""
+    import hashlib
+    return hashlib.md5(np.asarray(sums).astype("<u8").tobytes()).hexdigest()
+
+
+def lines_md5(lines):
+    """md5 of sorted "KMER idx count" lines as the text "KMER idx=N count\\n" (make_golden.md5_lines)"""
+    import hashlib
+    return hashlib.md5("".join("{} idx={} {}\n".format(*l.split()) for l in lines).encode()).hexdigest()
+
+
+def envelope_answers(X, r):
+    """What X (oracle.Oracle or oracle.Ref: the same calls) says about row r: the index of reads A, the per-read sums of the row's
+    queries.  The record of envelope_reference.json."""
+    a, b, c = read_sets(r)
+    q = queries_of(a, b, c)
+    flat, offs = oracle.pack_reads(a)
+    qflat, qoffs = oracle.pack_reads(q)
+    h = X.index_new(r.k, r.m, r.b)
+    try:
+        X.index_insert_reads(h, flat, offs)
+        nb_kmers, nb_buckets = X.index_stats(h)
+        lines = oracle.multiset_lines(*X.index_dump(h), r.k)
+        sums = X.index_query_reads(h, qflat, qoffs)
+    finally:
+        X.index_free(h)
+    return dict(k=r.k, m=r.m, b=r.b, nb_kmers=nb_kmers, nb_buckets=nb_buckets, md5=lines_md5(lines), sums_md5=sums_md5(sums))
 
 
 class Case:
@@ -141,8 +231,7 @@ class Case:
         self.dump_a = O.index_dump(self.ha)
         self.da, self.db, self.dc = (as_dict(O.index_dump(h)) for h in (self.ha, self.hb, self.hc))
         self.stats_a = O.index_stats(self.ha)
-        na, nb_, nc = n_queries  # reads of A (present), of B (half of them absent), of C's random tail (absent), the low-complexity set
-        self.queries = [q.upper() for q in self.reads_a[:na] + self.reads_a[-12:] + self.reads_b[:nb_] + self.reads_c[-nc:] + SPECIAL]
+        self.queries = queries_of(self.reads_a, self.reads_b, self.reads_c, n_queries)
         self.qflat, self.qoffs = oracle.pack_reads(self.queries)
         self.slots, self.alts, self.base = expected_all(O, self.ha, self.queries, k, m)
         self.sums = O.index_query_reads(self.ha, self.qflat, self.qoffs)

@@ -2,7 +2,8 @@
 BRISK_BINS, BRISK_HUGE_AT, BRISK_HUGE_QUERY_AT, BRISK_DEFER and BRISK_CLS_BITS once), the device paths against the oracle at the
 rows of tests/geometry_edges.py.  Prints "ok <n checks>"; any mismatch is an AssertionError and exit status 1.
 
-  variants   every row: insert in two batches, get_reads, get_kmers, one merge
+  variants   every row: insert in two batches, get_reads, get_kmers, one merge; "variants corners": the same over
+             geometry_edges.CORNERS
   cls        the class rows and (31, 11, 11), (63, 11, 4): layout, index, get_reads, get_kmers, the scan's records element by
              element and every record within one class; a snapshot of this setting is written to GEOMETRY_WORKER_DIR/child-<row>.snap
              and the parent's file (parent-<row>.snap) is loaded: refused with EINVAL unless it was saved under the same cls_bits"""
@@ -50,9 +51,9 @@ def index_and_gets(O, r, c, ix):
     return 3
 
 
-def variants(O):
+def variants(O, rows=G.TABLE):
     checks = 0
-    for r in G.TABLE:
+    for r in rows:
         c = G.case(O, r)
         with filled(r, c.reads_a) as ix, filled(r, c.reads_b) as src:
             G.check_library_layout(r, ix.layout)
@@ -140,4 +141,7 @@ def cls(O):
 if __name__ == "__main__":
     assert torch.cuda.is_available()
     oracle.build(ref=False)
-    print("ok", {"variants": variants, "cls": cls}[sys.argv[1]](oracle.Oracle()))
+    if sys.argv[1:] == ["variants", "corners"]:
+        print("ok", variants(oracle.Oracle(), G.CORNERS))
+    else:
+        print("ok", {"variants": variants, "cls": cls}[sys.argv[1]](oracle.Oracle()))

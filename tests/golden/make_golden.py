@@ -4,6 +4,7 @@
 Run in the build container only (needs /root/reference):
     python tests/golden/make_golden.py
     python tests/golden/make_golden.py reference_build    # tests/golden/reference_build.json alone
+    python tests/golden/make_golden.py envelope           # tests/golden/envelope_reference.json alone
 
 Every expected value written here is an output of the reference's own code
 (Kmers.cpp, hashing.cpp, Decycling.cpp, buckets.hpp, SuperKmerLight.hpp)
@@ -213,10 +214,25 @@ def reference_build(R):
     return out
 
 
+def envelope_reference(R):
+    """The reference's answers at every row of tests/geometry_edges.py (TABLE and CORNERS) on the row's own reads A and queries,
+    which the tests rebuild from the rows' seeds: nb_kmers, nb_buckets, the md5 of the multiset text and of the per-read sums.
+    tests/test_envelope_corners_cpu.py holds the restatement to it, tests/test_envelope_corners.py the library."""
+    sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..")))
+    import geometry_edges as G
+    assert G.lines_md5(["ACGT 1 2", "CCGT 0 7"]) == md5_lines(["ACGT 1 2", "CCGT 0 7"])
+    assert G.sums_md5(np.arange(5, dtype=np.uint64)) == stream_md5([np.arange(5, dtype=np.uint64)])
+    return {G.row_id(r): G.envelope_answers(R, r) for r in G.all_rows()}
+
+
 def main():
     if sys.argv[1:] == ["reference_build"]:  # only tests/golden/reference_build.json
         oracle.build()
         json.dump(reference_build(oracle.Ref()), open(os.path.join(HERE, "reference_build.json"), "w"), indent=1)
+        return
+    if sys.argv[1:] == ["envelope"]:  # only tests/golden/envelope_reference.json
+        oracle.build()
+        json.dump(envelope_reference(oracle.Ref()), open(os.path.join(HERE, "envelope_reference.json"), "w"), indent=1)
         return
     oracle.build()
     R, O = oracle.Ref(), oracle.Oracle()
@@ -228,6 +244,7 @@ def main():
     dump("enumerator.json.gz", enum_vectors(R, rng))
     json.dump(multisets(R, O, rng), open(os.path.join(HERE, "multisets.json"), "w"), indent=1)
     json.dump(reference_build(R), open(os.path.join(HERE, "reference_build.json"), "w"), indent=1)
+    json.dump(envelope_reference(R), open(os.path.join(HERE, "envelope_reference.json"), "w"), indent=1)
     print("golden fixtures written to", HERE)
 
 

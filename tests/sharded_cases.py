@@ -68,7 +68,7 @@ def edge_reads(row):
 
 def edge_queries(row):
     a, b, c = _once(("edge", row), lambda: G.read_sets(row))
-    return [q.upper() for q in a[:70] + a[-12:] + b[:50] + c[-30:] + SPECIAL]
+    return G.queries_of(a, b, c)
 
 
 def middle_cut(row):

@@ -62,8 +62,7 @@ def check_get_kmers(ix, c, slots=None, alts=None, what=""):
 
 
 # ---- index ---------------------------------------------------------------------------------------------------------------------
-@ROWS
-def test_index(B, O, tmp_path, r):
+def index_family(B, O, tmp_path, r):
     c = G.case(O, r)
     lo, hi, idx, cnt = c.dump_a
     with filled(B, r, tmp_path, c.reads_a) as ix:
@@ -81,18 +80,26 @@ def test_index(B, O, tmp_path, r):
             assert np.array_equal(data2[want2 >= 0], want2[want2 >= 0].astype(np.uint8))
 
 
-# ---- get -----------------------------------------------------------------------------------------------------------------------
 @ROWS
-def test_get(B, O, tmp_path, r):
+def test_index(B, O, tmp_path, r):
+    index_family(B, O, tmp_path, r)
+
+
+# ---- get -----------------------------------------------------------------------------------------------------------------------
+def get_family(B, O, tmp_path, r):
     c = G.case(O, r)
     with filled(B, r, tmp_path, c.reads_a) as ix:
         assert np.array_equal(ix.get_reads(c.queries), c.sums)
         check_get_kmers(ix, c, what=G.row_id(r))
 
 
-# ---- abundance -----------------------------------------------------------------------------------------------------------------
 @ROWS
-def test_abundance(B, O, tmp_path, r):
+def test_get(B, O, tmp_path, r):
+    get_family(B, O, tmp_path, r)
+
+
+# ---- abundance -----------------------------------------------------------------------------------------------------------------
+def abundance_family(B, O, tmp_path, r):
     c = G.case(O, r)
     left = keep(c.dump_a, 2, 255)
     assert 10 * len(left[0]) >= len(c.dump_a[0]) and 10 * (len(c.dump_a[0]) - len(left[0])) >= len(c.dump_a[0])
@@ -106,9 +113,13 @@ def test_abundance(B, O, tmp_path, r):
         check_get_kmers(ix, c, slots, alts, "after the prune")
 
 
-# ---- set operations --------------------------------------------------------------------------------------------------------------
 @ROWS
-def test_set_operations(B, O, tmp_path, r):
+def test_abundance(B, O, tmp_path, r):
+    abundance_family(B, O, tmp_path, r)
+
+
+# ---- set operations --------------------------------------------------------------------------------------------------------------
+def set_operations_family(B, O, tmp_path, r):
     c = G.case(O, r)
     for op, rule in (("merge", "left"), ("subtract", "left"), ("intersect", "min"), ("intersect", "sum")):
         want = expected(op, c.da, c.db, rule)
@@ -126,9 +137,13 @@ def test_set_operations(B, O, tmp_path, r):
         assert b.compare(a) == expected_compare(c.db, c.da)
 
 
-# ---- snapshot ----------------------------------------------------------------------------------------------------------------------
 @ROWS
-def test_snapshot(B, O, tmp_path, monkeypatch, r):
+def test_set_operations(B, O, tmp_path, r):
+    set_operations_family(B, O, tmp_path, r)
+
+
+# ---- snapshot ----------------------------------------------------------------------------------------------------------------------
+def snapshot_family(B, O, tmp_path, monkeypatch, r):
     c = G.case(O, r)
     hab = oracle_index(O, c.reads_a + c.reads_b, r.k, r.m, r.b)  # the oracle index that received A, then B
     want_ab = O.index_dump(hab)
@@ -168,9 +183,13 @@ def test_snapshot(B, O, tmp_path, monkeypatch, r):
     O.index_free(hab)
 
 
-# ---- profiles and extraction ----------------------------------------------------------------------------------------------------------
 @ROWS
-def test_profiles_and_extraction(B, O, tmp_path, r):
+def test_snapshot(B, O, tmp_path, monkeypatch, r):
+    snapshot_family(B, O, tmp_path, monkeypatch, r)
+
+
+# ---- profiles and extraction ----------------------------------------------------------------------------------------------------------
+def profiles_and_extraction_family(B, O, tmp_path, r):
     """The oracle's slots reduced by profile_from_slots are the expected records.  Where a span of a read is its own reverse
     complement the oracle allows two orders of the span's slots (test_kmer_query.expected_slots); get_kmers must return one of
     the two, and the profile, the intervals and the extraction are then held to that one (geometry_edges.resolved_slots): the
@@ -219,41 +238,55 @@ def test_profiles_and_extraction(B, O, tmp_path, r):
             assert d_text.cpu().numpy()[:n_nts].tobytes().decode() == "".join(s for _, s in kept), rule.kind
 
 
+@ROWS
+def test_profiles_and_extraction(B, O, tmp_path, r):
+    profiles_and_extraction_family(B, O, tmp_path, r)
+
+
 # ---- saturating counts -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("r", [G.TABLE[i] for i in G.SATURATE_ROWS], ids=[G.row_id(G.TABLE[i]) for i in G.SATURATE_ROWS])
-def test_saturating_counts(B, O, tmp_path, r):
+def saturating_counts_family(B, O, tmp_path, r, part=None):
     """tests/test_saturate.py's construction -- a read set whose oracle counts are exact, inserted twice -- with one read 300 times
-    among it, and a merge whose sums cross 255 between counts that have not"""
+    among it, and a merge whose sums cross 255 between counts that have not.  part: "insert" or "merge" alone (the second handle is
+    opened for the merge only), None: both"""
     import saturate_worker as S
     reads, other, one = G.saturate_reads()
     want_a, want_b, nb_a, nb_union = G.saturate_expectation(O, r)
     assert any(v == 255 for v in want_a.values()) and any(v < 255 for v in want_a.values())
     shared = set(want_a) & set(want_b)
     assert any(want_a[x] + want_b[x] > 255 and want_a[x] < 255 and want_b[x] < 255 for x in shared)
-    with B.BriskHip(r.k, r.m, r.b, count_mode="saturate", **G.opts(r)) as dst, B.BriskHip(r.k, r.m, r.b, count_mode="saturate", **G.opts(r)) as src:
+    with B.BriskHip(r.k, r.m, r.b, count_mode="saturate", **G.opts(r)) as dst:
         G.check_library_layout(r, dst.layout)
-        for part in (reads, one * 300, reads):  # the filler, the read past 255, the filler again: three calls
-            dst.insert_reads(part)
-        src.insert_reads(other * 2)
-        S.check_index(dst, want_a, nb_a, r.k, "saturating insert")
-        path = tmp_path / "sat.snap"
-        dst.save(path)
-        info = B.snapshot_info(path)
-        G.check_library_layout(r, dst.layout, info)
-        assert info["count_mode"] == 1
-        src_cs = src.checksum()
-        merged = {x: S.clamp(want_a.get(x, 0) + want_b.get(x, 0)) for x in set(want_a) | set(want_b)}
-        assert dst.merge(src) == len(set(want_b) - set(want_a))
-        S.check_index(dst, merged, nb_union, r.k, "saturating merge")
-        assert src.checksum() == src_cs and dst.count_spectrum()[0] == 0
+        for batch in (reads, one * 300, reads):  # the filler, the read past 255, the filler again: three calls
+            dst.insert_reads(batch)
+        if part != "merge":
+            S.check_index(dst, want_a, nb_a, r.k, "saturating insert")
+            path = tmp_path / "sat.snap"
+            dst.save(path)
+            info = B.snapshot_info(path)
+            G.check_library_layout(r, dst.layout, info)
+            assert info["count_mode"] == 1
+        if part == "insert":
+            return
+        with B.BriskHip(r.k, r.m, r.b, count_mode="saturate", **G.opts(r)) as src:
+            src.insert_reads(other * 2)
+            src_cs = src.checksum()
+            merged = {x: S.clamp(want_a.get(x, 0) + want_b.get(x, 0)) for x in set(want_a) | set(want_b)}
+            assert dst.merge(src) == len(set(want_b) - set(want_a))
+            S.check_index(dst, merged, nb_union, r.k, "saturating merge")
+            assert src.checksum() == src_cs and dst.count_spectrum()[0] == 0
+
+
+@pytest.mark.parametrize("r", [G.TABLE[i] for i in G.SATURATE_ROWS], ids=[G.row_id(G.TABLE[i]) for i in G.SATURATE_ROWS])
+def test_saturating_counts(B, O, tmp_path, r):
+    saturating_counts_family(B, O, tmp_path, r)
 
 
 # ---- kernel variants and BRISK_CLS_BITS: a process per environment (the library reads these variables once) ----------------------------
-def _worker(mode, extra_env, tmp_path):
+def _worker(mode, extra_env, tmp_path, *more):
     env = {n: v for n, v in os.environ.items() if not n.startswith("BRISK_") or n == "BRISK_HIP_LIB"}
     env.update(extra_env, GEOMETRY_WORKER_DIR=str(tmp_path))
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(TESTS, "geometry_edges_worker.py"), mode], env=env, capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, os.path.join(TESTS, "geometry_edges_worker.py"), mode, *more], env=env, capture_output=True, text=True, timeout=600)
     print(f"geometry_edges_worker {mode} {extra_env}: {time.time() - t0:.0f} s")
     print(p.stdout)
     last = p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""

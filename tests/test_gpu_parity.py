@@ -639,10 +639,15 @@ def test_device_synth_generator_matches_oracle(B, O):
 
 
 def test_parameter_contract(B):
-    for k, m, b in ((31, 11, 14), (31, 12, 4), (31, 31, 4), (64, 21, 14), (31, 11, 0), (63, 33, 4)):
+    # k - b < 4: the reference aborts there (SuperKmerLight.hpp:62), so create refuses; k - b = 4 is inside
+    for k, m, b in ((31, 11, 14), (31, 12, 4), (31, 31, 4), (64, 21, 14), (31, 11, 0), (63, 33, 4),
+                    (12, 11, 11), (18, 17, 16), (8, 7, 7), (17, 15, 15), (4, 3, 1), (19, 17, 16), (2, 1, 1)):
         with pytest.raises(B.BriskHipError) as e:
             B.BriskHip(k, m, b)
         assert e.value.code == 1
+    for k, m, b in ((20, 17, 16), (9, 5, 5), (5, 1, 1)):
+        with B.BriskHip(k, m, b) as ix:
+            assert ix.stats()["nb_kmers"] == 0
     with pytest.raises(B.BriskHipError) as e:  # key does not fit 128 bits: outside this library's envelope
         B.BriskHip(63, 21, 1)
     assert e.value.code == 2

@@ -163,9 +163,13 @@ def test_counts_wrap_mod_256(O):
 
 def test_parameter_contract(O):
     # F1: b > m is invalid in the reference (parameters.hpp:22,28 underflows); reject
-    for k, m, b in ((31, 11, 14), (31, 12, 4), (31, 31, 4), (64, 21, 14), (31, 11, 0), (63, 33, 4)):
+    # k - b < 4: the reference aborts there (SuperKmerLight.hpp:62), so the restatement refuses; k - b = 4 is inside
+    for k, m, b in ((31, 11, 14), (31, 12, 4), (31, 31, 4), (64, 21, 14), (31, 11, 0), (63, 33, 4),
+                    (12, 11, 11), (18, 17, 16), (8, 7, 7), (17, 15, 15), (4, 3, 1), (19, 17, 16), (2, 1, 1)):
         with pytest.raises(ValueError):
             O.index_new(k, m, b)
+    for k, m, b in ((20, 17, 16), (9, 5, 5), (5, 1, 1)):
+        O.index_free(O.index_new(k, m, b))
 
 
 def test_record_format_matches_kmer_semantics(O):

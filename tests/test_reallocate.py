@@ -109,16 +109,18 @@ def test_bulk_reallocate_at_the_key_layout_rows(O, k, m, b, spb, tpb):
     _reallocate_and_check(O, k, m, b, spb, tpb)
 
 
-def _reallocate_and_check(O, k, m, b, spb, pb):
+def _reallocate_and_check(O, k, m, b, spb, pb, times=1, n=1500):
+    """n random reads; times: every one of them goes in that often (m = 1: minimizer ties make an entry's identity depend on the read around the
+    k-mer, so the coverage alone leaves the counts at a dozen)"""
     import brisk_amd
     rng = random.Random(77)
     genome = "".join(rng.choice("ACGT") for _ in range(6000))
     reads = []
-    for _ in range(1500):
+    for _ in range(n):
         p = rng.randrange(0, len(genome) - 150)
         s = genome[p:p + 150]
         reads.append(s if rng.random() < 0.5 else "".join(COMP[c] for c in reversed(s)))
-    reads += ["A" * 120, "ACGT" * 40, "AC" * 70]  # low complexity: minimizer ties, entries that merge
+    reads = reads * times + ["A" * 120, "ACGT" * 40, "AC" * 70]  # low complexity: minimizer ties, entries that merge
     with brisk_amd.BriskHip(k, m, b, part_bits=spb) as old, brisk_amd.BriskHip(k, m + 2, b + 2, part_bits=pb) as new:
         old.insert_reads(reads)
         before = oracle.multiset_lines(*old.enumerate(), k)

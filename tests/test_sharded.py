@@ -58,6 +58,10 @@ def test_owner_counts(B, k, m, b, n_owners):
 def test_boundary_geometries(B, row):
     """The key-layout boundary rows whose routing differs (tests/geometry_edges.py): three owners with equal ranges, then with cut
     points that fall on partitions holding records (taken from the first run's scanned records)."""
+    boundary_geometry(B, row)
+
+
+def boundary_geometry(B, row):
     k, m, b = row.k, row.m, row.b
     reads, queries = C.edge_reads(row), C.edge_queries(row)
     rec, lay, _ = count_and_get(B, reads, queries, k, m, b, 3, part_bits=row.part_bits)

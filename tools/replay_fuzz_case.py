@@ -1,7 +1,7 @@
 """Rebuild one case of tests/fuzz_parity.py on the CPU (no GPU, no library call) and say, for a k-mer the GPU index got wrong,
 which reads hold it, where the wrong nucleotide lies in the read and in the packed stream, which super-k-mer of the oracle's
 enumerator it belongs to, and which host path every insert call of the case takes.
-    python tools/replay_fuzz_case.py [--v1] SEED CASE [WRONG_KMER RIGHT_KMER [--observed NB_KMERS NB_BUCKETS LINE...]]
+    python tools/replay_fuzz_case.py [--v1 | --v2] SEED CASE [WRONG_KMER RIGHT_KMER [--observed NB_KMERS NB_BUCKETS LINE...]]
 The random sequence is the fuzz's own (same draws in the same order), so the inputs are those of the failed run exactly.
 --observed: what the failed run reported (entry count, bucket count, some of its "KMER idx count" lines); every read that holds
 the right k-mer is then run through the oracle with that one nucleotide changed, and the runs that give exactly the observed
@@ -15,9 +15,10 @@ import numpy as np
 import oracle
 
 
-def cases(seed, order="v2"):
-    """order "v2": the committed fuzz (splits and peeks drawn up front); "v1": the fuzz as it ran when the round-2 failure was
-    recorded (read sample, immediate flag, then one split and one peek draw per insert call)."""
+def cases(seed, order="v3"):
+    """order "v3": the committed fuzz (the geometry drawn from the whole envelope: m from 1, b up to 16, k from m + 1); "v2": the
+    fuzz before that (k from 12 first, m from 5, b up to 14; splits and peeks drawn up front); "v1": the fuzz as it ran when the
+    round-2 failure was recorded (read sample, immediate flag, then one split and one peek draw per insert call)."""
     rng = random.Random(seed)
 
     def rand_reads():
@@ -45,11 +46,16 @@ def cases(seed, order="v2"):
     case = -1
     while True:
         case += 1
-        k = rng.randint(12, 63)
-        m = rng.choice([x for x in range(5, min(k - 1, 31) + 1, 2)])
-        b = rng.randint(1, min(m, 14))
+        if order == "v3":
+            m = rng.choice(range(1, 32, 2))
+            b = rng.randint(1, min(m, 16))
+            k = rng.randint(m + 1, 63)
+        else:
+            k = rng.randint(12, 63)
+            m = rng.choice([x for x in range(5, min(k - 1, 31) + 1, 2)])
+            b = rng.randint(1, min(m, 14))
         pb = rng.choice([0, 0, 0, rng.randint(1, min(2 * b, 20))])
-        if 2 * (k - b) + 6 > 128:
+        if 2 * (k - b) + 6 > 128 or (order == "v3" and k - b < 4):
             yield case, None
             continue
         reads, genome = rand_reads()
@@ -113,9 +119,10 @@ def explain_by_one_input_nt(O, reads, k, m, b, got, max_sims=600):
 
 
 def main():
-    order = "v2"
-    if "--v1" in sys.argv:
-        sys.argv.remove("--v1"); order = "v1"
+    order = "v3"
+    for flag in ("--v1", "--v2"):
+        if flag in sys.argv:
+            sys.argv.remove(flag); order = flag[2:]
     seed, want_case = int(sys.argv[1]), int(sys.argv[2])
     for case, c in cases(seed, order):
         if case == want_case:
