@@ -1,11 +1,17 @@
 // brisk_count -- this repo's own small k-mer counter over the facade / C-ABI (not the reference's
 // apps/counter.cpp, which compiles unchanged against brisk_amd/include and is built by the tests).
 //   brisk_count --facade FASTA k m b [dump.txt]   per-call API: SuperKmerEnumerator + Brisk<uint8_t>
-//   brisk_count --bulk   FASTA k m b [dump.txt]   bulk C-ABI: brisk_hip_insert_reads, FASTA or FASTA.gz streamed in batches
+//   brisk_count --bulk   FASTA k m b [dump.txt]   bulk C-ABI: brisk_hip_insert_reads, FASTA or FASTA.gz streamed in batches; a file whose first
+//                                                 inflated byte is '@' is FASTQ (plain or .gz) and goes through brisk_hip_insert_raw_reads
 //   brisk_count --mixed  FASTA k m b              BASELINE config #5's protocol (apps/counter.cpp:197-227,314-346): one thread streams the
 //                                                 file into brisk_hip_insert_reads while a second thread issues brisk_hip_get_reads on
 //                                                 the first reads of batches that are already in; prints what every get saw
 // --bulk only, anywhere on the command line (taken out before the positional arguments are read):
+//   --min-qual Q [--qual-base 33|64]   FASTQ input only (the main input and the FILE of --merge / --subtract / --intersect / --filter-joint /
+//                    --joint): a base whose quality is below Q (0..93, default 0: no cut) is cut like an N, on the device; the quality
+//                    characters are Phred+33 (default) or Phred+64.  One line on stderr per FASTQ file carries the intake's stats.
+//                    Exit status 2 when no input is FASTQ.  --profile and --extract read the input again as FASTA: with a FASTQ main
+//                    input they exit 2
 //   --histo FILE     the count spectrum (brisk_hip_count_spectrum): 256 lines "count<TAB>entries", empty bins included
 //   --saturate       counts stop at 255 instead of wrapping (brisk_hip_options.count_mode = BRISK_HIP_COUNTS_SATURATE): the index, and the
 //                    second index of --merge / --subtract / --intersect FILE, are created in that mode; --load FILE (or a set operation's
@@ -50,6 +56,7 @@
 
 #include "Brisk.hpp"
 #include "brisk_fasta.hpp"
+#include "brisk_fastq.hpp"
 #include "writer.hpp"
 
 // a snapshot file is told from a FASTA by its first eight bytes
@@ -77,6 +84,34 @@ static int load_snapshot(brisk_hip_index* h, const char* opt, const char* path, 
         return 1;
     }
     std::cerr << (opt + 2) << " " << path << ": " << n << " entries loaded" << std::endl;
+    return 0;
+}
+
+static bool is_fastq(const char* path) { return strcmp(path, "-") && !is_snapshot(path) && first_inflated_byte(path) == '@'; }
+// a FASTQ file into `h`: whole records as they are to brisk_hip_insert_raw_reads, which cuts them on the device; one stderr line with
+// the stats.  0 fine, 1 failed.  *produce_s / *wait_s (may be null): the reader thread's seconds, and the seconds spent waiting for it
+static int count_fastq(brisk_hip_index* h, const char* path, const brisk_hip_intake_rule& rule, size_t batch_bases, double* produce_s = nullptr, double* wait_s = nullptr) {
+    brisk_hip_intake_stats total{};
+    try {
+        FastqBatcher batches(path, batch_bases);
+        FastqBatch bt;
+        while (batches.next(bt)) {
+            brisk_hip_intake_stats st{};
+            if (brisk_hip_insert_raw_reads(h, bt.bases.data(), rule.min_qual ? bt.quals.data() : nullptr, bt.offs.data(), bt.size(), &rule, &st) != BRISK_HIP_OK) {
+                std::cerr << path << ": " << brisk_hip_last_error(h) << std::endl;
+                return 1;
+            }
+            const uint64_t* v = (const uint64_t*)&st;
+            for (size_t i = 0; i < sizeof st / 8; i++) ((uint64_t*)&total)[i] += v[i];
+        }
+        if (produce_s) *produce_s = batches.produce_seconds();
+        if (wait_s) *wait_s = batches.consumer_wait_seconds();
+    } catch (const std::exception& e) {
+        std::cerr << path << ": " << e.what() << std::endl;
+        return 1;
+    }
+    std::cerr << "fastq " << path << ": n_reads=" << total.n_reads << " n_reads_kept=" << total.n_reads_kept << " n_fragments=" << total.n_fragments << " n_bases_in=" << total.n_bases_in
+              << " n_nts=" << total.n_nts << " n_cut_base=" << total.n_cut_base << " n_cut_qual=" << total.n_cut_qual << " n_short=" << total.n_short << std::endl;
     return 0;
 }
 
@@ -183,6 +218,8 @@ int main(int argc_in, char** argv_in) {
     const char* extract_file = nullptr;
     const char* rule_text = nullptr;
     long min_len = 0;
+    long min_qual = 0, qual_base = 33;
+    bool have_qual = false;
     long min_count = 0, max_count = 255, solid = 2;
     bool have_solid = false;
     bool have_range = false;
@@ -195,8 +232,9 @@ int main(int argc_in, char** argv_in) {
     const char* window_text = nullptr;
     static const char* const usage =
         "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] "
-        "[--subtract FILE] [--intersect FILE] [--filter-joint FILE --window SLO:SHI:OLO:OHI[:absent]] [--joint FILE --joint-histo OUT] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]] "
-        "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]]; FASTA \"-\": no reads; a FILE may be a snapshot)\n"
+        "[--subtract FILE] [--intersect FILE] [--filter-joint FILE --window SLO:SHI:OLO:OHI[:absent]] [--joint FILE --joint-histo OUT] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]] [--min-qual Q] [--qual-base 33|64] "
+        "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]]; FASTA \"-\": no reads; a FILE may be a snapshot; an input that starts with '@' is FASTQ)\n"
+        "  --min-qual Q   FASTQ input: a base of quality below Q (0..93) is cut like an N, on the device; --qual-base 33|64 (default 33)\n"
         "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+";
     for (int i = 0; i < argc_in; i++) {
         if (i > 0 && (!strcmp(argv_in[i], "--help") || !strcmp(argv_in[i], "-h"))) {
@@ -213,7 +251,7 @@ int main(int argc_in, char** argv_in) {
         const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count") ||
                                     !strcmp(argv_in[i], "--profile") || !strcmp(argv_in[i], "--solid") || !strcmp(argv_in[i], "--extract") || !strcmp(argv_in[i], "--rule") ||
                                     !strcmp(argv_in[i], "--min-len") || !strcmp(argv_in[i], "--joint") || !strcmp(argv_in[i], "--joint-histo") || !strcmp(argv_in[i], "--filter-joint") ||
-                                    !strcmp(argv_in[i], "--window"));
+                                    !strcmp(argv_in[i], "--window") || !strcmp(argv_in[i], "--min-qual") || !strcmp(argv_in[i], "--qual-base"));
         if (!named) {
             args.push_back(argv_in[i]);
             continue;
@@ -233,6 +271,17 @@ int main(int argc_in, char** argv_in) {
         else if (!strcmp(opt, "--joint-histo")) joint_histo = argv_in[i];
         else if (!strcmp(opt, "--filter-joint")) filter_joint_file = argv_in[i];
         else if (!strcmp(opt, "--window")) window_text = argv_in[i];
+        else if (!strcmp(opt, "--min-qual") || !strcmp(opt, "--qual-base")) {
+            char* end = nullptr;
+            const long v = strtol(argv_in[i], &end, 10);
+            const bool mq = !strcmp(opt, "--min-qual");
+            if (end == argv_in[i] || *end || (mq ? (v < 0 || v > 93) : (v != 33 && v != 64))) {
+                std::cerr << opt << (mq ? ": a quality is 0..93, got " : ": 33 or 64, got ") << argv_in[i] << std::endl;
+                return 2;
+            }
+            (mq ? min_qual : qual_base) = v;
+            have_qual = true;
+        }
         else if (!strcmp(opt, "--min-len")) {
             char* end = nullptr;
             min_len = strtol(argv_in[i], &end, 10);
@@ -270,8 +319,8 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || extract_file || rule_text || min_len) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule and --min-len work on the device "
+    if ((histo || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || extract_file || rule_text || min_len || have_qual) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule, --min-len, --min-qual and --qual-base work on the device "
                      "index: --bulk only" << std::endl;
         return 2;
     }
@@ -345,6 +394,23 @@ int main(int argc_in, char** argv_in) {
     const char* dump = argc > 6 && strcmp(argv[6], "-") ? argv[6] : nullptr;
     const char* kff = argc > 7 ? argv[7] : nullptr;
     Parameters params(k, m, b);
+    brisk_hip_intake_rule intake{};
+    intake.struct_size = sizeof intake;
+    intake.min_qual = (uint32_t)min_qual;
+    intake.qual_base = (uint32_t)qual_base;
+    const bool fastq_main = bulk && is_fastq(argv[2]);
+    if (bulk && have_qual) {
+        bool any = fastq_main;
+        for (const char* f : {setop_file[0], setop_file[1], setop_file[2], filter_joint_file, joint_file}) any = any || (f && is_fastq(f));
+        if (!any) {
+            std::cerr << "--min-qual and --qual-base apply to FASTQ input, and no input is FASTQ" << std::endl;
+            return 2;
+        }
+    }
+    if (fastq_main && (profile_file || extract_file)) {
+        std::cerr << (profile_file ? "--profile" : "--extract") << " reads the input again as FASTA: not with a FASTQ input" << std::endl;
+        return 2;
+    }
     if (mixed) return run_mixed(argv[2], k, m, b, params.dede->coef(), batch_bases);
     std::vector<std::string> lines;
     uint64_t nb_buckets = 0, nb_skmers = 0, nb_kmers = 0, mem = 0, largest = 0, sum = 0;
@@ -420,7 +486,16 @@ int main(int argc_in, char** argv_in) {
             double insert_calls_s = 0.0;
             uint64_t n_reads_in = 0, n_bases_in = 0, n_batches = 0;
             if (no_reads) brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
-            else {
+            else if (fastq_main) {
+                double produce_s = 0.0, wait_s = 0.0;
+                if (count_fastq(h, argv[2], intake, batch_bases, &produce_s, &wait_s)) return 1;
+                brisk_hip_sync(h);  // (completes deferred inserts: the index is whole when the clock stops)
+                const double wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+                brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+                if (e2e)
+                    std::cout << "E2E {\"wall_s\": " << wall_s << ", \"entries\": " << nb_kmers << ", \"reader_produce_s\": " << produce_s << ", \"main_waits_for_reader_s\": " << wait_s << "}"
+                              << std::endl;
+            } else {
                 FastaBatcher batches(argv[2], batch_bases);
                 FastaBatch bt;
                 while (batches.next(bt)) {
@@ -468,6 +543,8 @@ int main(int argc_in, char** argv_in) {
                 }
                 if (is_snapshot(file)) {  // the second index from its snapshot: compact, it only serves this operation
                     if (int lrc = load_snapshot(other, opt, file, k, m, b, BRISK_HIP_LOAD_COMPACT)) return lrc;
+                } else if (is_fastq(file)) {
+                    if (count_fastq(other, file, intake, batch_bases)) return 1;
                 } else {
                     FastaBatcher batches(file, batch_bases);
                     FastaBatch bt;

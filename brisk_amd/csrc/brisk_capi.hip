@@ -31,11 +31,11 @@
 
 namespace {
 
-enum Slot { S_PACK, S_SYNTH, S_COUNT, S_SCAN, S_HIST, S_PSUM, S_TOUCHED, S_SCATTER, S_INSERT, S_QUERY, S_ENUM, S_LOOKUP, S_PROFILE, S_PROFILE_LONG, S_UPLOAD, S_NSLOTS };
-// (the last slot is host wall time, not a kernel: a host batch's bytes from the caller's memory to the packed stream on the device)
+enum Slot { S_PACK, S_SYNTH, S_COUNT, S_SCAN, S_HIST, S_PSUM, S_TOUCHED, S_SCATTER, S_INSERT, S_QUERY, S_ENUM, S_LOOKUP, S_PROFILE, S_PROFILE_LONG, S_UPLOAD, S_INTAKE, S_NSLOTS };
+// (S_UPLOAD is host wall time, not a kernel: a host batch's bytes from the caller's memory to the packed stream on the device)
 const char* const kSlotNames[S_NSLOTS] = {"k_pack_ascii", "k_synth", "k_count_kmers", "k_scan", "k_part_hist", "k_psum", "k_touched_need",
                                           "k_scatter", "k_insert", "k_query", "k_enumerate", "k_lookup", "k_profile_reads", "k_profile_segments_and_fold",
-                                          "host_upload_and_pack_wall"};
+                                          "host_upload_and_pack_wall", "k_intake_mask_count_apply_gather"};
 static_assert(S_NSLOTS <= BRISK_HIP_PROFILE_SLOTS, "brisk_hip_profile_read fills caller arrays of BRISK_HIP_PROFILE_SLOTS");
 
 struct DevBuf {
@@ -141,6 +141,9 @@ struct brisk_hip_index {
     DevBuf prof_out, prof_plan;          // brisk_hip_read_profile_*: a host call's records; counters, long-read and segment lists, partials
     DevBuf reck_buf;                     // brisk_hip_record_kmers: block sums
     DevBuf ext_iv, ext_tmp, ext_src;     // brisk_hip_extract_packed / _trim_*: a call's intervals; flags and block sums; the kept reads' source positions
+    DevBuf ink_mask, ink_tmp, ink_tab;   // brisk_hip_intake_*: a lane's valid and read-start bits; flags, block carries and sums; fragment rows, starts, source positions
+    DevBuf ink_raw, ink_offs, ink_packed;  // brisk_hip_intake_reads / _insert_raw_reads: a piece's bytes (bases, then qualities); its read table; its packed stream
+    u64 intake_piece = 1ull << 28;       // BRISK_INTAKE_PIECE (bytes of bases): the piece size of the host intake calls
     u32* d_ovf_cnt = nullptr;              // OVF_REGIONS counters of the binned scan's overflow area
     std::vector<u64> owner_cut;            // sharded index: owner o holds partitions [owner_cut[o], owner_cut[o + 1]) (n_owners + 1 entries)
     u32* d_owner_cut = nullptr;            // the same on the device once brisk_hip_set_owner_cuts has replaced the equal ranges (else null)
@@ -1758,7 +1761,7 @@ void free_all(brisk_hip_index* h) {
     hipStreamSynchronize(h->stream);  // nothing of ours may be in flight when the arena is unmapped
     auto fr = [](void* p) { if (p) hipFree(p); };
     for (DevBuf* b : {&h->huge, &h->left, &h->pend, &h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp, &h->enum_out,
-                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src})
+                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed})
         fr(b->p);
     fr(h->d_coef);
     fr(h->d_tabs);
@@ -2019,6 +2022,7 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
             // reserve virtual ranges as large as the device's memory; physical pages follow demand
             size_t free_b = 0, total_b = 0;
             if (const char* lim = getenv("BRISK_ARENA_LIMIT")) h->arena_limit = strtoull(lim, nullptr, 10);
+            if (const char* pc = getenv("BRISK_INTAKE_PIECE")) h->intake_piece = std::max<u64>(1, strtoull(pc, nullptr, 10));
             const char* novmm = getenv("BRISK_NO_VMM");
             if (!(novmm && novmm[0] == '1') && hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) {
                 const u64 max_entries = total_b / 17;
@@ -2524,6 +2528,258 @@ BRISK_API int brisk_hip_trim_reads(brisk_hip_index* h, const char* bases, const 
     return check_device_flags(h);
 }
 
+// ---- raw read intake: rule, passes, the host calls (clean_dna of counter.cpp:130-169 in bulk; kernels: brisk_intake.hip) ----
+static_assert(sizeof(brisk_hip_fragment) == 16 && sizeof(IntakeFragment) == 16 && offsetof(brisk_hip_fragment, start) == offsetof(IntakeFragment, start) &&
+                  offsetof(brisk_hip_fragment, len) == offsetof(IntakeFragment, len),
+              "the kernels write the C-ABI's fragment");
+static_assert(sizeof(brisk_hip_intake_rule) == 16 && sizeof(brisk_hip_intake_stats) == 64, "include/brisk_hip.h: 16 / 16 / 64 bytes");
+static_assert(BRISK_HIP_INTAKE_BLOCK == INTAKE_BLOCK, "the header names the kernels' block");
+
+// *min_len: the effective one, max(rule.min_len, k); *thr: 0 for no quality cut, else qual_base + min_qual
+static int check_intake_rule(brisk_hip_index* h, const brisk_hip_intake_rule* rule, bool have_quals, const char* who, u32* min_len, u32* thr) {
+    if (!rule) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": null rule");
+    if (rule->struct_size < sizeof(brisk_hip_intake_rule)) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.struct_size is smaller than brisk_hip_intake_rule");
+    if (rule->min_qual > 93) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.min_qual " + std::to_string(rule->min_qual) + " is above 93");
+    if (rule->qual_base != 0 && rule->qual_base != 33 && rule->qual_base != 64) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.qual_base is " + std::to_string(rule->qual_base) + ", not 33 or 64");
+    if (rule->min_qual && !have_quals) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.min_qual > 0 needs the qualities");
+    *min_len = std::max<u32>(rule->min_len, h->P.k);
+    *thr = rule->min_qual ? (rule->qual_base ? rule->qual_base : 33u) + rule->min_qual : 0u;
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held; the rule is checked.  The table is checked and the counts are taken first (two host synchronisations),
+// the fragment rows go to scratch (ink_tab: rows, then starts, then source positions), and only when the caller's room suffices
+// are they copied out and the stream gathered: a refused call writes nothing.  d_out_starts == NULL (the host calls): the rows stay
+// in scratch.  d_bases / d_quals are indexed by the table's offsets; neither is read outside [offsets[0], offsets[n_reads]).
+static int intake_impl(brisk_hip_index* h, const uint8_t* d_bases, const uint8_t* d_quals, const u64* d_offsets, u64 n_reads, u32 min_len, u32 thr, u32* d_out, u64 cap_words,
+                       u64* d_out_starts, IntakeFragment* d_out_frags, u64 frag_cap, brisk_hip_intake_stats* st) {
+    int rc;
+    memset(st, 0, sizeof(*st));
+    st->n_reads = n_reads;
+    // (k >= 5 on every handle that create accepts; the gather's LDS stage is sized by this bound)
+    if (min_len < INTAKE_MIN_LEN) return fail(h, BRISK_HIP_EUNSUPPORTED, "intake: fragments of fewer than " + std::to_string(INTAKE_MIN_LEN) + " nucleotides");
+    u64 lo = 0, hi = 0, a0 = 0, n_lanes = 0;
+    u32 nb = 0;
+    u64 *d_carry = nullptr, *d_first = nullptr;
+    if (n_reads) {
+        if ((rc = ensure(h, h->ink_tmp, 64))) return rc;
+        unsigned long long* d_flags = (unsigned long long*)h->ink_tmp.p;
+        HIPCHK(h, hipMemsetAsync(d_flags, 0, 8, h->stream));
+        if (n_reads > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "intake: more reads than one launch covers");
+        hipLaunchKernelGGL(k_intake_check, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_offsets, n_reads, d_flags);
+        if ((rc = launch_check(h, "k_intake_check"))) return rc;
+        u64 got[3] = {0, 0, 0};
+        HIPCHK(h, hipMemcpyAsync(got, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 1, d_offsets, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 2, d_offsets + n_reads, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (got[0] & 1) return fail(h, BRISK_HIP_EINVAL, "intake: read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (got[0] & 2) return fail(h, BRISK_HIP_EINVAL, "intake: a read of 2^32 bytes or more does not fit the fragment record");
+        lo = got[1];
+        hi = got[2];
+        st->n_bases_in = hi - lo;
+    }
+    if (hi > lo) {
+        a0 = lo - ((uintptr_t)(d_bases + lo) & 15);  // (may wrap below zero: positions are taken relative to it, modulo 2^64)
+        const u64 lo_x = lo - a0, hi_x = hi - a0;
+        const u64 nb64 = (hi_x + INTAKE_BLOCK - 1) / INTAKE_BLOCK;
+        if (nb64 > 0x7fffffffull) return fail(h, BRISK_HIP_EINVAL, "intake: more input blocks than one launch covers");
+        nb = (u32)nb64;
+        n_lanes = nb64 * 256;
+        if ((rc = ensure(h, h->ink_mask, n_lanes * 4))) return rc;
+        // [64 bytes of flags][the blocks' run begins, nb + 1][block sums: cut bases, cut qualities, fragments, nucleotides, short, nb + 1 each]
+        // [the partials of the two-level scans, nb2 + 1 for each of the six]
+        const u32 nb2 = nblocks(nb, INTAKE_SCAN);
+        // [per block, nb + 1: the first read that starts in or behind it]
+        if ((rc = ensure(h, h->ink_tmp, 64 + 7 * ((size_t)nb + 1) * 8 + 6 * ((size_t)nb2 + 1) * 8))) return rc;
+        d_carry = (u64*)((char*)h->ink_tmp.p + 64);
+        u64 *d_bs[5], *d_part[6];
+        for (int i = 0; i < 5; i++) d_bs[i] = d_carry + (size_t)(i + 1) * (nb + 1);
+        for (int i = 0; i < 6; i++) d_part[i] = d_carry + (size_t)6 * (nb + 1) + (size_t)i * (nb2 + 1);
+        d_first = d_carry + (size_t)6 * (nb + 1) + (size_t)6 * (nb2 + 1);
+        HIPCHK(h, hipMemsetAsync(h->ink_mask.p, 0, n_lanes * 4, h->stream));
+        {
+            ProfScope ps(h, S_INTAKE);
+            hipLaunchKernelGGL(k_intake_bounds, dim3(nblocks(n_reads + 1, 256)), dim3(256), 0, h->stream, d_offsets, n_reads, a0, n_lanes, (u32*)h->ink_mask.p);
+            hipLaunchKernelGGL(k_intake_first, dim3(nblocks((u64)nb + 1, 256)), dim3(256), 0, h->stream, d_offsets, n_reads, a0, (u64)nb, d_first);
+            hipLaunchKernelGGL(k_intake_mask, dim3(nb), dim3(256), 0, h->stream, d_bases, d_quals, a0, lo_x, hi_x, thr, (u32*)h->ink_mask.p, d_carry, d_bs[0], d_bs[1]);
+            hipLaunchKernelGGL(k_intake_reduce<true>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_carry, nb, d_part[5]);
+            hipLaunchKernelGGL(k_intake_top, dim3(1), dim3(1024), 0, h->stream, d_part[5], nb2);
+            hipLaunchKernelGGL(k_intake_spread<true>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, d_carry, nb, (const u64*)d_part[5]);
+            hipLaunchKernelGGL(k_intake_count, dim3(nb), dim3(256), 0, h->stream, (const u32*)h->ink_mask.p, n_lanes, (const u64*)d_carry, min_len, d_bs[2], d_bs[3], d_bs[4]);
+            for (int i = 0; i < 5; i++) {  // the totals of all five; the exclusive prefixes of the fragments and their nucleotides, which the apply pass takes
+                hipLaunchKernelGGL(k_intake_reduce<false>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_bs[i], nb, d_part[i]);
+                hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_part[i], nb2);
+                if (i == 2 || i == 3) hipLaunchKernelGGL(k_intake_spread<false>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, d_bs[i], nb, (const u64*)d_part[i]);
+            }
+            if ((rc = launch_check(h, "k_intake_bounds / k_intake_first / k_intake_mask / k_intake_reduce / k_intake_top / k_intake_spread / k_intake_count / k_slot_top"))) return rc;
+        }
+        u64 tot[5] = {0, 0, 0, 0, 0};
+        for (int i = 0; i < 5; i++) HIPCHK(h, hipMemcpyAsync(tot + i, d_part[i] + nb2, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        st->n_cut_base = tot[0];
+        st->n_cut_qual = tot[1];
+        st->n_fragments = tot[2];
+        st->n_nts = tot[3];
+        st->n_short = tot[4];
+    }
+    const u64 n_frag = st->n_fragments, n_words = (st->n_nts + 15) / 16;
+    IntakeFragment* d_rows = nullptr;
+    u64 *d_starts = nullptr, *d_src = nullptr;
+    if (n_frag) {
+        const u32 nbk = nblocks(n_frag, 256);
+        const u32 nbk2 = nblocks(nbk, INTAKE_SCAN);
+        if ((rc = ensure(h, h->ink_tab, n_frag * 16 + (n_frag + 1) * 8 + n_frag * 8 + ((size_t)nbk + 1) * 8 + ((size_t)nbk2 + 1) * 8))) return rc;
+        d_rows = (IntakeFragment*)h->ink_tab.p;
+        d_starts = (u64*)(d_rows + n_frag);
+        d_src = d_starts + n_frag + 1;
+        u64* d_kept = d_src + n_frag;
+        const u64* d_bs_frag = d_carry + (size_t)3 * (nb + 1);
+        const u64* d_bs_nts = d_carry + (size_t)4 * (nb + 1);
+        {
+            ProfScope ps(h, S_INTAKE);
+            hipLaunchKernelGGL(k_intake_apply, dim3(nb), dim3(256), 0, h->stream, (const u32*)h->ink_mask.p, n_lanes, (const u64*)d_carry, min_len, d_bs_frag, d_bs_nts, d_offsets, n_reads, a0,
+                               (const u64*)d_first, d_rows, d_starts, d_src);
+            hipLaunchKernelGGL(k_intake_kept, dim3(nbk), dim3(256), 0, h->stream, (const IntakeFragment*)d_rows, n_frag, d_kept);
+            u64* d_kept2 = d_kept + nbk + 1;
+            hipLaunchKernelGGL(k_intake_reduce<false>, dim3(nbk2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_kept, nbk, d_kept2);
+            hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_kept2, nbk2);
+            if ((rc = launch_check(h, "k_intake_apply / k_intake_kept / k_intake_reduce / k_slot_top"))) return rc;
+        }
+        HIPCHK(h, hipMemcpyAsync(&st->n_reads_kept, d_kept + nbk + 1 + nbk2, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (frag_cap < n_frag)
+        return fail(h, BRISK_HIP_ECAPACITY, "intake: " + std::to_string(n_frag) + " fragments, frag_cap is " + std::to_string(frag_cap));
+    if (d_out && cap_words < n_words + 2)
+        return fail(h, BRISK_HIP_ECAPACITY, "intake: " + std::to_string(st->n_nts) + " nucleotides need " + std::to_string(n_words + 2) + " words, out_cap_words is " + std::to_string(cap_words));
+    if (!n_frag) {  // no fragment: the empty stream
+        if (d_out_starts) HIPCHK(h, hipMemsetAsync(d_out_starts, 0, 8, h->stream));
+        if (d_out) HIPCHK(h, hipMemsetAsync(d_out, 0, 8, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    }
+    if (d_out_starts) HIPCHK(h, hipMemcpyAsync(d_out_starts, d_starts, (n_frag + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (d_out_frags) HIPCHK(h, hipMemcpyAsync(d_out_frags, d_rows, n_frag * 16, hipMemcpyDeviceToDevice, h->stream));
+    if (d_out) {
+        if (n_words + 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "intake: more output words than one launch covers");
+        ProfScope ps(h, S_INTAKE);
+        hipLaunchKernelGGL(k_intake_gather, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_bases, hi, (const u64*)d_starts, (const u64*)d_src, n_frag, n_words, d_out);
+        if ((rc = launch_check(h, "k_intake_gather"))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_intake_ascii(brisk_hip_index* h, const char* d_bases, const char* d_quals, const uint64_t* d_offsets, uint64_t n_reads, const brisk_hip_intake_rule* rule,
+                                     uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, brisk_hip_fragment* d_out_frags, uint64_t frag_cap,
+                                     brisk_hip_intake_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    u32 min_len = 0, thr = 0;
+    if (int rrc = check_intake_rule(h, rule, d_quals != nullptr, "intake_ascii", &min_len, &thr)) return rrc;
+    if (!stats || !d_out_starts || (n_reads && (!d_bases || !d_offsets))) return fail(h, BRISK_HIP_EINVAL, "intake_ascii: null pointer");
+    if (!d_out_packed && out_cap_words) return fail(h, BRISK_HIP_EINVAL, "intake_ascii: out_cap_words without d_out_packed");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    return intake_impl(h, (const uint8_t*)d_bases, (const uint8_t*)d_quals, d_offsets, n_reads, min_len, thr, d_out_packed, out_cap_words, d_out_starts, (IntakeFragment*)d_out_frags,
+                       frag_cap, stats);
+}
+
+// host reads -> the device, as they are, in pieces of whole reads (at least one) of about h->intake_piece bytes; body(r0, nr, d_bases,
+// d_quals, d_offsets): the piece's table holds the caller's offsets, and the two pointers are displaced so that those index them
+extern "C++" template <class F>
+static int for_each_raw_piece(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, F&& body) {
+    for (u64 r0 = 0; r0 < n_reads;) {
+        const u64 r_hi = std::min<u64>(n_reads, r0 + (1ull << 26));
+        u64 r1 = (u64)(std::upper_bound(offsets + r0, offsets + r_hi + 1, offsets[r0] + h->intake_piece) - offsets) - 1;
+        if (r1 <= r0) r1 = r0 + 1;
+        const u64 nb = offsets[r1] - offsets[r0], nr = r1 - r0, pad = (nb + 15) & ~15ull;
+        int rc;
+        if ((rc = ensure(h, h->ink_raw, (quals ? 2 : 1) * pad + 16))) return rc;
+        if ((rc = ensure(h, h->ink_offs, (nr + 1) * 8))) return rc;
+        uint8_t* d_b = (uint8_t*)h->ink_raw.p;
+        uint8_t* d_q = quals ? d_b + pad : nullptr;
+        if (nb) {
+            HIPCHK(h, hipMemcpyAsync(d_b, bases + offsets[r0], nb, hipMemcpyHostToDevice, h->stream));
+            if (quals) HIPCHK(h, hipMemcpyAsync(d_q, quals + offsets[r0], nb, hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCHK(h, hipMemcpyAsync(h->ink_offs.p, offsets + r0, (nr + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        if ((rc = body(r0, nr, (const uint8_t*)(d_b - offsets[r0]), quals ? (const uint8_t*)(d_q - offsets[r0]) : nullptr, (const u64*)h->ink_offs.p))) return rc;
+        r0 = r1;
+    }
+    return BRISK_HIP_OK;
+}
+
+static int check_raw_reads(brisk_hip_index* h, const uint64_t* offsets, uint64_t n_reads, const char* who) {
+    for (u64 r = 0; r < n_reads; r++) {
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (offsets[r + 1] - offsets[r] > 0xffffffffull) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": a read of 2^32 bytes or more does not fit the fragment record");
+    }
+    return BRISK_HIP_OK;
+}
+static void add_intake_stats(brisk_hip_intake_stats* sum, const brisk_hip_intake_stats& st) {
+    uint64_t* a = (uint64_t*)sum;
+    const uint64_t* b = (const uint64_t*)&st;
+    for (size_t i = 0; i < sizeof(st) / 8; i++) a[i] += b[i];
+}
+
+BRISK_API int brisk_hip_intake_reads(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, const brisk_hip_intake_rule* rule,
+                                     brisk_hip_fragment* out_frags, uint64_t frag_cap, brisk_hip_intake_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    u32 min_len = 0, thr = 0;
+    if (int rrc = check_intake_rule(h, rule, quals != nullptr, "intake_reads", &min_len, &thr)) return rrc;
+    if (!stats || (frag_cap && !out_frags) || (n_reads && (!bases || !offsets))) return fail(h, BRISK_HIP_EINVAL, "intake_reads: null pointer");
+    if (int orc = check_raw_reads(h, offsets, n_reads, "intake_reads")) return orc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    memset(stats, 0, sizeof(*stats));
+    int rc = for_each_raw_piece(h, bases, thr ? quals : nullptr, offsets, n_reads, [&](u64 r0, u64 nr, const uint8_t* d_b, const uint8_t* d_q, const u64* d_offs) -> int {
+        brisk_hip_intake_stats st;
+        if (int rc2 = intake_impl(h, d_b, d_q, d_offs, nr, min_len, thr, nullptr, 0, nullptr, nullptr, ~0ull, &st)) return rc2;
+        const u64 at = stats->n_fragments;
+        if (st.n_fragments && at + st.n_fragments <= frag_cap) {  // (past the caller's room the pieces are still counted: the stats are whole)
+            HIPCHK(h, hipMemcpyAsync(out_frags + at, h->ink_tab.p, st.n_fragments * 16, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            for (u64 j = 0; j < st.n_fragments; j++) out_frags[at + j].read += r0;  // the device counted the piece's reads
+        }
+        add_intake_stats(stats, st);
+        return BRISK_HIP_OK;
+    });
+    if (rc) return rc;
+    if (stats->n_fragments > frag_cap) return fail(h, BRISK_HIP_ECAPACITY, "intake_reads: " + std::to_string(stats->n_fragments) + " fragments, frag_cap is " + std::to_string(frag_cap));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_insert_raw_reads(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, const brisk_hip_intake_rule* rule,
+                                         brisk_hip_intake_stats* stats) {
+    if (!h || (n_reads && (!bases || !offsets))) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "insert_reads on a sharded index: use scan/route/insert_records");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "bulk count on an entry-id index");
+    u32 min_len = 0, thr = 0;
+    if (int rrc = check_intake_rule(h, rule, quals != nullptr, "insert_raw_reads", &min_len, &thr)) return rrc;
+    if (int orc = check_raw_reads(h, offsets, n_reads, "insert_raw_reads")) return orc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    brisk_hip_intake_stats sum;
+    memset(&sum, 0, sizeof(sum));
+    if (stats) *stats = sum;
+    int rc = for_each_raw_piece(h, bases, thr ? quals : nullptr, offsets, n_reads, [&](u64 r0, u64 nr, const uint8_t* d_b, const uint8_t* d_q, const u64* d_offs) -> int {
+        // the piece's packed stream and its starts: what always suffices (include/brisk_hip.h)
+        const u64 nb = offsets[r0 + nr] - offsets[r0], cap_words = (nb + 15) / 16 + 2, cap_frag = nb / min_len, words_room = (cap_words + 1) & ~1ull;
+        if (int rc2 = ensure(h, h->ink_packed, words_room * 4 + (cap_frag + 1) * 8)) return rc2;
+        u32* d_packed = (u32*)h->ink_packed.p;
+        u64* d_starts = (u64*)(d_packed + words_room);
+        brisk_hip_intake_stats st;
+        if (int rc2 = intake_impl(h, d_b, d_q, d_offs, nr, min_len, thr, d_packed, cap_words, d_starts, nullptr, cap_frag, &st)) return rc2;
+        add_intake_stats(&sum, st);
+        // the scan of this stream is queued before insert_packed_impl returns (a deferred insert keeps records, not the stream), and the
+        // next piece's writes follow it on the handle's stream: the scratch is free for them
+        return insert_packed_impl(h, d_packed, d_starts, st.n_fragments);
+    });
+    if (stats) *stats = sum;
+    return rc;
+}
+
 BRISK_API int brisk_hip_lookup(brisk_hip_index* h, const uint64_t* kmer_lo, const uint64_t* kmer_hi, const uint8_t* minimizer_idx, uint64_t n,
                                uint8_t* out_data, uint8_t* out_found) {
     if (!h || (n && (!kmer_lo || !kmer_hi || !minimizer_idx || !out_data || !out_found))) return BRISK_HIP_EINVAL;
@@ -2730,7 +2986,7 @@ BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t
     if (memory_bytes) {
         u64 m = h->arena_cap * (8ull * h->ix.key_words + 1) + h->n_parts * 16 + (h->n_buckets + 7) / 8 + (h->n_parts + 1) * 20;
         for (const DevBuf* b : {&h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp,
-                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src})
+                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed})
             m += b->bytes;
         *memory_bytes = m;
     }

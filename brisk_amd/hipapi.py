@@ -34,7 +34,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU). In-tree output."""
     out = library_path()
     srcs = [os.path.join(HERE, "csrc", f) for f in ("brisk_capi.hip", "brisk_kernels.hip", "brisk_scan.hip", "brisk_partition.hip", "brisk_insert.hip",
-                                                    "brisk_readout.hip", "brisk_answers.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_extract.hip", "brisk_device.h")]
+                                                    "brisk_readout.hip", "brisk_answers.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_extract.hip", "brisk_intake.hip", "brisk_device.h")]
     srcs.append(os.path.join(ROOT, "include", "brisk_hip.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
@@ -125,6 +125,7 @@ SYMBOLS = [
     "brisk_hip_read_profile_reads", "brisk_hip_read_profile_packed",
     "brisk_hip_scan_kmers", "brisk_hip_record_kmers", "brisk_hip_answer_records", "brisk_hip_place_answers", "brisk_hip_profile_slots",
     "brisk_hip_select_intervals", "brisk_hip_extract_packed", "brisk_hip_trim_packed", "brisk_hip_trim_reads", "brisk_hip_unpack_ascii",
+    "brisk_hip_intake_ascii", "brisk_hip_intake_reads", "brisk_hip_insert_raw_reads",
     "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_joint_spectrum", "brisk_hip_filter_joint", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
     "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
@@ -167,6 +168,10 @@ def load() -> C.CDLL:
     L.brisk_hip_trim_packed.argtypes = [vp, vp, vp, u64, u32, C.POINTER(_SelectRule), vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.brisk_hip_trim_reads.argtypes = [vp, _u8p, _u64p, u64, u32, C.POINTER(_SelectRule), _ivp]
     L.brisk_hip_unpack_ascii.argtypes = [vp, vp, u64, u64, vp]
+    _fragp = np.ctypeslib.ndpointer(dtype=FRAGMENT_DTYPE, flags="C_CONTIGUOUS")
+    L.brisk_hip_intake_ascii.argtypes = [vp, vp, vp, vp, u64, C.POINTER(_IntakeRule), vp, u64, vp, vp, u64, C.POINTER(_IntakeStats)]
+    L.brisk_hip_intake_reads.argtypes = [vp, vp, vp, _u64p, u64, C.POINTER(_IntakeRule), _fragp, u64, C.POINTER(_IntakeStats)]
+    L.brisk_hip_insert_raw_reads.argtypes = [vp, vp, vp, _u64p, u64, C.POINTER(_IntakeRule), C.POINTER(_IntakeStats)]
     L.brisk_hip_enumerate.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64)]
     L.brisk_hip_stats.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.brisk_hip_checksum.argtypes = [vp, _u64p]
@@ -326,6 +331,104 @@ def intervals_from_profile(profile, k: int, rule) -> np.ndarray:
     out["start"] = np.where(keep, start, 0)
     out["len"] = np.where(keep, length, 0)
     return out
+
+
+# brisk_hip_fragment (include/brisk_hip.h): bytes [start, start + len) of read `read`; 16 bytes, little-endian, no padding
+FRAGMENT_DTYPE = np.dtype([("read", "<u8"), ("start", "<u4"), ("len", "<u4")])
+assert FRAGMENT_DTYPE.itemsize == 16
+INTAKE_STATS_FIELDS = ("n_reads", "n_reads_kept", "n_fragments", "n_bases_in", "n_nts", "n_cut_base", "n_cut_qual", "n_short")
+INTAKE_BLOCK = 4096  # BRISK_HIP_INTAKE_BLOCK: input bytes per thread block of the intake kernels
+
+
+class _IntakeRule(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "min_len", "min_qual", "qual_base")]
+
+
+class _IntakeStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in INTAKE_STATS_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in INTAKE_STATS_FIELDS}
+
+
+class _Fragment(C.Structure):
+    _fields_ = [("read", C.c_uint64), ("start", C.c_uint32), ("len", C.c_uint32)]
+
+
+def intake_rule(min_len: int = 0, min_qual: int = 0, qual_base: int = 33) -> _IntakeRule:
+    """A brisk_hip_intake_rule: a fragment has at least max(min_len, k) nucleotides; a base whose quality byte is below qual_base +
+    min_qual is cut like an N (min_qual 0: no quality cut); qual_base 33 or 64.  Nothing is checked here: the library (EINVAL) and
+    fragments_from_reads (ValueError) refuse min_qual > 93 and any other qual_base."""
+    return _IntakeRule(C.sizeof(_IntakeRule), min_len, min_qual, qual_base)
+
+
+_IS_BASE = np.zeros(256, bool)
+_IS_BASE[list(b"ACGTacgt")] = True
+
+
+def _as_bytes_list(seqs) -> list:
+    return [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
+
+
+def fragments_from_reads(seqs, quals, k: int, rule=None):
+    """The rule of brisk_hip_intake_* on the host: (FRAGMENT_DTYPE[n_fragments], stats dict).  The definition, written out; no device
+    needed.  A byte is valid when it is one of ACGTacgt and either min_qual == 0 or its quality byte >= qual_base + min_qual; a
+    fragment is a maximal run of valid bytes inside one read, of at least max(min_len, k) bytes; fragments are ordered by read, then
+    by position.  seqs[f.read][f.start:f.start + f.len] is fragment f's string."""
+    rule = intake_rule() if rule is None else rule
+    qual_base = rule.qual_base or 33
+    if rule.struct_size < C.sizeof(_IntakeRule) or rule.min_qual > 93 or qual_base not in (33, 64):
+        raise ValueError("not a rule: struct_size %d min_qual %d qual_base %d" % (rule.struct_size, rule.min_qual, rule.qual_base))
+    bs = _as_bytes_list(seqs)
+    qs = None if quals is None else _as_bytes_list(quals)
+    if rule.min_qual and qs is None:
+        raise ValueError("min_qual > 0 needs the qualities")
+    if qs is not None and [len(q) for q in qs] != [len(b) for b in bs]:
+        raise ValueError("a quality string differs in length from its read")
+    min_len = max(int(rule.min_len), k)
+    st = dict.fromkeys(INTAKE_STATS_FIELDS, 0)
+    st["n_reads"] = len(bs)
+    rows = []
+    for r, b in enumerate(bs):
+        a = np.frombuffer(b, np.uint8)
+        base = _IS_BASE[a]
+        valid = base
+        if rule.min_qual:
+            valid = base & (np.frombuffer(qs[r], np.uint8) >= qual_base + rule.min_qual)
+        st["n_bases_in"] += len(a)
+        st["n_cut_base"] += int((~base).sum())
+        st["n_cut_qual"] += int((base & ~valid).sum())
+        edge = np.diff(np.concatenate(([0], valid.astype(np.int8), [0])))
+        starts, ends = np.nonzero(edge == 1)[0], np.nonzero(edge == -1)[0]
+        lens = ends - starts
+        keep = lens >= min_len
+        st["n_short"] += int(lens[~keep].sum())
+        st["n_nts"] += int(lens[keep].sum())
+        st["n_fragments"] += int(keep.sum())
+        st["n_reads_kept"] += bool(keep.any())
+        rows.extend((r, int(s), int(n)) for s, n in zip(starts[keep], lens[keep]))
+    return np.array(rows, FRAGMENT_DTYPE) if rows else np.zeros(0, FRAGMENT_DTYPE), st
+
+
+def _pack_raw(seqs, quals):
+    """(flat bases, flat qualities or None, offsets) of str / bytes reads; ValueError where a quality string's length is not its read's"""
+    bs = _as_bytes_list(seqs)
+    flat, offs = _pack_reads(bs)
+    qflat = None
+    if quals is not None:
+        qs = _as_bytes_list(quals)
+        if len(qs) != len(bs) or any(len(q) != len(b) for q, b in zip(qs, bs)):
+            raise ValueError("a quality string differs in length from its read")
+        qflat, _ = _pack_reads(qs)
+    return flat, qflat, offs
+
+
+_ONE_BYTE = np.zeros(1, np.uint8)  # what an empty array's pointer stands on: it lives as long as the module
+
+
+def _host_ptr(a):
+    """the address of a numpy array's bytes (of _ONE_BYTE for an empty one: a non-null pointer of which nothing is read), or None"""
+    return None if a is None else C.c_void_p(a.ctypes.data if len(a) else _ONE_BYTE.ctypes.data)
 
 
 def joint_spectrum_from_entries(dump_a, dump_b) -> np.ndarray:
@@ -506,6 +609,30 @@ class BriskHip:
         rule = select_rule("solid_run") if rule is None else rule
         self._chk(self.L.brisk_hip_trim_reads(self.h, flat, offs, len(offs) - 1, solid_min, C.byref(rule), out))
         return out[:len(offs) - 1]
+
+    def intake(self, seqs: Sequence, quals: Optional[Sequence] = None, rule: Optional[_IntakeRule] = None):
+        """The fragments of raw reads (brisk_hip_intake_reads): (FRAGMENT_DTYPE[n_fragments], stats dict) -- what
+        fragments_from_reads(seqs, quals, k, rule) gives, computed on the device: maximal runs of ACGTacgt (at or above the quality
+        threshold) inside one read, at least max(rule.min_len, k) long.  seqs[f.read][f.start:f.start + f.len] is fragment f's string.
+        seqs and quals are str or bytes; ValueError where a quality string's length is not its read's.  Needs no index state."""
+        flat, qflat, offs = _pack_raw(seqs, quals)
+        rule = intake_rule() if rule is None else rule
+        st = _IntakeStats()
+        cap = max(1, len(flat) // max(1, max(int(rule.min_len), self.k)))
+        out = np.zeros(cap, FRAGMENT_DTYPE)
+        self._chk(self.L.brisk_hip_intake_reads(self.h, _host_ptr(flat), _host_ptr(qflat), offs, len(offs) - 1, C.byref(rule), out, cap, C.byref(st)))
+        return out[:st.n_fragments].copy(), st.as_dict()
+
+    def insert_raw(self, seqs: Sequence, quals: Optional[Sequence] = None, rule: Optional[_IntakeRule] = None) -> dict:
+        """Count raw reads (brisk_hip_insert_raw_reads): the bytes go to the device as they are, are cut there at every byte that is not
+        a base (and, with rule.min_qual, at every base below the quality threshold), and the fragments are inserted.  The index is the
+        one insert_reads builds from the fragments' strings.  Returns the intake's stats.  Clean input should stay on insert_reads,
+        which sends 2 bits per nucleotide to the device where this sends 8, or 16 with qualities."""
+        flat, qflat, offs = _pack_raw(seqs, quals)
+        rule = intake_rule() if rule is None else rule
+        st = _IntakeStats()
+        self._chk(self.L.brisk_hip_insert_raw_reads(self.h, _host_ptr(flat), _host_ptr(qflat), offs, len(offs) - 1, C.byref(rule), C.byref(st)))
+        return st.as_dict()
 
     def lookup(self, lo, hi, idx) -> Tuple[np.ndarray, np.ndarray]:
         lo = np.ascontiguousarray(lo, np.uint64)
@@ -815,6 +942,19 @@ class BriskHip:
 
     def pack_ascii(self, d_bases: int, n_bases: int, d_packed: int):
         self._chk(self.L.brisk_hip_pack_ascii(self.h, d_bases, n_bases, d_packed))
+
+    def intake_ascii(self, d_bases: int, d_quals: int, d_offsets: int, n_reads: int, rule: _IntakeRule, d_out_packed: int, out_cap_words: int,
+                     d_out_starts: int, d_out_frags: int, frag_cap: int, raise_on_capacity: bool = True) -> dict:
+        """Raw bytes on the device -> fragments as a packed stream (brisk_hip_intake_ascii); d_quals, d_out_packed (with out_cap_words
+        0) and d_out_frags may be 0.  Returns the stats; with raise_on_capacity=False an ECAPACITY answer returns them too, with
+        "rc" set, so that the call can be repeated with room."""
+        st = _IntakeStats()
+        rc = self.L.brisk_hip_intake_ascii(self.h, d_bases or None, d_quals or None, d_offsets or None, n_reads, C.byref(rule) if rule is not None else None,
+                                           d_out_packed or None, out_cap_words, d_out_starts or None, d_out_frags or None, frag_cap, C.byref(st))
+        if rc == ECAPACITY and not raise_on_capacity:
+            return dict(st.as_dict(), rc=rc)
+        self._chk(rc)
+        return st.as_dict()
 
     def unpack_ascii(self, d_packed: int, first_nt: int, n_nts: int, d_bases: int):
         """d_bases[i] = "ACTG"[code of nucleotide first_nt + i of the packed stream] (brisk_hip_unpack_ascii): pack_ascii's inverse"""

@@ -54,6 +54,10 @@
  *                               no reference counterpart (khmer's trim-low-abund and normalize-by-median act on the abundances
  *                               that brisk_hip_read_profile_* measures): a profile record becomes a nucleotide interval of its
  *                               read, and the kept intervals a new packed stream, on the device
+ *   brisk_hip_intake_ascii / brisk_hip_intake_reads / brisk_hip_insert_raw_reads
+ *                               no reference counterpart as a library call: with min_qual == 0 they restate, in bulk and on the
+ *                               device, clean_dna (apps/counter.cpp:130-169), which cuts a record at every byte that is not a
+ *                               base; the quality cut is Jellyfish's --min-qual-char and KMC's handling of N
  *   brisk_hip_lookup            Brisk::get (brisk/Brisk.hpp:64-69)
  *   brisk_hip_enumerate         Brisk::next / restart_kmer_enumeration
  *                               (brisk/Brisk.hpp:166-179, brisk/DenseMenuYo.hpp:476-521)
@@ -209,7 +213,9 @@ int brisk_hip_get_layout(const brisk_hip_index *h, brisk_hip_layout *out);
  * pieces: a dozen host threads turn the bytes into the 2-bit stream (nuc2int, Kmers.cpp:442-444)
  * while they stage them into pinned memory, and the scan of one piece runs under the upload of
  * the next (environment: BRISK_UPLOAD_LANES, BRISK_PIPE_PIECES, BRISK_UPLOAD_PIPELINE=0,
- * BRISK_HOST_PACK=0 for ASCII over PCIe and k_pack_ascii on arrival). */
+ * BRISK_HOST_PACK=0 for ASCII over PCIe and k_pack_ascii on arrival).  Non-base bytes are not
+ * detected here (each is counted as the base its bits 1-2 spell): brisk_hip_insert_raw_reads is
+ * the entry point for input that may hold them. */
 int brisk_hip_insert_reads(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads);
 
 /* DEVICE buffers: 2-bit packed stream (16 nts per u32, first nt in the top bits;
@@ -336,6 +342,64 @@ int brisk_hip_trim_packed(brisk_hip_index *h, const uint32_t *d_packed, const ui
                           uint64_t *n_out_reads, uint64_t *n_out_nts);
 int brisk_hip_trim_reads(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
                          uint32_t solid_min, const brisk_hip_select_rule *rule, brisk_hip_read_interval *out /* HOST, n_reads */);
+
+/* ---- raw read intake: N and quality cuts on the device (kernels: brisk_intake.hip) ----------------------------------------- */
+/* Input: `bases`, bytes of any value; `quals`, bytes aligned with them, or NULL; offsets[n_reads + 1], ascending byte offsets (read r
+ * is [offsets[r], offsets[r + 1]); empty reads are allowed).  A byte is VALID when it is one of ACGTacgt and either min_qual == 0 or
+ * its quality byte >= qual_base + min_qual (unsigned compare).  A FRAGMENT is a maximal run of valid bytes inside one read (a run
+ * never crosses a read boundary) of at least L = max(min_len, k) bytes, k the handle's.  Fragments are ordered by read, then by
+ * position.  With min_qual == 0 the fragments of a record body are the sequences of at least k nucleotides that clean_dna
+ * (counter.cpp:130-169) cuts it into.  brisk_amd.fragments_from_reads is the same rule in numpy: the definition the tests compare with.
+ * EINVAL: a null rule, a short struct_size, min_qual > 93, a qual_base other than 0 / 33 / 64, min_qual > 0 with NULL quals, a read of
+ * 2^32 bytes or more, offsets that do not ascend. */
+typedef struct brisk_hip_intake_rule {
+    uint32_t struct_size;
+    uint32_t min_len;    /* a fragment has at least max(min_len, k) nucleotides; 0 means k */
+    uint32_t min_qual;   /* 0..93; 0: no quality cut, quals may be NULL */
+    uint32_t qual_base;  /* 33 or 64; 0 means 33 */
+} brisk_hip_intake_rule;
+typedef struct brisk_hip_fragment { uint64_t read; uint32_t start, len; } brisk_hip_fragment; /* 16 bytes; start is relative to the read */
+typedef struct brisk_hip_intake_stats {
+    uint64_t n_reads;
+    uint64_t n_reads_kept;  /* reads with at least one fragment */
+    uint64_t n_fragments;
+    uint64_t n_bases_in;    /* offsets[n_reads] - offsets[0] */
+    uint64_t n_nts;         /* bytes inside fragments */
+    uint64_t n_cut_base;    /* bytes that are not one of the eight letters */
+    uint64_t n_cut_qual;    /* bytes that are a base but below the quality threshold */
+    uint64_t n_short;       /* valid bytes in runs shorter than L */
+} brisk_hip_intake_stats;   /* n_bases_in == n_nts + n_cut_base + n_cut_qual + n_short, always */
+#define BRISK_HIP_INTAKE_BLOCK 4096 /* input bytes per thread block of the intake kernels: where a run's begin is carried across */
+/* Everything on the DEVICE except `rule` and `stats`.  Output: the layout of brisk_hip_insert_packed -- 16 nts per u32, first nt in
+ * the top bits, A0 C1 T2 G3, lower case packed as upper; the fragments concatenated at nucleotide granularity;
+ * d_out_starts[0 .. n_fragments] ascending from 0; d_out_frags[j] (may be NULL) says where fragment j came from; the unused low bits
+ * of the last word zero and the two words after it zero.  d_out_packed == NULL with out_cap_words == 0: the table and the stats only.
+ * BRISK_HIP_ECAPACITY when frag_cap < n_fragments or out_cap_words < ceil(n_nts / 16) + 2: nothing is written to the device outputs,
+ * *stats is filled, and the call can be repeated with room.  frag_cap = n_bases_in / L and out_cap_words = ceil(n_bases_in / 16) + 2
+ * always suffice.  Needs no index state: works on any handle (sharded and entry-id ones included), on the handle's stream and under
+ * its lock; it returns when the output is complete.  No byte outside [offsets[0], offsets[n_reads]) of either input is read; d_bases
+ * and d_quals may have any alignment.  The output may not overlap the inputs.  Every output word and table row is stored once, by a
+ * plain store.  Scratch memory of the handle: 4 bytes per 16 input bytes, 32 bytes per fragment. */
+int brisk_hip_intake_ascii(brisk_hip_index *h, const char *d_bases, const char *d_quals /* NULL ok */, const uint64_t *d_offsets,
+                           uint64_t n_reads, const brisk_hip_intake_rule *rule,
+                           uint32_t *d_out_packed, uint64_t out_cap_words, uint64_t *d_out_starts /* frag_cap + 1 room */,
+                           brisk_hip_fragment *d_out_frags /* frag_cap room, may be NULL */, uint64_t frag_cap,
+                           brisk_hip_intake_stats *stats /* HOST */);
+/* HOST reads in, the fragment table out (out_frags[frag_cap], HOST): the caller slices its own strings, as with brisk_hip_trim_reads.
+ * Taken in pieces of whole reads (BRISK_INTAKE_PIECE).  ECAPACITY when frag_cap < n_fragments: *stats is filled for the whole call, so
+ * it can be repeated with room; unlike the device call, out_frags is then partly written (the rows of the leading pieces that fit). */
+int brisk_hip_intake_reads(brisk_hip_index *h, const char *bases, const char *quals /* NULL ok */, const uint64_t *offsets,
+                           uint64_t n_reads, const brisk_hip_intake_rule *rule, brisk_hip_fragment *out_frags, uint64_t frag_cap,
+                           brisk_hip_intake_stats *stats);
+/* HOST reads are uploaded as they are, cut on the device, and the fragments inserted through the path brisk_hip_insert_packed takes
+ * (deferral of small batches included).  The index afterwards is bit for bit the one brisk_hip_insert_reads builds from the
+ * fragments' strings, however the call is split: a large call is taken in pieces of whole reads, at least one read per piece
+ * (BRISK_INTAKE_PIECE=<bytes> sets the piece size; a test hook, read when the handle is created).  A piece's raw bytes, fragment
+ * table and packed stream live in scratch memory of the handle.  Refused exactly where brisk_hip_insert_reads is (a sharded or
+ * entry-id index), with the same code.  This sends 8 bits per nucleotide over the host link (16 with qualities) where
+ * brisk_hip_insert_reads sends 2: clean input should stay there.  stats may be NULL. */
+int brisk_hip_insert_raw_reads(brisk_hip_index *h, const char *bases, const char *quals /* NULL ok */, const uint64_t *offsets,
+                               uint64_t n_reads, const brisk_hip_intake_rule *rule, brisk_hip_intake_stats *stats);
 
 /* point lookups of UNHASHED (kmer_s, minimizer_idx) pairs, as Brisk::get takes them.
  * HOST arrays; out_found[i] in {0,1}; out_data[i] valid when found. */
