@@ -345,6 +345,151 @@ __device__ void emit_record(const BriskParams& P, const u32* __restrict__ packed
     emit_record_at<true>(P, packed, q0, p0, n, rev, idx_end, out, tag, ret, atomicAdd(out.n_rec, (unsigned long long)superkmer_pieces<true>(P, n, idx_end)));
 }
 
+// ---- the record builder of the k63 m21 bodies: the super-k-mer in a frame anchored at its minimizer --------------------------------
+// emit_record_wide holds the span right-aligned, so the minimizer, the bucket nts and the span's top all sit at per-lane bit positions:
+// four variable 256-bit shifts, each a word-select cascade plus a funnel.  With k and m constants the frame can be pinned to the
+// minimizer instead.  A super-k-mer has at most w = k - m = 42 nts below its minimizer and at most 42 above it (record orientation),
+// so a window of AF_DW = 7 dwords with the minimizer at bits [AF_MIN, AF_MIN + 2m) = [84, 126) holds every one of them:
+//   bits [84 - 2 idx_end, 84)   suffix       [84, 126)   minimizer       [126, 126 + 2 (w - idx_first))   prefix
+// The window is loaded at a per-lane stream position (the word part of the old shifts is in the address, the sub-word part in one
+// v_alignbit per dword); a reversed record loads the window that, reverse-complemented dword by dword in place, has the minimizer at
+// the same bits.  Minimizer extraction, hash replacement and the cut of the bucket nts then happen at wave-uniform positions, and one
+// variable shift (by 84 - 2 idx_end: a word select among three, a v_alignbit per dword) right-aligns the record.
+#define AF_K 63
+#define AF_M 21
+#define AF_W (AF_K - AF_M)
+#define AF_DW 7                      // dwords of the frame: 2 (w + m + w) = 210 bits
+#define AF_MIN (2 * AF_W)            // the minimizer's low bit
+struct Frame7 {                      // named fields, never an indexed array (see W4)
+    u32 d0, d1, d2, d3, d4, d5, d6;  // d0 least significant
+};
+__device__ __forceinline__ u32 af_align(u32 hi, u32 lo, u32 s) { return __builtin_amdgcn_alignbit(hi, lo, s); }  // ({hi,lo} >> s) & ~0u, s in [0,31]
+__device__ __forceinline__ u32 rc_nts32(u32 x) {  // the 16 nts of x complemented, their order reversed
+    const u32 r = __brev(x ^ 0xaaaaaaaau);
+    return ((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1);
+}
+__device__ __forceinline__ u32 af_low_ones(int h) {  // 32 - 2h low ones, h clamped to [0,16] (two shifts: one by 32 does not exist)
+    const u32 c = (u32)min(max(h, 0), 16);
+    return (~0u >> c) >> c;
+}
+// Stream index of the nt at the frame's bit 0.  q: the span's first nt, n k-mers, idx_end as in emit_record_wide.  Forward, the
+// minimizer's last nt (frame nt 42) is stream nt q + L - idx_end - 1 and stream order runs down the frame; reversed, frame nt 42 is
+// the complement of the minimizer's first stream nt, q + idx_end, and lies at nt 111 - 42 of the window before it is turned round.
+__device__ __forceinline__ u64 af_last_nt(u64 q, u32 n, bool rev, u32 idx_end) {
+    return rev ? q + idx_end + (16 * AF_DW - 1 - AF_W) : q + (AF_K + n - 1) + (AF_W - 1) - idx_end;
+}
+// The record words (right-aligned, 2 (kb + n - 1) bits) and routing id of one super-k-mer.  e: af_last_nt(); reads stream words
+// [(e >> 4) - AF_DW, e >> 4], all eight issued before the first is used.  The caller checks that they lie inside the stream.
+__device__ __forceinline__ Frame7 anchored_record(const BriskParams& P, const u32* __restrict__ packed, u64 e, u32 n, bool rev, u32 idx_end, u32* rbase) {
+    const u32* p = packed + (e >> 4);
+    const u32 sh = 30 - 2 * ((u32)e & 15);
+    const u32 l0 = p[0], l1 = p[-1], l2 = p[-2], l3 = p[-3], l4 = p[-4], l5 = p[-5], l6 = p[-6], l7 = p[-7];
+    Frame7 f{af_align(l1, l0, sh), af_align(l2, l1, sh), af_align(l3, l2, sh), af_align(l4, l3, sh), af_align(l5, l4, sh), af_align(l6, l5, sh), af_align(l7, l6, sh)};
+    if (rev) f = Frame7{rc_nts32(f.d6), rc_nts32(f.d5), rc_nts32(f.d4), rc_nts32(f.d3), rc_nts32(f.d2), rc_nts32(f.d1), rc_nts32(f.d0)};
+    // what the window holds above the span's top (the nts before a forward span, after a reversed one) goes here, at dword
+    // granularity known at compile time; what it holds below the span's low end falls off in the final shift.  The top is bit
+    // 126 + 2 pre, pre = w - idx_first nts of prefix, 0..42
+    const u32 idx_first = idx_end - (n - 1);
+    const int pre = (int)(AF_W - idx_first);
+    f.d3 &= pre ? ~0u : 0x3fffffffu;
+    f.d4 &= af_low_ones(17 - pre);                     // 2 pre - 2 low bits
+    f.d5 &= af_low_ones(33 - pre);                     // 2 pre - 34
+    f.d6 &= (1u << (u32)max(2 * pre - 66, 0)) - 1;     // 2 pre - 66 <= 18
+    // the minimizer: bits [84, 126), inside the 64-bit pair {d3, d2}
+    u64 mid = ((u64)f.d3 << 32) | f.d2;
+    const u64 mm = (mid >> (AF_MIN - 64)) & P.m_mask;
+    const u64 h = mix2m(mm, P.m_mask);
+    *rbase = routing_base(P, h);
+    mid ^= (mm ^ h) << (AF_MIN - 64);  // replace_slice (Kmers.cpp:149-159)
+    f.d2 = (u32)mid;
+    f.d3 = (u32)(mid >> 32);
+    // get_compacted (Kmers.cpp:138-145): the b bucket nts start at bit c0 = 84 + 2 suff_reduc, inside the minimizer (dword 2 or 3);
+    // everything above them comes down by 2b <= 42 bits.  All wave-uniform: scalar masks, scalar shift
+    {
+        u32 geo = P.b | (P.suff_reduc << 8);
+        asm volatile("" : "+s"(geo));
+        const u32 c0 = AF_MIN + 2 * (geo >> 8), s = 2 * (geo & 0xff), bs = s & 31;
+        const bool ws = s >= 32;
+        const u32 a2 = ws ? f.d3 : f.d2, a3 = ws ? f.d4 : f.d3, a4 = ws ? f.d5 : f.d4, a5 = ws ? f.d6 : f.d5, a6 = ws ? 0u : f.d6;
+        const u32 r2 = af_align(a3, a2, bs), r3 = af_align(a4, a3, bs), r4 = af_align(a5, a4, bs), r5 = af_align(a6, a5, bs), r6 = a6 >> bs;
+        const u32 lm2 = c0 >= 96 ? ~0u : (1u << (c0 - 64)) - 1, lm3 = c0 <= 96 ? 0u : (1u << (c0 - 96)) - 1;
+        f.d2 = (f.d2 & lm2) | (r2 & ~lm2);
+        f.d3 = (f.d3 & lm3) | (r3 & ~lm3);
+        f.d4 = r4;
+        f.d5 = r5;
+        f.d6 = r6;
+    }
+    // the one variable shift: the span's low end, at bit 84 - 2 idx_end, goes to bit 0
+    {
+        const u32 s = AF_MIN - 2 * idx_end, ws = s >> 5, bs = s & 31;  // ws 0..2
+        const u32 t0 = ws == 0 ? f.d0 : ws == 1 ? f.d1 : f.d2, t1 = ws == 0 ? f.d1 : ws == 1 ? f.d2 : f.d3, t2 = ws == 0 ? f.d2 : ws == 1 ? f.d3 : f.d4;
+        const u32 t3 = ws == 0 ? f.d3 : ws == 1 ? f.d4 : f.d5, t4 = ws == 0 ? f.d4 : ws == 1 ? f.d5 : f.d6, t5 = ws == 0 ? f.d5 : ws == 1 ? f.d6 : 0u;
+        const u32 t6 = ws == 0 ? f.d6 : 0u;
+        f = Frame7{af_align(t1, t0, bs), af_align(t2, t1, bs), af_align(t3, t2, bs), af_align(t4, t3, bs), af_align(t5, t4, bs), af_align(t6, t5, bs), t6 >> bs};
+    }
+    return f;
+}
+// One super-k-mer's record through the anchored frame: what emit_record_at does with CLS false, from the record words on unchanged
+// (rank from the histogram atomic, bin, overflow regions, classic slot, tag and ret).
+template <bool POS>
+__device__ __forceinline__ void emit_record_anchored(const BriskParams& P, const u32* __restrict__ packed, u64 e, u32 n, bool rev, u32 idx_end, const ScanOut& out,
+                                                     u32 tag, u64 ret, unsigned long long slot) {
+    if (!out.bins && slot + 1 > out.cap) {
+        *out.overflow = 1;
+        return;
+    }
+    u32 bucket;
+    const Frame7 f = anchored_record(P, packed, e, n, rev, idx_end, &bucket);
+    u64* r;
+    if (out.bins) {
+        const u32 part = bucket >> P.shift;
+#ifdef SCAN_ATTR_NOATOMIC  // attribution builds: wrong results, timing only
+        const u32 rank = (part * 7u + (threadIdx.x & 63)) % out.bin_cap;
+#else
+        const u32 rank = (u32)atomicAdd(&out.hist[part], 1ull | ((unsigned long long)n << 32));
+#endif
+        if (rank < out.bin_cap) {
+            r = out.bins + ((u64)part * out.bin_cap + rank) * P.stride;
+            if (POS) {
+                const u64 ti = (u64)part * out.bin_cap + rank;
+                out.tag[ti] = (u32)ti;
+                out.ret[ti] = ret;
+            } else if (out.tag) out.tag[(u64)part * out.bin_cap + rank] = tag;
+        } else {
+            const u32 reg = part & (OVF_REGIONS - 1);
+            const u32 at = atomicAdd(&out.ovf_cnt[reg], 1u);
+            if (at >= out.ovf_region_cap) {
+                *out.overflow = 1;
+                return;
+            }
+            const u64 o = (u64)reg * out.ovf_region_cap + at;
+            r = out.ovf + o * P.stride;
+            if (POS) {
+                const u64 ti = ((u64)out.bin_cap << P.part_bits) + o;
+                out.tag[ti] = (u32)ti;
+                out.ret[ti] = ret;
+            } else if (out.tag) out.tag[((u64)out.bin_cap << P.part_bits) + o] = tag;
+        }
+    } else {
+        r = out.rec + slot * P.stride;
+    }
+#ifdef SCAN_ATTR_NOSTORE  // attribution builds: the record is computed and (practically) never stored
+    if ((f.d0 ^ f.d2) == 0x12345678u && f.d1 == 0x9abcdefu)
+#endif
+    {
+        r[0] = ((u64)f.d1 << 32) | f.d0;
+        if (P.nw > 1) r[1] = ((u64)f.d3 << 32) | f.d2;
+        if (P.nw > 2) r[2] = ((u64)f.d5 << 32) | f.d4;
+        if (P.nw > 3) r[3] = f.d6;
+        r[P.nw] = rec_header(bucket, n, idx_end - (n - 1) + P.suff_reduc);
+    }
+    if (!out.bins) {
+        if (out.tag) out.tag[slot] = tag;
+        if (out.ret) out.ret[slot] = ret;
+        if (out.hist) atomicAdd(&out.hist[bucket >> P.shift], 1ull | ((unsigned long long)n << 32));
+    }
+}
+
 // query_mode: stop after the first super-k-mer whose returned minimizer is 0,
 // the first one excepted (counter.cpp:296-307)
 __global__ void __launch_bounds__(SCAN_BLOCK) k_scan(BriskParams P, const u32* __restrict__ packed, const u64* __restrict__ starts,
@@ -921,10 +1066,35 @@ __device__ __forceinline__ u32 queue_records(const BriskParams& P, const u64* q_
     return mine;
 }
 // the queue's records into slots [base, base + queue_records())
-template <bool CLS, bool POS = false>  // slot_base: ChunkCtl::slot_base (POS only)
+// ANCH: the k63 m21 bodies, whose records go through the anchored frame.  Its window can stick out of the span at both ends, the
+// stream's contract (brisk_device.h: nothing before word 0, at most two words past the last nt touched) cannot: a pass of 64 entries
+// in which any lane's window would leave [0, hi_word] takes emit_record_wide as a whole, and so does what is left of the queue
+// behind it -- wave-uniform, and rare: the first super-k-mers of the stream's first read, the last ones of a block's last read.
+// hi_word: two words past the last nt of the block's reads (k_scan2)
+template <bool CLS, bool POS = false, bool ANCH = false>  // slot_base: ChunkCtl::slot_base (POS only)
 __device__ __forceinline__ void emit_queue(const BriskParams& P, const u32* __restrict__ packed, const ScanOut& out, const u64* q_ent, const u64* s_q0, const u32* s_tag,
-                                           u32 qcount, unsigned long long base, const u64* slot_base = nullptr) {
+                                           u32 qcount, unsigned long long base, const u64* slot_base = nullptr, u32 hi_word = 0) {
     const u32 lane = threadIdx.x & 63;
+    if constexpr (ANCH && !CLS) {
+        u32 e0 = 0;
+        for (; e0 < qcount; e0 += 64) {
+            const u32 e = e0 + lane;
+            const bool act = e < qcount;
+            const u64 ent = act ? q_ent[e] : 0;
+            const u32 mi = (u32)(ent >> 32), src = (mi >> 18) & 63u, n = mi & 0xff, idx_end = (mi >> 8) & 0xff;
+            const bool rev = (mi >> 16) & 1;
+            const u64 q_start = s_q0[src] + (u32)ent;
+            const u64 last = af_last_nt(q_start, n, rev, idx_end), wl = last >> 4;
+            if (__ballot(act && (wl < AF_DW || wl > hi_word))) break;
+            if (act) {
+                const u64 ret = POS ? pos_anchor(P, slot_base[s_tag[src]], q_start, n, rev, idx_end) : q_start | ((u64)((mi >> 17) & 1) << 63);
+                emit_record_anchored<POS>(P, packed, last, n, rev, idx_end, out, s_tag[src], ret, base + e);
+            }
+        }
+        // (that pass and what is left of the queue behind it: a loop of its own, so that the two builders do not share their registers)
+        for (u32 e = e0 + lane; e < qcount; e += 64) emit_queued<CLS, POS>(P, packed, out, q_ent[e], s_q0, s_tag, base + e, slot_base);
+        return;
+    }
     if (!(CLS ? P.cls_bits : 0u)) {
         for (u32 e = lane; e < qcount; e += 64) emit_queued<CLS, POS>(P, packed, out, q_ent[e], s_q0, s_tag, base + e, slot_base);
         return;
@@ -949,14 +1119,15 @@ __device__ __forceinline__ void emit_queue(const BriskParams& P, const u32* __re
 }
 
 // what is left in the waves' queues when their reads end: one slot reservation for the whole block
-template <bool CLS, bool POS = false>
+template <bool CLS, bool POS = false, bool ANCH = false>
 __device__ __forceinline__ void scan_final_flush(const BriskParams& P, const u32* __restrict__ packed, const ScanOut& out, const u64* q_ent, const u64* s_q0,
-                                                 const u32* s_tag, u32 qcount, u32* s_wcnt, unsigned long long* s_wbase, const u64* slot_base = nullptr) {
-    const u32 lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+                                                 const u32* s_tag, u32 qcount, u32* s_wcnt, unsigned long long* s_wbase, const u64* slot_base = nullptr, u32 hi_word = 0) {
+    const u32 lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const u32 wid = ANCH ? (u32)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;  // (as in k_scan2)
     const u32 n_mine = queue_records<CLS>(P, q_ent, qcount);
     if (out.bins) {  // binned records need no slots: no reservation, no barrier
         if (lane == 0 && n_mine) atomicAdd(out.n_rec, (unsigned long long)n_mine);
-        emit_queue<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, qcount, 0, slot_base);
+        emit_queue<CLS, POS, ANCH>(P, packed, out, q_ent, s_q0, s_tag, qcount, 0, slot_base, hi_word);
         return;
     }
     if (lane == 0) s_wcnt[wid] = n_mine;
@@ -969,15 +1140,21 @@ __device__ __forceinline__ void scan_final_flush(const BriskParams& P, const u32
     __syncthreads();
     unsigned long long base = *s_wbase;
     for (u32 i = 0; i < wid; i++) base += s_wcnt[i];
-    emit_queue<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, qcount, base, slot_base);
+    emit_queue<CLS, POS, ANCH>(P, packed, out, q_ent, s_q0, s_tag, qcount, base, slot_base, hi_word);
 }
 
 // minimum of x over the lane's 16-lane row, in every lane of the row (DPP row rotations: one instruction per step)
+// (The value a disabled lane would keep is ~0u, the minimum's identity -- a rotation with every row and bank enabled disables none --:
+// that lets the DPP combiner fold the move into the minimum, v_min_u32_dpp, where the lane's own value as `old` left v_mov, v_mov_dpp,
+// v_min_u32 per step.  ROW_MIN_FOLD 0: the earlier form (A/B))
+#ifndef ROW_MIN_FOLD
+#define ROW_MIN_FOLD 1
+#endif
 __device__ __forceinline__ u32 row_min_u32(u32 x) {
-#define ROW_MIN_STEP(CTRL)                                                                      \
-    {                                                                                           \
-        const u32 y_ = (u32)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, 0xf, 0xf, false); \
-        x = y_ < x ? y_ : x;                                                                    \
+#define ROW_MIN_STEP(CTRL)                                                                                               \
+    {                                                                                                                    \
+        const u32 y_ = (u32)__builtin_amdgcn_update_dpp(ROW_MIN_FOLD ? -1 : (int)x, (int)x, CTRL, 0xf, 0xf, false);      \
+        x = y_ < x ? y_ : x;                                                                                             \
     }
     ROW_MIN_STEP(0x128)  // row_ror:8
     ROW_MIN_STEP(0x124)  // row_ror:4
@@ -1065,8 +1242,11 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
                                                 u64 n_reads, const double* __restrict__ g_tabs, ScanOut out, ChunkCtl cc) {
     constexpr bool VR = MODE == 2 || MODE == 4, query_mode = MODE == 1, POS = MODE >= 3;
     constexpr bool CLS = MM < 12;  // minimizer_idx classes in the routing id exist only where 2m < 24 (brisk_hip_create)
+    constexpr bool ANCH = KK == AF_K && MM == AF_M;  // records through the anchored frame (anchored_record)
     extern __shared__ double smem_dyn[];
-    const u32 tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    // (ANCH: the wave's number in a scalar register -- the second builder's loop takes the vector register it and the queue's base held)
+    const u32 wid = ANCH ? (u32)__builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const u32 n_tab = MM ? 128 + cls_base(MM ? MM : 1, cls_nch(MM ? MM : 1)) : cfg.n_tab;
     double* smem_d = smem_dyn;         // coef[128], the chunk tables ...
     double* smem_q = smem_dyn + n_tab; // ... and behind them what the waves write
@@ -1119,7 +1299,21 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
     }
     s_q0[lane] = q0;
     s_tag[lane] = tagval;
+    // the last stream word the block may read: two past the last nt of its reads (ANCH; emit_queue).  Through s_wcnt, which is
+    // free until the final flush; a word index beyond 32 bits is cut down, which only sends more passes to the other builder
+    u32 hi_word = 0;
+    if constexpr (ANCH) {
+        const u64 hw = len >= k ? ((q0 + len - 1) >> 4) + 2 : 0;
+        hi_word = hw > 0xffffffffull ? 0xffffffffu : (u32)hw;
+        for (int o = 32; o > 0; o >>= 1) hi_word = max(hi_word, (u32)__shfl_xor(hi_word, o, 64));
+        if (lane == 0) s_wcnt[wid] = hi_word;
+    }
     __syncthreads();
+    if constexpr (ANCH) {
+        for (u32 i = 0; i < (blockDim.x >> 6); i++) hi_word = max(hi_word, s_wcnt[i]);
+        hi_word = __builtin_amdgcn_readfirstlane(hi_word);
+        __syncthreads();  // (s_wcnt is written again at the final flush, which a wave without reads reaches at once)
+    }
     const bool live = len >= k;  // counter.cpp:233-235
     u32 nk = live ? (u32)(len - k + 1) : 0;
     u32 max_nk = nk;
@@ -1128,7 +1322,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
         max_nk = y > max_nk ? y : max_nk;
     }
     if (max_nk == 0) {  // nothing to scan in this wave; it still takes part in the block's final reservation
-        scan_final_flush<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, 0, s_wcnt, s_wbase, cc.slot_base);
+        scan_final_flush<CLS, POS, ANCH>(P, packed, out, q_ent, s_q0, s_tag, 0, s_wcnt, s_wbase, cc.slot_base, hi_word);
         return;
     }
     const u64 KEY0 = order_key_fast<NCH, MM>(0, m, M, cfg, s_tabs, s_coef);
@@ -1445,7 +1639,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
                 if (lane == 0) base = atomicAdd(out.n_rec, (unsigned long long)n_out);
                 base = read_lane_u64(base, 0);
             }
-            emit_queue<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, qcount, base, cc.slot_base);
+            emit_queue<CLS, POS, ANCH>(P, packed, out, q_ent, s_q0, s_tag, qcount, base, cc.slot_base, hi_word);
 #endif
             qcount = 0;
         }
@@ -1471,5 +1665,5 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
 #ifdef SCAN_ATTR_NOEMIT
     qcount = 0;
 #endif
-    scan_final_flush<CLS, POS>(P, packed, out, q_ent, s_q0, s_tag, qcount, s_wcnt, s_wbase, cc.slot_base);
+    scan_final_flush<CLS, POS, ANCH>(P, packed, out, q_ent, s_q0, s_tag, qcount, s_wcnt, s_wbase, cc.slot_base, hi_word);
 }
