@@ -11,7 +11,7 @@
 //                    --joint): a base whose quality is below Q (0..93, default 0: no cut) is cut like an N, on the device; the quality
 //                    characters are Phred+33 (default) or Phred+64.  One line on stderr per FASTQ file carries the intake's stats.
 //                    Exit status 2 when no input is FASTQ.  --profile and --extract read the input again as FASTA: with a FASTQ main
-//                    input they exit 2
+//                    input they exit 2 (--extract takes one with --paired, below)
 //   --histo FILE     the count spectrum (brisk_hip_count_spectrum): 256 lines "count<TAB>entries", empty bins included
 //   --saturate       counts stop at 255 instead of wrapping (brisk_hip_options.count_mode = BRISK_HIP_COUNTS_SATURATE): the index, and the
 //                    second index of --merge / --subtract / --intersect FILE, are created in that mode; --load FILE (or a set operation's
@@ -39,6 +39,18 @@
 //                    ">read_index start len".  trim (the default): the stretch covered by the first longest run of k-mers with count
 //                    >= N (--solid, default 2); median:LO:HI: the whole read when LO <= its median count <= HI; present:LO:HI: when
 //                    LO <= the permille of its k-mers that are in the index <= HI.  --min-len L: at least L nucleotides (default k)
+//   --paired [--mate FILE] [--pair-mode each|all|any]
+//                    the input holds paired reads, one record a read: interleaved (records 2p and 2p + 1 are the mates of pair p), or,
+//                    with --mate FILE, record i of the input and record i of FILE (of the same kind, FASTA or FASTQ) are a pair.  A
+//                    record count that is odd, or differs between the two files, exits 2.  Pairing never changes the index: the reads
+//                    are counted exactly as unpaired ones (FILE after the input).  With --extract PREFIX three files are written,
+//                    PREFIX.1.fa and PREFIX.2.fa (the mates of intact pairs, line by line in step) and PREFIX.s.fa (the surviving mate
+//                    of a broken pair), headers ">pair_index/1 start len" and ">pair_index/2 start len", start relative to the input
+//                    read; the pair counts go to stderr on one line.  --pair-mode (default each): each -- mates are judged alone; all
+//                    -- a pair stays only when both mates do; any -- when either mate passes the rule both are kept whole.  FASTA
+//                    records must be clean (ACGTacgt only, else exit 2, like the counts before anything is counted) and go through brisk_hip_trim_pairs_reads; FASTQ records go
+//                    through brisk_hip_clean_pairs_reads with --min-qual / --qual-base: the first longest clean fragment of a read,
+//                    cut again by the rule -- the one case in which --extract takes a FASTQ input
 // Prints nb_kmers / nb_buckets / sum of counts (of the entries dumped); optionally dumps "KMER idx count" lines (dump.txt, "-" for none) and
 // writes the index as a KFF file (a 7th argument: BriskWriter in --facade mode, brisk_write_kff in --bulk mode).
 #include <algorithm>
@@ -49,6 +61,7 @@
 #include <atomic>
 #include <chrono>
 #include <iostream>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -112,6 +125,177 @@ static int count_fastq(brisk_hip_index* h, const char* path, const brisk_hip_int
     }
     std::cerr << "fastq " << path << ": n_reads=" << total.n_reads << " n_reads_kept=" << total.n_reads_kept << " n_fragments=" << total.n_fragments << " n_bases_in=" << total.n_bases_in
               << " n_nts=" << total.n_nts << " n_cut_base=" << total.n_cut_base << " n_cut_qual=" << total.n_cut_qual << " n_short=" << total.n_short << std::endl;
+    return 0;
+}
+
+// --paired: a file read record by record, one record a read, nothing cleaned.  FASTA: the lines of a record concatenated;
+// FASTQ: brisk_fastq.hpp's strict four-line records.
+class RecordReader {
+  public:
+    RecordReader(const char* path, bool fastq) : fastq_(fastq) {
+        if (fastq) {
+            fq_.reset(new FastqReader(path));
+        } else {
+            gz_ = gzopen(path, "rb");
+            if (!gz_) throw std::runtime_error(std::string("cannot open ") + path);
+            gzbuffer(gz_, 1 << 20);
+            line_.resize(1 << 16);
+        }
+    }
+    ~RecordReader() {
+        if (gz_) gzclose(gz_);
+    }
+    RecordReader(const RecordReader&) = delete;
+    RecordReader& operator=(const RecordReader&) = delete;
+    // the next record's bases appended to `bases` (its qualities to `quals`, FASTQ only); false at the end of the file
+    bool next(std::string& bases, std::string& quals) {
+        if (fastq_) {
+            one_.clear();
+            if (!fq_->fill(one_, 0)) return false;
+            bases += one_.bases;
+            quals += one_.quals;
+            return true;
+        }
+        if (!have_header_ && !skip_to_header()) return false;
+        have_header_ = false;
+        for (;;) {  // sequence lines up to the next header
+            bool whole = false;
+            size_t n = 0;
+            if (!read_piece(&n, &whole)) return true;
+            if (at_line_start_ && n && line_[0] == '>') {
+                have_header_ = true;
+                finish_line(whole);
+                return true;
+            }
+            bases.append(line_.data(), n);
+            at_line_start_ = whole;
+        }
+    }
+
+  private:
+    // up to a buffer of the current line, without '\n' and '\r'; *whole: the line ended here.  false at the end of the file
+    bool read_piece(size_t* n, bool* whole) {
+        if (!gzgets(gz_, &line_[0], (int)line_.size())) return false;
+        size_t len = strlen(line_.data());
+        *whole = len && line_[len - 1] == '\n';
+        while (len && (line_[len - 1] == '\n' || line_[len - 1] == '\r')) len--;
+        *n = len;
+        return true;
+    }
+    void finish_line(bool whole) {  // the rest of a header line
+        size_t n = 0;
+        while (!whole && read_piece(&n, &whole)) {
+        }
+        at_line_start_ = true;
+    }
+    bool skip_to_header() {  // the file's first record
+        for (;;) {
+            bool whole = false;
+            size_t n = 0;
+            if (!read_piece(&n, &whole)) return false;
+            const bool header = at_line_start_ && n && line_[0] == '>';
+            at_line_start_ = whole;
+            if (header) {
+                finish_line(whole);
+                return true;
+            }
+        }
+    }
+    bool fastq_;
+    std::unique_ptr<FastqReader> fq_;
+    FastqBatch one_;
+    gzFile gz_ = nullptr;
+    std::string line_;
+    bool have_header_ = false, at_line_start_ = true;
+};
+
+// the records of a file; *dirty (FASTA: trim_pairs takes clean reads): the first record that holds a byte that is no base, ~0 none
+static uint64_t count_records(const char* path, bool fastq, uint64_t* dirty) {
+    RecordReader rd(path, fastq);
+    std::string bases, quals;
+    uint64_t n = 0;
+    *dirty = ~0ull;
+    for (; rd.next(bases, quals); n++) {
+        if (!fastq && *dirty == ~0ull && (bases.find_first_not_of("ACGTacgt") != std::string::npos)) *dirty = n;
+        bases.clear();
+        quals.clear();
+    }
+    return n;
+}
+
+// --paired --extract PREFIX: the reads again, pair by pair, against the final index; intact pairs to PREFIX.1.fa / PREFIX.2.fa, singles
+// to PREFIX.s.fa.  0 fine, else the exit status.
+static int extract_paired(brisk_hip_index* h, const char* main_file, const char* mate_file, bool fastq, const char* prefix, const brisk_hip_select_rule& rule, uint32_t solid,
+                          const brisk_hip_intake_rule& intake, uint32_t pair_mode, size_t batch_bases) {
+    RecordReader rd1(main_file, fastq);
+    std::unique_ptr<RecordReader> rd2(mate_file ? new RecordReader(mate_file, fastq) : nullptr);
+    const std::string names[3] = {std::string(prefix) + ".1.fa", std::string(prefix) + ".2.fa", std::string(prefix) + ".s.fa"};
+    std::ofstream out[3];
+    for (int i = 0; i < 3; i++) out[i].open(names[i]);
+    brisk_hip_pair_counts total{};
+    brisk_hip_intake_stats stats{};
+    std::string bases, quals;
+    std::vector<uint64_t> offs;
+    std::vector<brisk_hip_read_interval> ivs;
+    uint64_t pair_index = 0;
+    for (bool more = true; more;) {
+        bases.clear();
+        quals.clear();
+        offs.assign(1, 0);
+        while (bases.size() < batch_bases) {  // whole pairs
+            if (!rd1.next(bases, quals)) {
+                more = false;
+                break;
+            }
+            offs.push_back(bases.size());
+            if (!(rd2 ? rd2->next(bases, quals) : rd1.next(bases, quals))) {
+                std::cerr << "--paired: the input ends inside a pair" << std::endl;
+                return 2;
+            }
+            offs.push_back(bases.size());
+        }
+        const uint64_t n = offs.size() - 1;
+        if (!n) break;
+        ivs.resize(n);
+        brisk_hip_pair_counts pc{};
+        int rc;
+        if (fastq) {
+            brisk_hip_intake_stats st{};
+            rc = brisk_hip_clean_pairs_reads(h, bases.data(), intake.min_qual ? quals.data() : nullptr, offs.data(), n, &intake, &rule, solid, pair_mode, ivs.data(), &pc, &st);
+            for (size_t i = 0; i < sizeof st / 8; i++) ((uint64_t*)&stats)[i] += ((const uint64_t*)&st)[i];
+        } else {  // (the records are clean: main() has looked at every one before anything was counted)
+            rc = brisk_hip_trim_pairs_reads(h, bases.data(), offs.data(), n, solid, &rule, pair_mode, ivs.data(), &pc);
+        }
+        if (rc != BRISK_HIP_OK) {
+            std::cerr << "--extract: " << brisk_hip_last_error(h) << std::endl;
+            return 1;
+        }
+        for (size_t i = 0; i < sizeof pc / 8; i++) ((uint64_t*)&total)[i] += ((const uint64_t*)&pc)[i];
+        for (uint64_t p = 0; p < n / 2; p++, pair_index++) {
+            const bool both = ivs[2 * p].len && ivs[2 * p + 1].len;
+            for (int mate = 0; mate < 2; mate++) {
+                const brisk_hip_read_interval v = ivs[2 * p + mate];
+                if (!v.len) continue;
+                std::ofstream& o = out[both ? mate : 2];
+                o << ">" << pair_index << "/" << (mate + 1) << " " << v.start << " " << v.len << "\n";
+                o.write(bases.data() + offs[2 * p + mate] + v.start, v.len);
+                o << "\n";
+            }
+        }
+    }
+    for (int i = 0; i < 3; i++) {
+        out[i].close();
+        if (!out[i]) {
+            std::cerr << "--extract " << names[i] << ": write failed" << std::endl;
+            return 1;
+        }
+    }
+    if (fastq)
+        std::cerr << "clean " << main_file << ": n_reads=" << stats.n_reads << " n_reads_kept=" << stats.n_reads_kept << " n_fragments=" << stats.n_fragments << " n_bases_in=" << stats.n_bases_in
+                  << " n_nts=" << stats.n_nts << " n_cut_base=" << stats.n_cut_base << " n_cut_qual=" << stats.n_cut_qual << " n_short=" << stats.n_short << std::endl;
+    std::cerr << "pairs " << prefix << ": n_pairs_in=" << total.n_pairs_in << " n_pairs_kept=" << total.n_pairs_kept << " n_single_first=" << total.n_single_first
+              << " n_single_second=" << total.n_single_second << " n_pairs_dropped=" << total.n_pairs_dropped << " n_nts_pairs=" << total.n_nts_pairs << " n_nts_singles=" << total.n_nts_singles
+              << std::endl;
     return 0;
 }
 
@@ -224,6 +408,9 @@ int main(int argc_in, char** argv_in) {
     bool have_solid = false;
     bool have_range = false;
     bool saturate = false;
+    bool paired = false;
+    const char* mate_file = nullptr;
+    const char* pair_mode_text = nullptr;
     const char* const setop_names[3] = {"--merge", "--subtract", "--intersect"};  // in the order they are applied
     const char* setop_file[3] = {nullptr, nullptr, nullptr};
     const char* joint_file = nullptr;
@@ -233,8 +420,9 @@ int main(int argc_in, char** argv_in) {
     static const char* const usage =
         "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] "
         "[--subtract FILE] [--intersect FILE] [--filter-joint FILE --window SLO:SHI:OLO:OHI[:absent]] [--joint FILE --joint-histo OUT] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]] [--min-qual Q] [--qual-base 33|64] "
-        "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]]; FASTA \"-\": no reads; a FILE may be a snapshot; an input that starts with '@' is FASTQ)\n"
+        "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]] [--paired [--mate FILE] [--pair-mode each|all|any]]; FASTA \"-\": no reads; a FILE may be a snapshot; an input that starts with '@' is FASTQ)\n"
         "  --min-qual Q   FASTQ input: a base of quality below Q (0..93) is cut like an N, on the device; --qual-base 33|64 (default 33)\n"
+        "  --paired   one record a read, interleaved or zipped with --mate FILE; --extract PREFIX then writes PREFIX.1.fa PREFIX.2.fa PREFIX.s.fa (FASTQ input allowed)\n"
         "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+";
     for (int i = 0; i < argc_in; i++) {
         if (i > 0 && (!strcmp(argv_in[i], "--help") || !strcmp(argv_in[i], "-h"))) {
@@ -245,13 +433,18 @@ int main(int argc_in, char** argv_in) {
             saturate = true;
             continue;
         }
+        if (i > 0 && !strcmp(argv_in[i], "--paired")) {
+            paired = true;
+            continue;
+        }
         int setop = -1;
         for (int q = 0; q < 3; q++)
             if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
         const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count") ||
                                     !strcmp(argv_in[i], "--profile") || !strcmp(argv_in[i], "--solid") || !strcmp(argv_in[i], "--extract") || !strcmp(argv_in[i], "--rule") ||
                                     !strcmp(argv_in[i], "--min-len") || !strcmp(argv_in[i], "--joint") || !strcmp(argv_in[i], "--joint-histo") || !strcmp(argv_in[i], "--filter-joint") ||
-                                    !strcmp(argv_in[i], "--window") || !strcmp(argv_in[i], "--min-qual") || !strcmp(argv_in[i], "--qual-base"));
+                                    !strcmp(argv_in[i], "--window") || !strcmp(argv_in[i], "--min-qual") || !strcmp(argv_in[i], "--qual-base") || !strcmp(argv_in[i], "--mate") ||
+                                    !strcmp(argv_in[i], "--pair-mode"));
         if (!named) {
             args.push_back(argv_in[i]);
             continue;
@@ -271,6 +464,8 @@ int main(int argc_in, char** argv_in) {
         else if (!strcmp(opt, "--joint-histo")) joint_histo = argv_in[i];
         else if (!strcmp(opt, "--filter-joint")) filter_joint_file = argv_in[i];
         else if (!strcmp(opt, "--window")) window_text = argv_in[i];
+        else if (!strcmp(opt, "--mate")) mate_file = argv_in[i];
+        else if (!strcmp(opt, "--pair-mode")) pair_mode_text = argv_in[i];
         else if (!strcmp(opt, "--min-qual") || !strcmp(opt, "--qual-base")) {
             char* end = nullptr;
             const long v = strtol(argv_in[i], &end, 10);
@@ -319,8 +514,8 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || extract_file || rule_text || min_len || have_qual) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule, --min-len, --min-qual and --qual-base work on the device "
+    if ((histo || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || extract_file || rule_text || min_len || have_qual || paired || mate_file || pair_mode_text) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule, --min-len, --min-qual, --qual-base, --paired, --mate and --pair-mode work on the device "
                      "index: --bulk only" << std::endl;
         return 2;
     }
@@ -331,6 +526,20 @@ int main(int argc_in, char** argv_in) {
     if ((rule_text || min_len) && !extract_file) {
         std::cerr << "--rule and --min-len belong to --extract FILE" << std::endl;
         return 2;
+    }
+    if ((mate_file || pair_mode_text) && !paired) {
+        std::cerr << "--mate FILE and --pair-mode belong to --paired" << std::endl;
+        return 2;
+    }
+    uint32_t pair_mode = BRISK_HIP_PAIR_EACH;
+    if (pair_mode_text) {
+        if (!strcmp(pair_mode_text, "each")) pair_mode = BRISK_HIP_PAIR_EACH;
+        else if (!strcmp(pair_mode_text, "all")) pair_mode = BRISK_HIP_PAIR_ALL;
+        else if (!strcmp(pair_mode_text, "any")) pair_mode = BRISK_HIP_PAIR_ANY;
+        else {
+            std::cerr << "--pair-mode: each, all or any, got " << pair_mode_text << std::endl;
+            return 2;
+        }
     }
     if (!joint_file != !joint_histo) {
         std::cerr << "--joint FILE and --joint-histo OUT come together" << std::endl;
@@ -407,9 +616,37 @@ int main(int argc_in, char** argv_in) {
             return 2;
         }
     }
-    if (fastq_main && (profile_file || extract_file)) {
+    if (fastq_main && (profile_file || (extract_file && !paired))) {
         std::cerr << (profile_file ? "--profile" : "--extract") << " reads the input again as FASTA: not with a FASTQ input" << std::endl;
         return 2;
+    }
+    if (paired) {  // whole pairs, before anything is counted
+        if (!bulk || !strcmp(argv[2], "-") || is_snapshot(argv[2])) {
+            std::cerr << "--paired needs reads: a FASTA or FASTQ input" << std::endl;
+            return 2;
+        }
+        try {
+            if (mate_file && (is_snapshot(mate_file) || is_fastq(mate_file) != fastq_main)) {
+                std::cerr << "--mate " << mate_file << ": the two files of a paired input are both FASTA or both FASTQ" << std::endl;
+                return 2;
+            }
+            uint64_t dirty1 = ~0ull, dirty2 = ~0ull;
+            const uint64_t n1 = count_records(argv[2], fastq_main, &dirty1), n2 = mate_file ? count_records(mate_file, fastq_main, &dirty2) : 0;
+            if (mate_file ? n1 != n2 : n1 % 2 != 0) {
+                if (mate_file) std::cerr << "--paired: " << argv[2] << " holds " << n1 << " reads, --mate " << mate_file << " " << n2 << std::endl;
+                else std::cerr << "--paired: " << argv[2] << " holds " << n1 << " reads, an odd number: an interleaved file holds whole pairs" << std::endl;
+                return 2;
+            }
+            if (dirty1 != ~0ull || dirty2 != ~0ull) {  // (FASTA only; in two files the earlier pair is named)
+                const bool second = mate_file ? dirty2 < dirty1 : (dirty1 & 1) != 0;
+                const uint64_t pair = mate_file ? std::min(dirty1, dirty2) : dirty1 / 2;
+                std::cerr << "--paired: mate " << (second ? 2 : 1) << " of pair " << pair << " holds a byte that is no base: paired FASTA records must be clean (FASTQ input is cut on the device)" << std::endl;
+                return 2;
+            }
+        } catch (const std::exception& e) {
+            std::cerr << "--paired: " << e.what() << std::endl;
+            return 1;
+        }
     }
     if (mixed) return run_mixed(argv[2], k, m, b, params.dede->coef(), batch_bases);
     std::vector<std::string> lines;
@@ -533,6 +770,21 @@ int main(int argc_in, char** argv_in) {
                     std::cout << "}}" << std::endl;
                 }
             }
+            if (mate_file) {  // the mates' file is counted like the input: pairing never changes the index
+                if (fastq_main) {
+                    if (count_fastq(h, mate_file, intake, batch_bases)) return 1;
+                } else {
+                    FastaBatcher batches(mate_file, batch_bases);
+                    FastaBatch bt;
+                    while (batches.next(bt))
+                        if (brisk_hip_insert_reads(h, bt.flat.data(), bt.offs.data(), bt.size()) != BRISK_HIP_OK) {
+                            std::cerr << "--mate: " << brisk_hip_last_error(h) << std::endl;
+                            return 1;
+                        }
+                }
+                brisk_hip_sync(h);
+                brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
+            }
             // FILE of a set operation counted (or, a snapshot, loaded) into a second index of the same parameters; 0 or the exit status
             auto second_index = [&](const char* opt, const char* file, brisk_hip_index** out) -> int {
                 brisk_hip_index* other = nullptr;
@@ -650,7 +902,9 @@ int main(int argc_in, char** argv_in) {
                 }
                 std::cerr << "profile " << profile_file << ": " << read_index << " reads, solid >= " << solid << std::endl;
             }
-            if (extract_file) {  // the reads of the input again, against the final index: what the rule keeps of them, as FASTA
+            if (extract_file && paired) {
+                if (int erc = extract_paired(h, argv[2], mate_file, fastq_main, extract_file, rule, (uint32_t)solid, intake, pair_mode, batch_bases)) return erc;
+            } else if (extract_file) {  // the reads of the input again, against the final index: what the rule keeps of them, as FASTA
                 std::ofstream out(extract_file);
                 uint64_t read_index = 0, kept = 0, kept_nts = 0;
                 if (!no_reads) {

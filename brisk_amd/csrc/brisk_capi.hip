@@ -143,6 +143,8 @@ struct brisk_hip_index {
     DevBuf ext_iv, ext_tmp, ext_src;     // brisk_hip_extract_packed / _trim_*: a call's intervals; flags and block sums; the kept reads' source positions
     DevBuf ink_mask, ink_tmp, ink_tab;   // brisk_hip_intake_*: a lane's valid and read-start bits; flags, block carries and sums; fragment rows, starts, source positions
     DevBuf ink_raw, ink_offs, ink_packed;  // brisk_hip_intake_reads / _insert_raw_reads: a piece's bytes (bases, then qualities); its read table; its packed stream
+    DevBuf pair_tab, pair_iv, pair_raw, pair_fs;  // brisk_hip_*_pairs_*: counters, flags and the two masked tables; iv1 / whole and each; the packed raw stream and its
+                                                  // read table; the one-fragment-per-read stream with its starts and index
     u64 intake_piece = 1ull << 28;       // BRISK_INTAKE_PIECE (bytes of bases): the piece size of the host intake calls
     u32* d_ovf_cnt = nullptr;              // OVF_REGIONS counters of the binned scan's overflow area
     std::vector<u64> owner_cut;            // sharded index: owner o holds partitions [owner_cut[o], owner_cut[o + 1]) (n_owners + 1 entries)
@@ -1761,7 +1763,7 @@ void free_all(brisk_hip_index* h) {
     hipStreamSynchronize(h->stream);  // nothing of ours may be in flight when the arena is unmapped
     auto fr = [](void* p) { if (p) hipFree(p); };
     for (DevBuf* b : {&h->huge, &h->left, &h->pend, &h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp, &h->enum_out,
-                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed})
+                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed, &h->pair_tab, &h->pair_iv, &h->pair_raw, &h->pair_fs})
         fr(b->p);
     fr(h->d_coef);
     fr(h->d_tabs);
@@ -2686,13 +2688,15 @@ BRISK_API int brisk_hip_intake_ascii(brisk_hip_index* h, const char* d_bases, co
 }
 
 // host reads -> the device, as they are, in pieces of whole reads (at least one) of about h->intake_piece bytes; body(r0, nr, d_bases,
-// d_quals, d_offsets): the piece's table holds the caller's offsets, and the two pointers are displaced so that those index them
+// d_quals, d_offsets): the piece's table holds the caller's offsets, and the two pointers are displaced so that those index them;
+// group: a piece holds a multiple of so many reads
 extern "C++" template <class F>
-static int for_each_raw_piece(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, F&& body) {
+static int for_each_raw_piece(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, F&& body, u64 group = 1) {
     for (u64 r0 = 0; r0 < n_reads;) {
         const u64 r_hi = std::min<u64>(n_reads, r0 + (1ull << 26));
         u64 r1 = (u64)(std::upper_bound(offsets + r0, offsets + r_hi + 1, offsets[r0] + h->intake_piece) - offsets) - 1;
-        if (r1 <= r0) r1 = r0 + 1;
+        if (group > 1) r1 = r0 + (r1 - r0) / group * group;  // (the pairs calls: whole pairs, n_reads a multiple of group)
+        if (r1 <= r0) r1 = std::min<u64>(n_reads, r0 + group);
         const u64 nb = offsets[r1] - offsets[r0], nr = r1 - r0, pad = (nb + 15) & ~15ull;
         int rc;
         if ((rc = ensure(h, h->ink_raw, (quals ? 2 : 1) * pad + 16))) return rc;
@@ -2778,6 +2782,423 @@ BRISK_API int brisk_hip_insert_raw_reads(brisk_hip_index* h, const char* bases, 
     });
     if (stats) *stats = sum;
     return rc;
+}
+
+// ---- paired-end reads: the pair decision over intervals, pairs and singles as two streams (no reference counterpart; khmer's
+// extract-paired-reads and Trimmomatic's paired mode are the usual tools; kernels: brisk_pairs.hip).  Beside read extraction in
+// purpose; behind the intake calls because the clean_pairs calls are built from both. ----
+static_assert(sizeof(brisk_hip_pair_counts) == 64 && offsetof(brisk_hip_pair_counts, n_nts_pairs) == 40, "include/brisk_hip.h: eight 64-bit counters");
+static_assert(BRISK_HIP_PAIR_EACH == PAIR_EACH && BRISK_HIP_PAIR_ALL == PAIR_ALL && BRISK_HIP_PAIR_ANY == PAIR_ANY, "the kernel's modes are the header's");
+
+// h->pair_tab: [PAIR_CTR_ROWS rows of 64 bytes: k_pair_split's six counters, summed here][64 bytes: two flags][the intervals of intact pairs,
+// n_reads][those of singles, n_reads]
+constexpr size_t kPairCtrBytes = (size_t)PAIR_CTR_ROWS * 64, kPairHeadBytes = kPairCtrBytes + 64;
+static unsigned long long* pair_flags(brisk_hip_index* h) { return (unsigned long long*)((char*)h->pair_tab.p + kPairCtrBytes); }
+
+static int check_pairs(brisk_hip_index* h, u64 n_reads, u32 pair_mode, const char* who) {
+    if (n_reads & 1) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": n_reads " + std::to_string(n_reads) + " is odd (an interleaved stream holds whole pairs)");
+    if (pair_mode > BRISK_HIP_PAIR_ANY) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": unknown pair_mode " + std::to_string(pair_mode));
+    if (n_reads / 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": more pairs than one launch covers");
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held.  The table is checked first (a host synchronisation): a refused call writes nothing.
+static int fragment_intervals_impl(brisk_hip_index* h, const IntakeFragment* d_frags, u64 n_frags, u64 n_reads, ReadInterval* d_iv) {
+    int rc;
+    if (n_reads > 0x7fffffffull * 256 || n_frags > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "fragment_intervals: more rows than one launch covers");
+    if (n_frags) {
+        if ((rc = ensure(h, h->pair_tab, kPairHeadBytes))) return rc;
+        unsigned long long* d_flags = pair_flags(h);
+        HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 8, h->stream));
+        hipLaunchKernelGGL(k_fragment_check, dim3(nblocks(n_frags, 256)), dim3(256), 0, h->stream, d_frags, n_frags, n_reads, d_flags);
+        if ((rc = launch_check(h, "k_fragment_check"))) return rc;
+        u64 bad = 0;
+        HIPCHK(h, hipMemcpyAsync(&bad, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (bad != ~0ull)
+            return fail(h, BRISK_HIP_EINVAL, "fragment_intervals: row " + std::to_string(bad) + " of the fragment table names a read >= n_reads or stands before the row ahead of it (by read, then by position)");
+    }
+    if (!n_reads) return BRISK_HIP_OK;
+    hipLaunchKernelGGL(k_fragment_intervals, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_frags, n_frags, n_reads, d_iv);
+    return launch_check(h, "k_fragment_intervals");
+}
+
+BRISK_API int brisk_hip_fragment_intervals(brisk_hip_index* h, const brisk_hip_fragment* d_frags, uint64_t n_frags, uint64_t n_reads, brisk_hip_read_interval* d_intervals) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if ((n_frags && !d_frags) || (n_reads && !d_intervals)) return fail(h, BRISK_HIP_EINVAL, "fragment_intervals: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int rc = fragment_intervals_impl(h, (const IntakeFragment*)d_frags, n_frags, n_reads, (ReadInterval*)d_intervals)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// the handle's lock is held; n_reads and the mode are checked
+static int pair_intervals_impl(brisk_hip_index* h, const ReadInterval* d_each, const ReadInterval* d_whole, u64 n_reads, u32 pair_mode, ReadInterval* d_out) {
+    if (!n_reads) return BRISK_HIP_OK;
+    hipLaunchKernelGGL(k_pair_intervals, dim3(nblocks(n_reads / 2, 256)), dim3(256), 0, h->stream, d_each, d_whole, n_reads / 2, pair_mode, d_out);
+    return launch_check(h, "k_pair_intervals");
+}
+
+BRISK_API int brisk_hip_pair_intervals(brisk_hip_index* h, const brisk_hip_read_interval* d_each, const brisk_hip_read_interval* d_whole, uint64_t n_reads, uint32_t pair_mode,
+                                       brisk_hip_read_interval* d_out) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int crc = check_pairs(h, n_reads, pair_mode, "pair_intervals")) return crc;
+    if (pair_mode == BRISK_HIP_PAIR_ANY && !d_whole) return fail(h, BRISK_HIP_EINVAL, "pair_intervals: BRISK_HIP_PAIR_ANY needs d_whole");
+    if (n_reads && (!d_each || !d_out)) return fail(h, BRISK_HIP_EINVAL, "pair_intervals: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int rc = pair_intervals_impl(h, (const ReadInterval*)d_each, (const ReadInterval*)d_whole, n_reads, pair_mode, (ReadInterval*)d_out)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held.  The inputs are checked first (a host synchronisation): a refused call writes nothing.
+static int compose_impl(brisk_hip_index* h, const ReadInterval* d_outer, u64 n_reads, const ReadInterval* d_inner, const u64* d_index, u64 n_kept, ReadInterval* d_out) {
+    int rc;
+    if (n_reads > 0x7fffffffull * 256 || n_kept > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "compose_intervals: more rows than one launch covers");
+    if (n_kept) {
+        if ((rc = ensure(h, h->pair_tab, kPairHeadBytes))) return rc;
+        unsigned long long* d_flags = pair_flags(h);
+        HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 16, h->stream));
+        hipLaunchKernelGGL(k_compose_check, dim3(nblocks(n_kept, 256)), dim3(256), 0, h->stream, d_outer, n_reads, d_inner, d_index, n_kept, d_flags);
+        if ((rc = launch_check(h, "k_compose_check"))) return rc;
+        u64 got[2] = {0, 0};
+        HIPCHK(h, hipMemcpyAsync(got, d_flags, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (got[1] != ~0ull) return fail(h, BRISK_HIP_EINVAL, "compose_intervals: d_index does not ascend at row " + std::to_string(got[1]));  // (first: the rows of an index out of order pair the wrong intervals)
+        if (got[0] != ~0ull)
+            return fail(h, BRISK_HIP_EINVAL, "compose_intervals: row " + std::to_string(got[0]) + ": the inner interval leaves the outer one (start + len > outer.len), or d_index names a read >= n_reads");
+    }
+    if (!n_reads) return BRISK_HIP_OK;
+    hipLaunchKernelGGL(k_compose_intervals, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_outer, n_reads, d_inner, d_index, n_kept, d_out);
+    return launch_check(h, "k_compose_intervals");
+}
+
+BRISK_API int brisk_hip_compose_intervals(brisk_hip_index* h, const brisk_hip_read_interval* d_outer, uint64_t n_reads, const brisk_hip_read_interval* d_inner, const uint64_t* d_index,
+                                          uint64_t n_kept, brisk_hip_read_interval* d_out) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if ((n_reads && !d_out) || (n_kept && (!d_outer || !d_inner || !d_index))) return fail(h, BRISK_HIP_EINVAL, "compose_intervals: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int rc = compose_impl(h, (const ReadInterval*)d_outer, n_reads, (const ReadInterval*)d_inner, d_index, n_kept, (ReadInterval*)d_out)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held; n_reads is even.  The two masked tables into h->pair_tab, *counts filled.  d_starts (may be NULL: the
+// intervals are then taken as they are): EINVAL where brisk_hip_extract_packed gives it, before anything is extracted.
+static int pair_split_impl(brisk_hip_index* h, const ReadInterval* d_iv, u64 n_reads, const u64* d_starts, brisk_hip_pair_counts* counts, const ReadInterval** iv_pairs,
+                           const ReadInterval** iv_singles) {
+    int rc;
+    memset(counts, 0, sizeof(*counts));
+    counts->n_pairs_in = n_reads / 2;
+    *iv_pairs = *iv_singles = nullptr;
+    if (!n_reads) return BRISK_HIP_OK;
+    if ((rc = ensure(h, h->pair_tab, kPairHeadBytes + 2 * n_reads * sizeof(ReadInterval)))) return rc;
+    unsigned long long* d_ctr = (unsigned long long*)h->pair_tab.p;
+    unsigned long long* d_flags = pair_flags(h);
+    ReadInterval* d_p = (ReadInterval*)((char*)h->pair_tab.p + kPairHeadBytes);
+    ReadInterval* d_s = d_p + n_reads;
+    HIPCHK(h, hipMemsetAsync(d_ctr, 0, kPairHeadBytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 8, h->stream));
+    hipLaunchKernelGGL(k_pair_split, dim3(nblocks(n_reads / 2, 256 * PAIR_ITEMS)), dim3(256), 0, h->stream, d_iv, n_reads / 2, d_starts, d_p, d_s, d_ctr, d_flags);
+    if ((rc = launch_check(h, "k_pair_split"))) return rc;
+    std::vector<u64> rows(kPairHeadBytes / 8);
+    HIPCHK(h, hipMemcpyAsync(rows.data(), d_ctr, kPairHeadBytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    u64 got[8] = {0, 0, 0, 0, 0, 0, rows[kPairCtrBytes / 8], rows[kPairCtrBytes / 8 + 1]};
+    for (size_t r = 0; r < PAIR_CTR_ROWS; r++)
+        for (int i = 0; i < 6; i++) got[i] += rows[r * 8 + i];
+    if (got[7]) return fail(h, BRISK_HIP_EINVAL, "extract_pairs_packed: read offsets do not ascend (offsets[i + 1] < offsets[i])");
+    if (got[6] != ~0ull) return fail(h, BRISK_HIP_EINVAL, "extract_pairs_packed: the interval of read " + std::to_string(got[6]) + " ends beyond the read (start + len > its length)");
+    counts->n_pairs_kept = got[0];
+    counts->n_single_first = got[1];
+    counts->n_single_second = got[2];
+    counts->n_pairs_dropped = got[3];
+    counts->n_nts_pairs = got[4];
+    counts->n_nts_singles = got[5];
+    *iv_pairs = d_p;
+    *iv_singles = d_s;
+    return BRISK_HIP_OK;
+}
+
+struct PairOut {  // one output stream of the pairs calls: brisk_hip_extract_packed's four
+    u32* packed;
+    u64 cap_words;
+    u64* starts;
+    u64* index;
+};
+static int check_pair_outs(brisk_hip_index* h, const PairOut& P, const PairOut& S, const brisk_hip_pair_counts* counts, const char* who) {
+    if (!counts || !P.packed || !P.starts) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": null pointer");
+    if (!S.packed || !S.starts) {
+        if (S.packed || S.starts || S.index || S.cap_words) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": the singles output is given in part (all four NULL / 0 drops the singles)");
+    }
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held; the arguments are checked.  Split and count (one pass, a host synchronisation), refuse before either
+// stream is written, then brisk_hip_extract_packed's own block / apply / gather passes over each masked table.
+static int extract_pairs_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, const ReadInterval* d_iv, const PairOut& P, const PairOut& S,
+                              brisk_hip_pair_counts* counts) {
+    int rc;
+    const ReadInterval *iv_p = nullptr, *iv_s = nullptr;
+    if ((rc = pair_split_impl(h, d_iv, n_reads, d_starts, counts, &iv_p, &iv_s))) return rc;
+    const u64 need_p = (counts->n_nts_pairs + 15) / 16 + 2, need_s = (counts->n_nts_singles + 15) / 16 + 2;
+    if (P.cap_words < need_p)
+        return fail(h, BRISK_HIP_ECAPACITY, "extract_pairs_packed: " + std::to_string(counts->n_nts_pairs) + " nucleotides of pairs need " + std::to_string(need_p) + " words, the pairs output holds " + std::to_string(P.cap_words));
+    if (S.packed && S.cap_words < need_s)
+        return fail(h, BRISK_HIP_ECAPACITY, "extract_pairs_packed: " + std::to_string(counts->n_nts_singles) + " nucleotides of singles need " + std::to_string(need_s) + " words, the singles output holds " + std::to_string(S.cap_words));
+    u64 n_out = 0, n_nts = 0;
+    if ((rc = extract_impl(h, d_packed, d_starts, n_reads, iv_p, P.packed, P.cap_words, P.starts, P.index, &n_out, &n_nts))) return rc;
+    if (n_out != 2 * counts->n_pairs_kept || n_nts != counts->n_nts_pairs) return fail(h, BRISK_HIP_EHIP, "extract_pairs_packed: the pairs stream and the pair counts disagree");
+    if (!S.packed) return BRISK_HIP_OK;
+    if ((rc = extract_impl(h, d_packed, d_starts, n_reads, iv_s, S.packed, S.cap_words, S.starts, S.index, &n_out, &n_nts))) return rc;
+    if (n_out != counts->n_single_first + counts->n_single_second || n_nts != counts->n_nts_singles) return fail(h, BRISK_HIP_EHIP, "extract_pairs_packed: the singles stream and the pair counts disagree");
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_extract_pairs_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, const brisk_hip_read_interval* d_intervals,
+                                             uint32_t* d_pairs_packed, uint64_t pairs_cap_words, uint64_t* d_pairs_starts, uint64_t* d_pairs_index, uint32_t* d_singles_packed,
+                                             uint64_t singles_cap_words, uint64_t* d_singles_starts, uint64_t* d_singles_index, brisk_hip_pair_counts* counts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    const PairOut P = {d_pairs_packed, pairs_cap_words, d_pairs_starts, d_pairs_index}, S = {d_singles_packed, singles_cap_words, d_singles_starts, d_singles_index};
+    if (int orc = check_pair_outs(h, P, S, counts, "extract_pairs_packed")) return orc;
+    if (n_reads && (!d_packed || !d_starts || !d_intervals)) return fail(h, BRISK_HIP_EINVAL, "extract_pairs_packed: null pointer");
+    if (int crc = check_pairs(h, n_reads, BRISK_HIP_PAIR_EACH, "extract_pairs_packed")) return crc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    return extract_pairs_impl(h, d_packed, d_starts, n_reads, (const ReadInterval*)d_intervals, P, S, counts);
+}
+
+// the rule that keeps a read whole (subject to the same minimum length): what BRISK_HIP_PAIR_ANY restores
+static brisk_hip_select_rule whole_rule(const brisk_hip_select_rule* rule) {
+    brisk_hip_select_rule w;
+    memset(&w, 0, sizeof(w));
+    w.struct_size = sizeof(w);
+    w.kind = BRISK_HIP_SELECT_MEDIAN;  // (a median is at most 255: every read with a k-mer passes)
+    w.min_len = rule->min_len;
+    w.lo = 0;
+    w.hi = 0xffffffffu;
+    return w;
+}
+
+// The handle's lock is held, pending inserts are completed.  d_each[0 .. n_reads): the rule over the profiles of a packed stream, as
+// brisk_hip_trim_packed computes them, one internal batch at a time; d_whole (may be NULL): the same reads kept whole.
+static int profile_select(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u32 solid_min, const brisk_hip_select_rule* rule, ReadInterval* d_each,
+                          ReadInterval* d_whole) {
+    int rc;
+    if (!n_reads) return BRISK_HIP_OK;
+    const brisk_hip_select_rule whole = whole_rule(rule);
+    const u64 batch = std::min<u64>(h->max_batch_reads, profile_batch_reads());
+    if ((rc = ensure(h, h->prof_out, std::min<u64>(batch, n_reads) * sizeof(ReadProfile)))) return rc;
+    for (u64 r0 = 0; r0 < n_reads; r0 += batch) {
+        const u64 nb = std::min<u64>(batch, n_reads - r0);
+        u64 ns = 0;
+        if ((rc = count_kmers(h, d_starts + r0, nb, &ns))) return rc;  // (EINVAL on a table that does not ascend)
+        if ((rc = profile_batch(h, d_packed, d_starts + r0, nb, ns, solid_min, (ReadProfile*)h->prof_out.p))) return rc;
+        if ((rc = select_impl(h, (const ReadProfile*)h->prof_out.p, nb, rule, d_each + r0))) return rc;
+        if (d_whole && (rc = select_impl(h, (const ReadProfile*)h->prof_out.p, nb, &whole, d_whole + r0))) return rc;
+    }
+    return check_device_flags(h);
+}
+
+BRISK_API int brisk_hip_trim_pairs_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, const brisk_hip_select_rule* rule,
+                                          uint32_t pair_mode, uint32_t* d_pairs_packed, uint64_t pairs_cap_words, uint64_t* d_pairs_starts, uint64_t* d_pairs_index,
+                                          uint32_t* d_singles_packed, uint64_t singles_cap_words, uint64_t* d_singles_starts, uint64_t* d_singles_index, brisk_hip_pair_counts* counts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_packed on a sharded index sees one bucket range only");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_packed on an entry-id index: DATA lives with the caller (find_kmers)");
+    if (int rrc = check_rule(h, rule, "trim_pairs_packed")) return rrc;
+    if (int crc = check_pairs(h, n_reads, pair_mode, "trim_pairs_packed")) return crc;
+    const PairOut P = {d_pairs_packed, pairs_cap_words, d_pairs_starts, d_pairs_index}, S = {d_singles_packed, singles_cap_words, d_singles_starts, d_singles_index};
+    if (int orc = check_pair_outs(h, P, S, counts, "trim_pairs_packed")) return orc;
+    if (n_reads && (!d_packed || !d_starts)) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_packed: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    int rc;
+    const bool any = pair_mode == BRISK_HIP_PAIR_ANY;
+    if (n_reads) {
+        if ((rc = ensure(h, h->ext_iv, n_reads * sizeof(ReadInterval)))) return rc;
+        if (any && (rc = ensure(h, h->pair_iv, n_reads * sizeof(ReadInterval)))) return rc;
+        ReadInterval* d_each = (ReadInterval*)h->ext_iv.p;
+        ReadInterval* d_whole = any ? (ReadInterval*)h->pair_iv.p : nullptr;
+        if ((rc = profile_select(h, d_packed, d_starts, n_reads, solid_min, rule, d_each, d_whole))) return rc;
+        if ((rc = pair_intervals_impl(h, d_each, d_whole, n_reads, pair_mode, d_each))) return rc;
+    }
+    return extract_pairs_impl(h, d_packed, d_starts, n_reads, (const ReadInterval*)h->ext_iv.p, P, S, counts);
+}
+
+BRISK_API int brisk_hip_trim_pairs_reads(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t solid_min, const brisk_hip_select_rule* rule,
+                                         uint32_t pair_mode, brisk_hip_read_interval* out, brisk_hip_pair_counts* counts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_reads on a sharded index sees one bucket range only");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_reads on an entry-id index: DATA lives with the caller (find_kmers)");
+    if (int rrc = check_rule(h, rule, "trim_pairs_reads")) return rrc;
+    if (int crc = check_pairs(h, n_reads, pair_mode, "trim_pairs_reads")) return crc;
+    if (!counts || (n_reads && (!bases || !offsets || !out))) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_reads: null pointer");
+    for (u64 r = 0; r < n_reads; r++) {
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (offsets[r + 1] - offsets[r] >= PROFILE_MAX_SLOTS + h->P.k) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_reads: a read of more than 2^32-1 slots does not fit the record");
+    }
+    memset(counts, 0, sizeof(*counts));
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    BatchLimit limit(h);
+    int rc;
+    // the whole call's intervals stay on the device until the pair decision: a batch may end between two mates
+    const bool any = pair_mode == BRISK_HIP_PAIR_ANY;
+    const brisk_hip_select_rule whole = whole_rule(rule);
+    if ((rc = ensure(h, h->ext_iv, n_reads * sizeof(ReadInterval)))) return rc;
+    if (any && (rc = ensure(h, h->pair_iv, n_reads * sizeof(ReadInterval)))) return rc;
+    ReadInterval* d_each = (ReadInterval*)h->ext_iv.p;
+    ReadInterval* d_whole = any ? (ReadInterval*)h->pair_iv.p : nullptr;
+    rc = for_each_host_batch(h, bases, offsets, n_reads, [&](u64 r0, u64 nr) -> int {
+        int rc2;
+        if ((rc2 = ensure(h, h->prof_out, nr * sizeof(ReadProfile)))) return rc2;
+        if ((rc2 = profile_batch(h, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, nr, host_slots(offsets, r0, r0 + nr, h->P.k), solid_min, (ReadProfile*)h->prof_out.p)))
+            return rc2;
+        if ((rc2 = select_impl(h, (const ReadProfile*)h->prof_out.p, nr, rule, d_each + r0))) return rc2;
+        if (any && (rc2 = select_impl(h, (const ReadProfile*)h->prof_out.p, nr, &whole, d_whole + r0))) return rc2;
+        HIPCHK(h, hipStreamSynchronize(h->stream));  // (the next batch's upload overwrites what this one's kernels read)
+        return BRISK_HIP_OK;
+    });
+    if (rc) return rc;
+    if ((rc = check_device_flags(h))) return rc;
+    if ((rc = pair_intervals_impl(h, d_each, d_whole, n_reads, pair_mode, d_each))) return rc;
+    const ReadInterval *iv_p, *iv_s;
+    if ((rc = pair_split_impl(h, d_each, n_reads, nullptr, counts, &iv_p, &iv_s))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, d_each, n_reads * sizeof(ReadInterval), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held; the rules and n_reads are checked; with a select rule pending inserts are completed.  Raw reads on the
+// device -> *stats, and (n_reads > 0) *d_final: one interval per raw read after the pair decision; *d_raw / *d_raw_starts: the raw
+// bytes as a packed stream whose read table begins at 0 (scratch of the handle, all three).
+static int clean_pairs_core(brisk_hip_index* h, const uint8_t* d_bases, const uint8_t* d_quals, const u64* d_offsets, u64 n_reads, u32 min_len, u32 thr,
+                            const brisk_hip_select_rule* select, u32 solid_min, u32 pair_mode, brisk_hip_intake_stats* stats, const ReadInterval** d_final, const u32** d_raw,
+                            const u64** d_raw_starts) {
+    int rc;
+    *d_final = nullptr;
+    *d_raw = nullptr;
+    *d_raw_starts = nullptr;
+    if ((rc = intake_impl(h, d_bases, d_quals, d_offsets, n_reads, min_len, thr, nullptr, 0, nullptr, nullptr, ~0ull, stats))) return rc;  // the table only: its rows stay in ink_tab
+    if (!n_reads) return BRISK_HIP_OK;
+    if ((rc = ensure(h, h->pair_iv, 2 * n_reads * sizeof(ReadInterval)))) return rc;
+    ReadInterval* d_iv1 = (ReadInterval*)h->pair_iv.p;
+    ReadInterval* d_each = d_iv1 + n_reads;
+    if ((rc = fragment_intervals_impl(h, (const IntakeFragment*)h->ink_tab.p, stats->n_fragments, n_reads, d_iv1))) return rc;
+    // the raw bytes, packed: a byte that is no base packs to some code, and lies in no fragment
+    u64 lo = 0;
+    HIPCHK(h, hipMemcpyAsync(&lo, d_offsets, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 n_bytes = stats->n_bases_in, n_words = (n_bytes + 15) / 16, words_room = (n_words + 3) & ~1ull;
+    if ((rc = ensure(h, h->pair_raw, words_room * 4 + (n_reads + 1) * 8))) return rc;
+    u32* d_packed = (u32*)h->pair_raw.p;
+    u64* d_starts = (u64*)(d_packed + words_room);
+    HIPCHK(h, hipMemsetAsync(d_packed + n_words, 0, 8, h->stream));
+    if (n_words) {
+        if (n_words > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "clean_pairs: more input words than one launch covers");
+        ProfScope ps(h, S_PACK);
+        hipLaunchKernelGGL(k_pack_ascii, dim3(nblocks(n_words, 256)), dim3(256), 0, h->stream, d_bases + lo, n_bytes, d_packed, n_words);
+    }
+    hipLaunchKernelGGL(k_rebase_starts, dim3(nblocks(n_reads + 1, 256)), dim3(256), 0, h->stream, d_offsets, n_reads + 1, lo, d_starts);
+    if ((rc = launch_check(h, "k_pack_ascii / k_rebase_starts"))) return rc;
+    const ReadInterval* d_judged = d_iv1;
+    if (select) {
+        // the first longest fragment of every read as a stream of its own, its profile, the rule, and the cut back in the raw read's frame
+        if ((rc = ensure(h, h->pair_fs, words_room * 4 + (n_reads + 1) * 8 + n_reads * 8))) return rc;
+        u32* d_fs = (u32*)h->pair_fs.p;
+        u64* d_fs_starts = (u64*)(d_fs + words_room);
+        u64* d_fs_index = d_fs_starts + n_reads + 1;
+        u64 n_kept = 0, n_nts = 0;
+        if ((rc = extract_impl(h, d_packed, d_starts, n_reads, d_iv1, d_fs, n_words + 2, d_fs_starts, d_fs_index, &n_kept, &n_nts))) return rc;
+        if ((rc = ensure(h, h->ext_iv, std::max<u64>(n_kept, 1) * sizeof(ReadInterval)))) return rc;
+        if ((rc = profile_select(h, d_fs, d_fs_starts, n_kept, solid_min, select, (ReadInterval*)h->ext_iv.p, nullptr))) return rc;
+        if ((rc = compose_impl(h, d_iv1, n_reads, (const ReadInterval*)h->ext_iv.p, d_fs_index, n_kept, d_each))) return rc;
+        d_judged = d_each;
+    }
+    if ((rc = pair_intervals_impl(h, d_judged, d_iv1, n_reads, pair_mode, d_each))) return rc;
+    *d_final = d_each;
+    *d_raw = d_packed;
+    *d_raw_starts = d_starts;
+    return BRISK_HIP_OK;
+}
+
+static int check_clean_pairs(brisk_hip_index* h, const brisk_hip_intake_rule* intake, bool have_quals, const brisk_hip_select_rule* select, u64 n_reads, u32 pair_mode, const char* who,
+                             u32* min_len, u32* thr) {
+    if (int rrc = check_intake_rule(h, intake, have_quals, who, min_len, thr)) return rrc;
+    if (select) {
+        if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, std::string(who) + " with a select rule on a sharded index sees one bucket range only");
+        if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, std::string(who) + " with a select rule on an entry-id index: DATA lives with the caller (find_kmers)");
+        if (int src = check_rule(h, select, who)) return src;
+    }
+    return check_pairs(h, n_reads, pair_mode, who);
+}
+
+BRISK_API int brisk_hip_clean_pairs_ascii(brisk_hip_index* h, const char* d_bases, const char* d_quals, const uint64_t* d_offsets, uint64_t n_reads, const brisk_hip_intake_rule* intake,
+                                          const brisk_hip_select_rule* select, uint32_t solid_min, uint32_t pair_mode, uint32_t* d_pairs_packed, uint64_t pairs_cap_words,
+                                          uint64_t* d_pairs_starts, uint64_t* d_pairs_index, uint32_t* d_singles_packed, uint64_t singles_cap_words, uint64_t* d_singles_starts,
+                                          uint64_t* d_singles_index, brisk_hip_read_interval* d_out_intervals, brisk_hip_pair_counts* counts, brisk_hip_intake_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    u32 min_len = 0, thr = 0;
+    if (int crc = check_clean_pairs(h, intake, d_quals != nullptr, select, n_reads, pair_mode, "clean_pairs_ascii", &min_len, &thr)) return crc;
+    const PairOut P = {d_pairs_packed, pairs_cap_words, d_pairs_starts, d_pairs_index}, S = {d_singles_packed, singles_cap_words, d_singles_starts, d_singles_index};
+    if (int orc = check_pair_outs(h, P, S, counts, "clean_pairs_ascii")) return orc;
+    if (!stats || (n_reads && (!d_bases || !d_offsets))) return fail(h, BRISK_HIP_EINVAL, "clean_pairs_ascii: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (select)
+        if (int frc = enter(h)) return frc;
+    int rc;
+    const ReadInterval* d_final = nullptr;
+    const u32* d_raw = nullptr;
+    const u64* d_raw_starts = nullptr;
+    if ((rc = clean_pairs_core(h, (const uint8_t*)d_bases, (const uint8_t*)d_quals, d_offsets, n_reads, min_len, thr, select, solid_min, pair_mode, stats, &d_final, &d_raw, &d_raw_starts)))
+        return rc;
+    if ((rc = extract_pairs_impl(h, d_raw, d_raw_starts, n_reads, d_final, P, S, counts))) return rc;
+    if (d_out_intervals && n_reads) {
+        HIPCHK(h, hipMemcpyAsync(d_out_intervals, d_final, n_reads * sizeof(ReadInterval), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_clean_pairs_reads(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, const brisk_hip_intake_rule* intake,
+                                          const brisk_hip_select_rule* select, uint32_t solid_min, uint32_t pair_mode, brisk_hip_read_interval* out, brisk_hip_pair_counts* counts,
+                                          brisk_hip_intake_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    u32 min_len = 0, thr = 0;
+    if (int crc = check_clean_pairs(h, intake, quals != nullptr, select, n_reads, pair_mode, "clean_pairs_reads", &min_len, &thr)) return crc;
+    if (!stats || !counts || (n_reads && (!bases || !offsets || !out))) return fail(h, BRISK_HIP_EINVAL, "clean_pairs_reads: null pointer");
+    if (int orc = check_raw_reads(h, offsets, n_reads, "clean_pairs_reads")) return orc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    memset(stats, 0, sizeof(*stats));
+    memset(counts, 0, sizeof(*counts));
+    if (select)
+        if (int frc = enter(h)) return frc;
+    return for_each_raw_piece(h, bases, thr ? quals : nullptr, offsets, n_reads, [&](u64 r0, u64 nr, const uint8_t* d_b, const uint8_t* d_q, const u64* d_offs) -> int {
+        int rc2;
+        brisk_hip_intake_stats st;
+        brisk_hip_pair_counts pc;
+        const ReadInterval *d_final = nullptr, *iv_p, *iv_s;
+        const u32* d_raw = nullptr;
+        const u64* d_raw_starts = nullptr;
+        if ((rc2 = clean_pairs_core(h, d_b, d_q, d_offs, nr, min_len, thr, select, solid_min, pair_mode, &st, &d_final, &d_raw, &d_raw_starts))) return rc2;
+        if ((rc2 = pair_split_impl(h, d_final, nr, nullptr, &pc, &iv_p, &iv_s))) return rc2;
+        HIPCHK(h, hipMemcpyAsync(out + r0, d_final, nr * sizeof(ReadInterval), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        add_intake_stats(stats, st);
+        uint64_t* a = (uint64_t*)counts;
+        const uint64_t* b = (const uint64_t*)&pc;
+        for (size_t i = 0; i < sizeof(pc) / 8; i++) a[i] += b[i];
+        return BRISK_HIP_OK;
+    }, 2);
 }
 
 BRISK_API int brisk_hip_lookup(brisk_hip_index* h, const uint64_t* kmer_lo, const uint64_t* kmer_hi, const uint8_t* minimizer_idx, uint64_t n,
@@ -2986,7 +3407,7 @@ BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t
     if (memory_bytes) {
         u64 m = h->arena_cap * (8ull * h->ix.key_words + 1) + h->n_parts * 16 + (h->n_buckets + 7) / 8 + (h->n_parts + 1) * 20;
         for (const DevBuf* b : {&h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp,
-                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed})
+                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed, &h->pair_tab, &h->pair_iv, &h->pair_raw, &h->pair_fs})
             m += b->bytes;
         *memory_bytes = m;
     }

@@ -34,7 +34,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU). In-tree output."""
     out = library_path()
     srcs = [os.path.join(HERE, "csrc", f) for f in ("brisk_capi.hip", "brisk_kernels.hip", "brisk_scan.hip", "brisk_partition.hip", "brisk_insert.hip",
-                                                    "brisk_readout.hip", "brisk_answers.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_extract.hip", "brisk_intake.hip", "brisk_device.h")]
+                                                    "brisk_readout.hip", "brisk_answers.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_extract.hip", "brisk_intake.hip", "brisk_pairs.hip", "brisk_device.h")]
     srcs.append(os.path.join(ROOT, "include", "brisk_hip.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
@@ -126,6 +126,8 @@ SYMBOLS = [
     "brisk_hip_scan_kmers", "brisk_hip_record_kmers", "brisk_hip_answer_records", "brisk_hip_place_answers", "brisk_hip_profile_slots",
     "brisk_hip_select_intervals", "brisk_hip_extract_packed", "brisk_hip_trim_packed", "brisk_hip_trim_reads", "brisk_hip_unpack_ascii",
     "brisk_hip_intake_ascii", "brisk_hip_intake_reads", "brisk_hip_insert_raw_reads",
+    "brisk_hip_fragment_intervals", "brisk_hip_pair_intervals", "brisk_hip_compose_intervals", "brisk_hip_extract_pairs_packed",
+    "brisk_hip_trim_pairs_packed", "brisk_hip_trim_pairs_reads", "brisk_hip_clean_pairs_ascii", "brisk_hip_clean_pairs_reads",
     "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_joint_spectrum", "brisk_hip_filter_joint", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
     "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
@@ -172,6 +174,17 @@ def load() -> C.CDLL:
     L.brisk_hip_intake_ascii.argtypes = [vp, vp, vp, vp, u64, C.POINTER(_IntakeRule), vp, u64, vp, vp, u64, C.POINTER(_IntakeStats)]
     L.brisk_hip_intake_reads.argtypes = [vp, vp, vp, _u64p, u64, C.POINTER(_IntakeRule), _fragp, u64, C.POINTER(_IntakeStats)]
     L.brisk_hip_insert_raw_reads.argtypes = [vp, vp, vp, _u64p, u64, C.POINTER(_IntakeRule), C.POINTER(_IntakeStats)]
+    _pair_out4 = [vp, u64, vp, vp]  # one output stream: packed, cap_words, starts, index
+    L.brisk_hip_fragment_intervals.argtypes = [vp, vp, u64, u64, vp]
+    L.brisk_hip_pair_intervals.argtypes = [vp, vp, vp, u64, u32, vp]
+    L.brisk_hip_compose_intervals.argtypes = [vp, vp, u64, vp, vp, u64, vp]
+    L.brisk_hip_extract_pairs_packed.argtypes = [vp, vp, vp, u64, vp] + _pair_out4 * 2 + [C.POINTER(_PairCounts)]
+    L.brisk_hip_trim_pairs_packed.argtypes = [vp, vp, vp, u64, u32, C.POINTER(_SelectRule), u32] + _pair_out4 * 2 + [C.POINTER(_PairCounts)]
+    L.brisk_hip_trim_pairs_reads.argtypes = [vp, _u8p, _u64p, u64, u32, C.POINTER(_SelectRule), u32, _ivp, C.POINTER(_PairCounts)]
+    L.brisk_hip_clean_pairs_ascii.argtypes = [vp, vp, vp, vp, u64, C.POINTER(_IntakeRule), C.POINTER(_SelectRule), u32, u32] + _pair_out4 * 2 + \
+                                             [vp, C.POINTER(_PairCounts), C.POINTER(_IntakeStats)]
+    L.brisk_hip_clean_pairs_reads.argtypes = [vp, vp, vp, _u64p, u64, C.POINTER(_IntakeRule), C.POINTER(_SelectRule), u32, u32, _ivp, C.POINTER(_PairCounts),
+                                              C.POINTER(_IntakeStats)]
     L.brisk_hip_enumerate.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64)]
     L.brisk_hip_stats.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.brisk_hip_checksum.argtypes = [vp, _u64p]
@@ -423,12 +436,146 @@ def _pack_raw(seqs, quals):
     return flat, qflat, offs
 
 
+# ---- paired-end reads (include/brisk_hip.h, "paired-end reads"): an interleaved stream, reads 2p and 2p + 1 the mates of pair p ----
+# brisk_hip_pair_intervals' pair_mode: BRISK_HIP_PAIR_EACH / _ALL / _ANY
+PAIR_MODES = {"each": 0, "all": 1, "any": 2}
+PAIR_COUNTS_FIELDS = ("n_pairs_in", "n_pairs_kept", "n_single_first", "n_single_second", "n_pairs_dropped", "n_nts_pairs", "n_nts_singles", "reserved")
+
+
+class _PairCounts(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in PAIR_COUNTS_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in PAIR_COUNTS_FIELDS}
+
+
+def _pair_mode(mode) -> int:
+    m = PAIR_MODES.get(mode, -1) if isinstance(mode, str) else int(mode)
+    if m not in (0, 1, 2):
+        raise ValueError("unknown pair mode %r" % (mode,))
+    return m
+
+
+def intervals_from_fragments(frags, n_reads: int) -> np.ndarray:
+    """brisk_hip_fragment_intervals on the host: READ_INTERVAL_DTYPE[n_reads] from an intake fragment table (FRAGMENT_DTYPE, ordered by
+    read, then by position) -- {start, len} of the first longest fragment of every read, {0, 0} for a read without one.  The
+    definition, written out; no device needed.  ValueError on a row with read >= n_reads and on a table that is not ordered."""
+    f = np.asarray(frags)
+    assert f.dtype == FRAGMENT_DTYPE
+    read, start, length = f["read"].astype(np.int64), f["start"].astype(np.int64), f["len"].astype(np.int64)
+    if len(f) and (f["read"] >= np.uint64(n_reads)).any():
+        raise ValueError("row %d names a read >= n_reads" % int(np.nonzero(f["read"] >= np.uint64(n_reads))[0][0]))
+    unordered = (read[1:] < read[:-1]) | ((read[1:] == read[:-1]) & (start[1:] <= start[:-1]))
+    if unordered.any():
+        raise ValueError("row %d stands before the row ahead of it" % (int(np.nonzero(unordered)[0][0]) + 1))
+    out = np.zeros(n_reads, READ_INTERVAL_DTYPE)
+    if len(f):
+        order = np.lexsort((np.arange(len(f)), -length, read))  # by read; the longest first; of equal lengths the earliest row
+        first = np.concatenate(([True], read[order][1:] != read[order][:-1]))
+        best = order[first]
+        out["start"][read[best]] = start[best]
+        out["len"][read[best]] = length[best]
+    return out
+
+
+def pair_intervals(each, whole, mode) -> np.ndarray:
+    """brisk_hip_pair_intervals on the host: the pair decision over interleaved READ_INTERVAL_DTYPE rows.  "each": the rows of `each`
+    as they are; "all": a pair keeps both rows of `each` when both have len > 0, else both become {0, 0}; "any": when either mate's
+    row of `each` has len > 0 both mates get their row of `whole` (one with len 0 stays {0, 0}), else both become {0, 0}.  `whole` is
+    needed for "any" only.  ValueError on an odd number of rows, an unknown mode, "any" without `whole`."""
+    m = _pair_mode(mode)
+    e = np.asarray(each)
+    assert e.dtype == READ_INTERVAL_DTYPE
+    if len(e) % 2:
+        raise ValueError("an interleaved stream holds whole pairs: %d rows" % len(e))
+    out = e.copy()
+    kept = (e["len"] > 0).reshape(-1, 2)
+    if m == 1:
+        out[np.repeat(~kept.all(axis=1), 2)] = (0, 0)
+    elif m == 2:
+        if whole is None:
+            raise ValueError('"any" needs the whole-read intervals')
+        w = np.asarray(whole)
+        assert w.dtype == READ_INTERVAL_DTYPE and len(w) == len(e)
+        out = w.copy()
+        out[(w["len"] == 0) | np.repeat(~kept.any(axis=1), 2)] = (0, 0)
+    return out
+
+
+def compose_intervals(outer, inner, index) -> np.ndarray:
+    """brisk_hip_compose_intervals on the host: two cuts chained.  outer[n_reads] is the first cut; inner[n_kept] a cut of the reads
+    the first one kept; index[n_kept] (ascending) the input read behind each of those.  out[index[j]] = {outer.start + inner[j].start,
+    inner[j].len} ({0, 0} when inner[j].len == 0), every other row {0, 0}.  ValueError where inner leaves outer (inner.start +
+    inner.len > outer.len), where index[j] >= n_reads, and on an index that does not ascend."""
+    o, i = np.asarray(outer), np.asarray(inner)
+    idx = np.asarray(index, np.uint64)
+    assert o.dtype == READ_INTERVAL_DTYPE and i.dtype == READ_INTERVAL_DTYPE and len(i) == len(idx)
+    if len(idx) and (idx >= np.uint64(len(o))).any():
+        raise ValueError("row %d: the index names a read >= n_reads" % int(np.nonzero(idx >= np.uint64(len(o)))[0][0]))
+    idx = idx.astype(np.int64)
+    if (idx[1:] <= idx[:-1]).any():
+        raise ValueError("the index does not ascend at row %d" % (int(np.nonzero(idx[1:] <= idx[:-1])[0][0]) + 1))
+    leaves = i["start"].astype(np.int64) + i["len"].astype(np.int64) > o["len"][idx].astype(np.int64)
+    if leaves.any():
+        raise ValueError("row %d: the inner interval leaves the outer one" % int(np.nonzero(leaves)[0][0]))
+    out = np.zeros(len(o), READ_INTERVAL_DTYPE)
+    keep = i["len"] > 0
+    out["start"][idx[keep]] = o["start"][idx[keep]] + i["start"][keep]
+    out["len"][idx[keep]] = i["len"][keep]
+    return out
+
+
+def split_pairs(intervals):
+    """k_pair_split on the host: (iv_pairs, iv_singles, counts) of interleaved READ_INTERVAL_DTYPE rows -- the rows of intact pairs
+    (both mates have len > 0) with every other row {0, 0}, the rows of singles (exactly one mate has) likewise, and the
+    brisk_hip_pair_counts as a dict.  brisk_hip_extract_pairs_packed is, by definition, brisk_hip_extract_packed over each table."""
+    v = np.asarray(intervals)
+    assert v.dtype == READ_INTERVAL_DTYPE
+    if len(v) % 2:
+        raise ValueError("an interleaved stream holds whole pairs: %d rows" % len(v))
+    kept = (v["len"] > 0).reshape(-1, 2)
+    both, one = np.repeat(kept.all(axis=1), 2), np.repeat(kept.sum(axis=1) == 1, 2)
+    iv_pairs, iv_singles = v.copy(), v.copy()
+    iv_pairs[~both] = (0, 0)
+    iv_singles[~(one & (v["len"] > 0))] = (0, 0)
+    counts = dict.fromkeys(PAIR_COUNTS_FIELDS, 0)
+    counts["n_pairs_in"] = len(kept)
+    counts["n_pairs_kept"] = int(kept.all(axis=1).sum())
+    counts["n_single_first"] = int((kept[:, 0] & ~kept[:, 1]).sum())
+    counts["n_single_second"] = int((kept[:, 1] & ~kept[:, 0]).sum())
+    counts["n_pairs_dropped"] = int((~kept.any(axis=1)).sum())
+    counts["n_nts_pairs"] = int(iv_pairs["len"].astype(np.int64).sum())
+    counts["n_nts_singles"] = int(iv_singles["len"].astype(np.int64).sum())
+    return iv_pairs, iv_singles, counts
+
+
+def _interleave(a, b, what="reads"):
+    """mates as one interleaved list: `a` alone is interleaved already; with `b`, read i of `a` and read i of `b` are a pair"""
+    if b is None:
+        a = list(a)
+        if len(a) % 2:
+            raise ValueError("an interleaved list of %s holds whole pairs: %d" % (what, len(a)))
+        return a
+    a, b = list(a), list(b)
+    if len(a) != len(b):
+        raise ValueError("the two lists of %s differ in length: %d and %d" % (what, len(a), len(b)))
+    return [x for pair in zip(a, b) for x in pair]
+
+
 _ONE_BYTE = np.zeros(1, np.uint8)  # what an empty array's pointer stands on: it lives as long as the module
 
 
 def _host_ptr(a):
     """the address of a numpy array's bytes (of _ONE_BYTE for an empty one: a non-null pointer of which nothing is read), or None"""
     return None if a is None else C.c_void_p(a.ctypes.data if len(a) else _ONE_BYTE.ctypes.data)
+
+
+def _pair_out(out):
+    """(d_out_packed, out_cap_words, d_out_starts, d_out_index) of one output stream of the pairs calls as ctypes arguments; None: all null"""
+    if out is None:
+        return None, 0, None, None
+    d_packed, cap, d_starts, d_index = out
+    return d_packed or None, cap, d_starts or None, d_index or None
 
 
 def joint_spectrum_from_entries(dump_a, dump_b) -> np.ndarray:
@@ -633,6 +780,37 @@ class BriskHip:
         st = _IntakeStats()
         self._chk(self.L.brisk_hip_insert_raw_reads(self.h, _host_ptr(flat), _host_ptr(qflat), offs, len(offs) - 1, C.byref(rule), C.byref(st)))
         return st.as_dict()
+
+    def trim_pairs(self, seqs1: Sequence, seqs2: Optional[Sequence] = None, solid_min: int = 2, rule: Optional[_SelectRule] = None, pair_mode="each"):
+        """trim_reads for paired reads (brisk_hip_trim_pairs_reads): (READ_INTERVAL_DTYPE[n_reads], counts dict).  seqs1 alone is an
+        interleaved list (reads 2p and 2p + 1 are mates); with seqs2, read i of each list are mates and the result is interleaved.  The
+        intervals are pair_intervals(each, whole, pair_mode) of what trim_reads gives for every read alone ("any": a pair of which
+        either mate passes keeps both mates whole); counts is split_pairs' (PAIR_COUNTS_FIELDS).  The caller slices its own strings."""
+        seqs = _interleave(seqs1, seqs2)
+        flat, offs = _pack_reads(seqs)
+        out = np.zeros(max(len(seqs), 1), READ_INTERVAL_DTYPE)
+        if len(flat) == 0:
+            flat = np.zeros(1, np.uint8)
+        rule = select_rule("solid_run") if rule is None else rule
+        pc = _PairCounts()
+        self._chk(self.L.brisk_hip_trim_pairs_reads(self.h, flat, offs, len(seqs), solid_min, C.byref(rule), _pair_mode(pair_mode), out, C.byref(pc)))
+        return out[:len(seqs)], pc.as_dict()
+
+    def clean_pairs(self, seqs1: Sequence, seqs2: Optional[Sequence] = None, quals1: Optional[Sequence] = None, quals2: Optional[Sequence] = None,
+                    intake: Optional[_IntakeRule] = None, rule: Optional[_SelectRule] = None, solid_min: int = 2, pair_mode="each"):
+        """Raw paired reads to one clean interval per read (brisk_hip_clean_pairs_reads): (READ_INTERVAL_DTYPE[n_reads], counts dict,
+        intake stats dict).  Mates are given as in trim_pairs; qualities likewise.  The first longest fragment of a read under the
+        intake rule is the read's; with `rule` (a select_rule) it is cut again by abundance, and the cut is expressed in the raw read's
+        frame; then the pair decision.  seqs[i][start:start + len] holds only ACGTacgt.  Without `rule` no index state is needed."""
+        seqs = _interleave(seqs1, seqs2)
+        quals = None if quals1 is None else _interleave(quals1, quals2, "qualities")
+        flat, qflat, offs = _pack_raw(seqs, quals)
+        intake = intake_rule() if intake is None else intake
+        out = np.zeros(max(len(seqs), 1), READ_INTERVAL_DTYPE)
+        pc, st = _PairCounts(), _IntakeStats()
+        self._chk(self.L.brisk_hip_clean_pairs_reads(self.h, _host_ptr(flat), _host_ptr(qflat), offs, len(seqs), C.byref(intake), C.byref(rule) if rule is not None else None,
+                                                     solid_min, _pair_mode(pair_mode), out, C.byref(pc), C.byref(st)))
+        return out[:len(seqs)], pc.as_dict(), st.as_dict()
 
     def lookup(self, lo, hi, idx) -> Tuple[np.ndarray, np.ndarray]:
         lo = np.ascontiguousarray(lo, np.uint64)
@@ -955,6 +1133,54 @@ class BriskHip:
             return dict(st.as_dict(), rc=rc)
         self._chk(rc)
         return st.as_dict()
+
+    def fragment_intervals(self, d_frags: int, n_frags: int, n_reads: int, d_intervals: int):
+        """d_intervals[r] = the first longest fragment of read r in an intake fragment table (brisk_hip_fragment_intervals), both on
+        the device; intervals_from_fragments is the definition"""
+        self._chk(self.L.brisk_hip_fragment_intervals(self.h, d_frags or None, n_frags, n_reads, d_intervals or None))
+
+    def pair_intervals(self, d_each: int, d_whole: Optional[int], n_reads: int, pair_mode, d_out: int):
+        """the pair decision over interleaved intervals on the device (brisk_hip_pair_intervals); d_out may be d_each; the module's
+        pair_intervals is the definition"""
+        self._chk(self.L.brisk_hip_pair_intervals(self.h, d_each or None, d_whole or None, n_reads, pair_mode if isinstance(pair_mode, int) else _pair_mode(pair_mode), d_out or None))
+
+    def compose_intervals(self, d_outer: int, n_reads: int, d_inner: int, d_index: int, n_kept: int, d_out: int):
+        """two cuts chained on the device (brisk_hip_compose_intervals); the module's compose_intervals is the definition"""
+        self._chk(self.L.brisk_hip_compose_intervals(self.h, d_outer or None, n_reads, d_inner or None, d_index or None, n_kept, d_out or None))
+
+    def _pairs_call(self, rc: int, pc: _PairCounts, raise_on_capacity: bool) -> dict:
+        if rc == ECAPACITY and not raise_on_capacity:
+            return dict(pc.as_dict(), rc=rc)
+        self._chk(rc)
+        return pc.as_dict()
+
+    def extract_pairs_packed(self, d_packed: int, d_starts: int, n_reads: int, d_intervals: int, pairs, singles=None, raise_on_capacity: bool = True) -> dict:
+        """An interleaved packed stream split into intact pairs and singles (brisk_hip_extract_pairs_packed), everything on the device.
+        pairs / singles: (d_out_packed, out_cap_words, d_out_starts, d_out_index) as extract_packed takes them; singles None: counted
+        and dropped.  Returns the counts (PAIR_COUNTS_FIELDS); with raise_on_capacity=False an ECAPACITY answer returns them too, with
+        "rc" set, so that the call can be repeated with room."""
+        pc = _PairCounts()
+        p, s = _pair_out(pairs), _pair_out(singles)
+        return self._pairs_call(self.L.brisk_hip_extract_pairs_packed(self.h, d_packed or None, d_starts or None, n_reads, d_intervals or None, *p, *s, C.byref(pc)), pc, raise_on_capacity)
+
+    def trim_pairs_packed(self, d_packed: int, d_starts: int, n_reads: int, pairs, singles=None, solid_min: int = 2, rule: Optional[_SelectRule] = None, pair_mode="each",
+                          raise_on_capacity: bool = True) -> dict:
+        """trim_packed for clean interleaved reads (brisk_hip_trim_pairs_packed): profile, rule, pair decision, pairs and singles as
+        two packed streams; arguments and result as extract_pairs_packed"""
+        rule = select_rule("solid_run") if rule is None else rule
+        pc = _PairCounts()
+        p, s = _pair_out(pairs), _pair_out(singles)
+        return self._pairs_call(self.L.brisk_hip_trim_pairs_packed(self.h, d_packed or None, d_starts or None, n_reads, solid_min, C.byref(rule), _pair_mode(pair_mode), *p, *s, C.byref(pc)),
+                                pc, raise_on_capacity)
+
+    def clean_pairs_ascii(self, d_bases: int, d_quals: int, d_offsets: int, n_reads: int, intake: _IntakeRule, pairs, singles=None, rule: Optional[_SelectRule] = None,
+                          solid_min: int = 2, pair_mode="each", d_out_intervals: int = 0, raise_on_capacity: bool = True):
+        """Raw interleaved bytes on the device to clean pairs and singles (brisk_hip_clean_pairs_ascii); returns (counts, intake stats)"""
+        pc, st = _PairCounts(), _IntakeStats()
+        p, s = _pair_out(pairs), _pair_out(singles)
+        rc = self.L.brisk_hip_clean_pairs_ascii(self.h, d_bases or None, d_quals or None, d_offsets or None, n_reads, C.byref(intake) if intake is not None else None,
+                                                C.byref(rule) if rule is not None else None, solid_min, _pair_mode(pair_mode), *p, *s, d_out_intervals or None, C.byref(pc), C.byref(st))
+        return self._pairs_call(rc, pc, raise_on_capacity), st.as_dict()
 
     def unpack_ascii(self, d_packed: int, first_nt: int, n_nts: int, d_bases: int):
         """d_bases[i] = "ACTG"[code of nucleotide first_nt + i of the packed stream] (brisk_hip_unpack_ascii): pack_ascii's inverse"""

@@ -58,6 +58,11 @@
  *                               no reference counterpart as a library call: with min_qual == 0 they restate, in bulk and on the
  *                               device, clean_dna (apps/counter.cpp:130-169), which cuts a record at every byte that is not a
  *                               base; the quality cut is Jellyfish's --min-qual-char and KMC's handling of N
+ *   brisk_hip_fragment_intervals / brisk_hip_pair_intervals / brisk_hip_compose_intervals / brisk_hip_extract_pairs_packed /
+ *   brisk_hip_trim_pairs_packed / brisk_hip_trim_pairs_reads / brisk_hip_clean_pairs_ascii / brisk_hip_clean_pairs_reads
+ *                               no reference counterpart; khmer's extract-paired-reads and Trimmomatic's paired mode are the usual
+ *                               tools: paired-end reads kept in sync through intake, trim and extraction -- the pair decision is
+ *                               taken over the mates' intervals, and intact pairs and singles leave as two packed streams
  *   brisk_hip_lookup            Brisk::get (brisk/Brisk.hpp:64-69)
  *   brisk_hip_enumerate         Brisk::next / restart_kmer_enumeration
  *                               (brisk/Brisk.hpp:166-179, brisk/DenseMenuYo.hpp:476-521)
@@ -400,6 +405,96 @@ int brisk_hip_intake_reads(brisk_hip_index *h, const char *bases, const char *qu
  * brisk_hip_insert_reads sends 2: clean input should stay there.  stats may be NULL. */
 int brisk_hip_insert_raw_reads(brisk_hip_index *h, const char *bases, const char *quals /* NULL ok */, const uint64_t *offsets,
                                uint64_t n_reads, const brisk_hip_intake_rule *rule, brisk_hip_intake_stats *stats);
+
+/* ---- paired-end reads: mates kept in sync through intake, trim and extract (no reference counterpart; kernels: brisk_pairs.hip) ---- */
+/* A paired stream is INTERLEAVED: reads 2p and 2p + 1 are mates 1 and 2 of pair p, and n_reads is even.  After any step a read is
+ * kept when its interval has len > 0.  A pair is in one of four states -- both mates kept (intact), only mate 1, only mate 2,
+ * neither -- and the surviving mate of a broken pair is a SINGLE.  Nothing else encodes the state of a pair: it is always readable
+ * from its two intervals.  brisk_amd.intervals_from_fragments, pair_intervals, compose_intervals and split_pairs are the same four
+ * definitions in numpy: what the tests compare with. */
+/* d_intervals[r] (DEVICE, n_reads rows, every one written) = {start, len} of the first longest fragment of read r in an intake
+ * fragment table (d_frags[n_frags], DEVICE: ordered by read, then by position, as brisk_hip_intake_ascii writes it), {0, 0} when the
+ * read has none.  EINVAL, nothing written: a row with read >= n_reads or a row that stands before its predecessor (found on the
+ * device; the message names the first such row).  n_frags == 0 is valid.  Needs no index state: any handle serves. */
+int brisk_hip_fragment_intervals(brisk_hip_index *h, const brisk_hip_fragment *d_frags, uint64_t n_frags, uint64_t n_reads,
+                                 brisk_hip_read_interval *d_intervals);
+/* The pair decision.  d_each: what a rule keeps of every read judged alone; d_whole: what the read would be if kept uncut.
+ *   BRISK_HIP_PAIR_EACH  out = each: mates are judged separately, singles can arise
+ *   BRISK_HIP_PAIR_ALL   a pair keeps both `each` intervals when both have len > 0, else both become {0, 0}
+ *   BRISK_HIP_PAIR_ANY   when either mate's `each` has len > 0 both mates get their `whole` interval (a mate whose `whole` has
+ *                        len 0 stays dropped), else both become {0, 0}
+ * d_whole is required for ANY and ignored otherwise.  EINVAL: odd n_reads, an unknown mode, ANY with d_whole NULL.  d_out may be
+ * d_each.  All DEVICE, n_reads rows each.  Needs no index state. */
+enum { BRISK_HIP_PAIR_EACH = 0, BRISK_HIP_PAIR_ALL = 1, BRISK_HIP_PAIR_ANY = 2 };
+int brisk_hip_pair_intervals(brisk_hip_index *h, const brisk_hip_read_interval *d_each, const brisk_hip_read_interval *d_whole /* NULL ok unless ANY */,
+                             uint64_t n_reads, uint32_t pair_mode, brisk_hip_read_interval *d_out);
+/* Two cuts chained.  d_outer[n_reads]: the first cut, over the input reads; d_inner[n_kept]: a second cut, over the reads that the
+ * first one kept; d_index[n_kept] (ascending, as brisk_hip_extract_packed writes it): the input read behind kept read j.
+ * d_out[d_index[j]] = {outer.start + inner[j].start, inner[j].len} ({0, 0} when inner[j].len == 0); every other row of d_out is
+ * {0, 0}; all n_reads rows are written.  EINVAL, nothing written: inner[j] leaves outer (inner.start + inner.len > outer.len) or
+ * d_index[j] >= n_reads (found on the device; the message names the first such row j), or an index that does not ascend.  d_out
+ * may not overlap the inputs.  All DEVICE.  Needs no index state. */
+int brisk_hip_compose_intervals(brisk_hip_index *h, const brisk_hip_read_interval *d_outer, uint64_t n_reads,
+                                const brisk_hip_read_interval *d_inner, const uint64_t *d_index, uint64_t n_kept,
+                                brisk_hip_read_interval *d_out);
+typedef struct brisk_hip_pair_counts {
+    uint64_t n_pairs_in;       /* n_reads / 2 */
+    uint64_t n_pairs_kept;     /* both mates kept */
+    uint64_t n_single_first;   /* only mate 1 kept */
+    uint64_t n_single_second;  /* only mate 2 kept */
+    uint64_t n_pairs_dropped;  /* neither kept */
+    uint64_t n_nts_pairs;      /* nucleotides of the pairs stream */
+    uint64_t n_nts_singles;    /* nucleotides of the singles stream */
+    uint64_t reserved;         /* 0 */
+} brisk_hip_pair_counts;       /* n_pairs_in == n_pairs_kept + n_single_first + n_single_second + n_pairs_dropped, always */
+/* brisk_hip_extract_packed for an interleaved stream, twice: the PAIRS output is, by definition, extract_packed over the intervals
+ * of intact pairs (every other row {0, 0}), so it is interleaved again -- d_pairs_index[2j] + 1 == d_pairs_index[2j + 1]; the
+ * SINGLES output is extract_packed over the intervals of singles.  Each output has the layout, the room rules (out_cap_words >=
+ * ceil(nts / 16) + 2, starts n_reads + 1, index n_reads or NULL) and the guarantees stated there.  The four singles arguments may
+ * all be NULL / 0: singles are then counted and dropped.  *counts (HOST) is filled whenever the intervals are valid.
+ * BRISK_HIP_ECAPACITY when either output is too small: nothing is written to either, *counts is filled, and the call can be
+ * repeated with room.  EINVAL exactly where brisk_hip_extract_packed gives it, and on odd n_reads.  The two masked tables live in
+ * scratch memory of the handle (16 bytes a read).  Needs no index state: works on any handle. */
+int brisk_hip_extract_pairs_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                                   const brisk_hip_read_interval *d_intervals,
+                                   uint32_t *d_pairs_packed, uint64_t pairs_cap_words, uint64_t *d_pairs_starts, uint64_t *d_pairs_index,
+                                   uint32_t *d_singles_packed, uint64_t singles_cap_words, uint64_t *d_singles_starts, uint64_t *d_singles_index,
+                                   brisk_hip_pair_counts *counts /* HOST */);
+/* brisk_hip_trim_packed for clean, packed, interleaved reads: the profiles as trim_packed takes them, the rule gives `each`, for
+ * BRISK_HIP_PAIR_ANY `whole` comes from the same profiles (the whole read [0, n_kmers + k - 1), dropped below max(rule.min_len, k)
+ * nucleotides), then the pair decision and brisk_hip_extract_pairs_packed.  ANY with BRISK_HIP_SELECT_SOLID_RUN means "either mate
+ * has a solid run: keep both whole".  Refusals and the independence of the answer from batching are those of brisk_hip_trim_packed;
+ * EINVAL also on odd n_reads and an unknown pair_mode.  trim_pairs_reads takes HOST reads and returns the intervals after the pair
+ * decision, out[n_reads] HOST, and the counts: the caller slices its own strings, as with brisk_hip_trim_reads. */
+int brisk_hip_trim_pairs_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                                uint32_t solid_min, const brisk_hip_select_rule *rule, uint32_t pair_mode,
+                                uint32_t *d_pairs_packed, uint64_t pairs_cap_words, uint64_t *d_pairs_starts, uint64_t *d_pairs_index,
+                                uint32_t *d_singles_packed, uint64_t singles_cap_words, uint64_t *d_singles_starts, uint64_t *d_singles_index,
+                                brisk_hip_pair_counts *counts /* HOST */);
+int brisk_hip_trim_pairs_reads(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
+                               uint32_t solid_min, const brisk_hip_select_rule *rule, uint32_t pair_mode,
+                               brisk_hip_read_interval *out /* HOST, n_reads */, brisk_hip_pair_counts *counts /* HOST */);
+/* Raw interleaved reads (bytes of any value, optional qualities: the input of brisk_hip_intake_ascii) to clean pairs and singles,
+ * one interval per raw read.  The intake table is built (only the table); the first longest fragment of a read is the read's (iv1,
+ * brisk_hip_fragment_intervals); the raw bytes are packed into scratch memory (a byte that is no base packs to some code and always
+ * lies outside iv1).  select == NULL: each = iv1, no abundance stage, any handle serves.  Otherwise the one-fragment-per-read stream
+ * is extracted, profiled with solid_min, cut by the select rule, and the cut composed back into the raw read's frame
+ * (brisk_hip_compose_intervals): each; the handle must then be one that brisk_hip_trim_packed takes.  whole = iv1.  Then the pair
+ * decision and brisk_hip_extract_pairs_packed from the packed raw stream.  d_out_intervals (DEVICE, n_reads rows, may be NULL)
+ * receives the final intervals, relative to the raw reads; *stats the intake's; *counts the pairs'.  ECAPACITY as in
+ * brisk_hip_extract_pairs_packed (d_out_intervals is then not written).  clean_pairs_reads takes HOST reads in pieces of whole
+ * pairs (BRISK_INTAKE_PIECE) and returns the intervals, out[n_reads] HOST: the caller slices its own strings. */
+int brisk_hip_clean_pairs_ascii(brisk_hip_index *h, const char *d_bases, const char *d_quals /* NULL ok */, const uint64_t *d_offsets,
+                                uint64_t n_reads, const brisk_hip_intake_rule *intake, const brisk_hip_select_rule *select /* NULL ok */,
+                                uint32_t solid_min, uint32_t pair_mode,
+                                uint32_t *d_pairs_packed, uint64_t pairs_cap_words, uint64_t *d_pairs_starts, uint64_t *d_pairs_index,
+                                uint32_t *d_singles_packed, uint64_t singles_cap_words, uint64_t *d_singles_starts, uint64_t *d_singles_index,
+                                brisk_hip_read_interval *d_out_intervals /* may be NULL */,
+                                brisk_hip_pair_counts *counts /* HOST */, brisk_hip_intake_stats *stats /* HOST */);
+int brisk_hip_clean_pairs_reads(brisk_hip_index *h, const char *bases, const char *quals /* NULL ok */, const uint64_t *offsets,
+                                uint64_t n_reads, const brisk_hip_intake_rule *intake, const brisk_hip_select_rule *select /* NULL ok */,
+                                uint32_t solid_min, uint32_t pair_mode, brisk_hip_read_interval *out /* HOST, n_reads */,
+                                brisk_hip_pair_counts *counts /* HOST */, brisk_hip_intake_stats *stats /* HOST */);
 
 /* point lookups of UNHASHED (kmer_s, minimizer_idx) pairs, as Brisk::get takes them.
  * HOST arrays; out_found[i] in {0,1}; out_data[i] valid when found. */
