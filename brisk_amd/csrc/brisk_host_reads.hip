@@ -1,0 +1,940 @@
+// brisk_host_reads.hip -- the read-cleaning host layer, a part of brisk_capi.hip (included there, not a translation unit of its own):
+// profile -> select -> extract -> intake -> pair decision.  Helpers in an anonymous namespace, then the entry points in one extern "C"
+// block.  Every call that profiles reads walks them in batches of min(max_batch_reads, BRISK_PROFILE_BATCH) through one of two loops,
+// profile_packed_batches (a stream on the device) and profile_host_batches (host reads).  A shared check takes the subject of its
+// message from the caller: the messages are part of the interface.
+namespace {
+
+// ---- per-read abundance profiles (no reference counterpart; kernels: brisk_profile.hip) ----
+static_assert(sizeof(brisk_hip_read_profile) == sizeof(ReadProfile) && offsetof(brisk_hip_read_profile, sum) == offsetof(ReadProfile, sum) &&
+                  offsetof(brisk_hip_read_profile, run_len) == offsetof(ReadProfile, run_len) && offsetof(brisk_hip_read_profile, median_present) == offsetof(ReadProfile, median_present),
+              "the kernels write the C-ABI's record");
+
+// reads above this many slots are reduced in segments of that many: -DBRISK_PROFILE_SEG=<slots> or the environment, read once
+#ifndef BRISK_PROFILE_SEG
+#define BRISK_PROFILE_SEG 4096
+#endif
+u32 profile_seg() {
+    static const u32 seg = [] {
+        long v = BRISK_PROFILE_SEG;
+        if (const char* e = getenv("BRISK_PROFILE_SEG")) v = atol(e);
+        return (u32)std::min<long>(std::max<long>(v, 1), (long)PROFILE_SEG_MAX);
+    }();
+    return seg;
+}
+// a profile call's batches hold at most this many reads (and at most max_batch_reads): their slots are the call's device memory
+u64 profile_batch_reads() {
+    static const u64 n = getenv("BRISK_PROFILE_BATCH") && atoll(getenv("BRISK_PROFILE_BATCH")) > 0 ? (u64)atoll(getenv("BRISK_PROFILE_BATCH")) : (1ull << 24);
+    return n;
+}
+u64 profile_batch_limit(const brisk_hip_index* h) { return std::min<u64>(h->max_batch_reads, profile_batch_reads()); }
+
+// One batch: its slots into kout_tmp (zeroed; kmers_packed_impl exactly as brisk_hip_get_kmers runs it), then one record per read into
+// d_out[0 .. n_reads).  n_slots: the batch's slots (count_kmers / host_slots).
+// caller_slots (brisk_hip_profile_slots): the batch's slots are ext_slots, as the caller holds them; nothing is looked up, only the slot bases are made.
+int profile_batch(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u64 n_slots, u32 solid_min, ReadProfile* d_out,
+                  bool caller_slots = false, const uint16_t* ext_slots = nullptr) {
+    int rc;
+    const u32 seg = profile_seg();
+    // what the table holds: reads that need segments, and a read too long for the record's 32-bit fields
+    if ((rc = ensure(h, h->prof_plan, 64))) return rc;
+    unsigned long long* d_ctr = (unsigned long long*)h->prof_plan.p;
+    HIPCHK(h, hipMemsetAsync(d_ctr, 0, 64, h->stream));
+    const u32 grid_reads = std::max<u32>(std::min<u32>(nblocks(n_reads, 256), 4096), 1);
+    hipLaunchKernelGGL(k_profile_count_long, dim3(grid_reads), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, seg, d_ctr);
+    if ((rc = launch_check(h, "k_profile_count_long"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->h_ctr->prof, d_ctr, 24, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 n_segs = h->h_ctr->prof[0], n_longs = h->h_ctr->prof[1];
+    if (h->h_ctr->prof[2]) return fail(h, BRISK_HIP_EINVAL, "read_profile: a read of more than 2^32-1 slots does not fit the record");
+    if (caller_slots) {
+        if ((rc = slot_bases(h, d_starts, n_reads))) return rc;
+    } else if (n_slots) {
+        if ((rc = ensure(h, h->kout_tmp, n_slots * 2))) return rc;
+        HIPCHK(h, hipMemsetAsync(h->kout_tmp.p, 0, n_slots * 2, h->stream));
+        if ((rc = kmers_packed_impl(h, d_packed, d_starts, n_reads, (uint16_t*)h->kout_tmp.p, n_slots))) return rc;
+    } else {  // nothing to look up; the records still need the table's slot bases (all zero slots: never read)
+        if ((rc = ensure(h, h->slot_buf, (n_reads + 1) * 8))) return rc;
+    }
+    const uint16_t* d_slots = caller_slots ? ext_slots : (const uint16_t*)h->kout_tmp.p;
+    const u64* d_slot_base = (const u64*)h->slot_buf.p;
+    {
+        ProfScope ps(h, S_PROFILE);
+        const u32 grid = std::max<u32>((u32)std::min<u64>((n_reads + 3) / 4, 8192), 1);  // a wave per read, grid-stride
+        hipLaunchKernelGGL(k_profile_reads, dim3(grid), dim3(256), 0, h->stream, d_slots, d_starts, d_slot_base, n_reads, (u32)h->P.k, solid_min, seg, d_out);
+        if ((rc = launch_check(h, "k_profile_reads"))) return rc;
+    }
+    if (!n_longs) return BRISK_HIP_OK;
+    // [64 bytes of counters][long reads][segments][partials]
+    const size_t off_longs = 64, off_segs = off_longs + n_longs * sizeof(ProfileLong), off_part = (off_segs + n_segs * sizeof(ProfileSeg) + 15) / 16 * 16;
+    if ((rc = ensure(h, h->prof_plan, off_part + n_segs * sizeof(ProfilePartial)))) return rc;
+    char* b0 = (char*)h->prof_plan.p;
+    d_ctr = (unsigned long long*)b0;
+    HIPCHK(h, hipMemsetAsync(d_ctr, 0, 64, h->stream));  // (ensure may have moved the buffer)
+    ProfileLong* d_longs = (ProfileLong*)(b0 + off_longs);
+    ProfileSeg* d_segs = (ProfileSeg*)(b0 + off_segs);
+    ProfilePartial* d_part = (ProfilePartial*)(b0 + off_part);
+    ProfScope ps(h, S_PROFILE_LONG);
+    hipLaunchKernelGGL(k_profile_plan, dim3(grid_reads), dim3(256), 0, h->stream, d_starts, n_reads, (u32)h->P.k, seg, d_ctr, d_longs, n_longs, d_segs, n_segs);
+    if ((rc = launch_check(h, "k_profile_plan"))) return rc;
+    hipLaunchKernelGGL(k_profile_segments, dim3((u32)std::min<u64>((n_segs + 3) / 4, 8192)), dim3(256), 0, h->stream, d_slots, d_starts, d_slot_base, (u32)h->P.k, solid_min, seg,
+                       (const ProfileSeg*)d_segs, n_segs, d_part);
+    if ((rc = launch_check(h, "k_profile_segments"))) return rc;
+    hipLaunchKernelGGL(k_profile_fold, dim3((u32)std::min<u64>((n_longs + 3) / 4, 8192)), dim3(256), 0, h->stream, d_starts, (u32)h->P.k, seg, (const ProfileLong*)d_longs, n_longs,
+                       (const ProfilePartial*)d_part, d_out);
+    return launch_check(h, "k_profile_fold");
+}
+
+// The handle's lock is held, pending inserts are completed.  The internal batches of a packed stream: a batch's records go to dest(r0),
+// then each(r0, n, records).  Nothing waits for the stream here: the caller ends with check_device_flags (read_profile_packed synchronises before it).
+template <class Dest, class Each>
+int profile_packed_batches(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u32 solid_min, Dest&& dest, Each&& each) {
+    const u64 batch = profile_batch_limit(h);
+    for (u64 r0 = 0; r0 < n_reads; r0 += batch) {
+        const u64 nb = std::min<u64>(batch, n_reads - r0);
+        u64 ns = 0;
+        int rc;
+        if ((rc = count_kmers(h, d_starts + r0, nb, &ns))) return rc;  // (EINVAL on a table that does not ascend)
+        ReadProfile* d_prof = dest(r0);
+        if ((rc = profile_batch(h, d_packed, d_starts + r0, nb, ns, solid_min, d_prof))) return rc;
+        if ((rc = each(r0, nb, (const ReadProfile*)d_prof))) return rc;
+    }
+    return BRISK_HIP_OK;
+}
+
+// The same for host reads (checked by check_profile_offsets): a batch is uploaded and packed, its records go to prof_out, then
+// each(r0, n, records), then the stream is waited for: the next batch's upload overwrites the packed stream that this one's kernels read.
+template <class Each>
+int profile_host_batches(brisk_hip_index* h, const char* bases, const uint64_t* offsets, u64 n_reads, u32 solid_min, Each&& each) {
+    const u64 saved = h->max_batch_reads;
+    h->max_batch_reads = profile_batch_limit(h);  // for_each_host_batch cuts by it; the handle's lock is held
+    int rc = for_each_host_batch(h, bases, offsets, n_reads, [&](u64 r0, u64 nr) -> int {
+        int rc2;
+        if ((rc2 = ensure(h, h->prof_out, nr * sizeof(ReadProfile)))) return rc2;
+        ReadProfile* d_prof = (ReadProfile*)h->prof_out.p;
+        if ((rc2 = profile_batch(h, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, nr, host_slots(offsets, r0, r0 + nr, h->P.k), solid_min, d_prof))) return rc2;
+        if ((rc2 = each(r0, nr, (const ReadProfile*)d_prof))) return rc2;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    });
+    h->max_batch_reads = saved;
+    return rc ? rc : check_device_flags(h);
+}
+
+// the read table of a host profile call; who: the subject of the second message (the first names none)
+int check_profile_offsets(brisk_hip_index* h, const uint64_t* offsets, u64 n_reads, const char* who) {
+    for (u64 r = 0; r < n_reads; r++) {
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (offsets[r + 1] - offsets[r] >= PROFILE_MAX_SLOTS + h->P.k) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": a read of more than 2^32-1 slots does not fit the record");
+    }
+    return BRISK_HIP_OK;
+}
+
+// ---- read extraction: rule, gather, the composed calls (no reference counterpart; kernels: brisk_extract.hip) ----
+static_assert(sizeof(brisk_hip_read_interval) == sizeof(ReadInterval) && offsetof(brisk_hip_read_interval, len) == offsetof(ReadInterval, len), "the kernels write the C-ABI's interval");
+static_assert(BRISK_HIP_SELECT_SOLID_RUN == SELECT_SOLID_RUN && BRISK_HIP_SELECT_MEDIAN == SELECT_MEDIAN && BRISK_HIP_SELECT_PRESENT == SELECT_PRESENT, "the kernel's kinds are the header's");
+
+int check_rule(brisk_hip_index* h, const brisk_hip_select_rule* rule, const char* who) {
+    if (!rule) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": null rule");
+    if (rule->struct_size < sizeof(brisk_hip_select_rule)) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.struct_size is smaller than brisk_hip_select_rule");
+    if (rule->kind > BRISK_HIP_SELECT_PRESENT) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": unknown rule.kind " + std::to_string(rule->kind));
+    if (rule->lo > rule->hi) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.lo " + std::to_string(rule->lo) + " is above rule.hi " + std::to_string(rule->hi));
+    return BRISK_HIP_OK;
+}
+// the handle's lock is held; the rule is checked
+int select_impl(brisk_hip_index* h, const ReadProfile* d_prof, u64 n_reads, const brisk_hip_select_rule* rule, ReadInterval* d_iv) {
+    if (!n_reads) return BRISK_HIP_OK;
+    hipLaunchKernelGGL(k_select_intervals, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_prof, n_reads, (u32)h->P.k, rule->kind, std::max<u32>(rule->min_len, h->P.k), rule->lo,
+                       rule->hi, d_iv);
+    return launch_check(h, "k_select_intervals");
+}
+
+struct OutStream {  // one output stream: brisk_hip_extract_packed's d_out_packed, out_cap_words, d_out_starts, d_out_index
+    u32* packed;
+    u64 cap_words;
+    u64* starts;
+    u64* index;
+};
+
+// The handle's lock is held.  Counts and flags first (one pass over the table, a host synchronisation), then -- only when the
+// intervals are valid and the output has room -- the tables of the kept reads and the gather: a refused call writes nothing.
+int extract_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, const ReadInterval* d_iv, const OutStream& out, u64* n_out_reads, u64* n_out_nts) {
+    int rc;
+    *n_out_reads = *n_out_nts = 0;
+    u64 n_out = 0, n_nts = 0;
+    const u32 nb = nblocks(n_reads, 256 * EXT_ITEMS);
+    u64 *d_bs_reads = nullptr, *d_bs_nts = nullptr;
+    if (n_reads) {
+        // [64 bytes of flags][block sums of kept reads, nb + 1][of kept nucleotides, nb + 1]
+        if ((rc = ensure(h, h->ext_tmp, 64 + 2 * ((size_t)nb + 1) * 8))) return rc;
+        unsigned long long* d_flags = (unsigned long long*)h->ext_tmp.p;
+        d_bs_reads = (u64*)((char*)h->ext_tmp.p + 64);
+        d_bs_nts = d_bs_reads + nb + 1;
+        HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 8, h->stream));
+        HIPCHK(h, hipMemsetAsync(d_flags + 1, 0, 8, h->stream));
+        hipLaunchKernelGGL(k_extract_block, dim3(nb), dim3(256), 0, h->stream, d_starts, d_iv, n_reads, d_bs_reads, d_bs_nts, d_flags);
+        hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bs_reads, nb);
+        hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bs_nts, nb);
+        if ((rc = launch_check(h, "k_extract_block / k_slot_top"))) return rc;
+        u64 got[4] = {0, 0, 0, 0};
+        HIPCHK(h, hipMemcpyAsync(got, d_flags, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 2, d_bs_reads + nb, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 3, d_bs_nts + nb, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (got[1]) return fail(h, BRISK_HIP_EINVAL, "extract_packed: read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (got[0] != ~0ull) return fail(h, BRISK_HIP_EINVAL, "extract_packed: the interval of read " + std::to_string(got[0]) + " ends beyond the read (start + len > its length)");
+        n_out = got[2];
+        n_nts = got[3];
+    }
+    *n_out_reads = n_out;
+    *n_out_nts = n_nts;
+    const u64 n_words = (n_nts + 15) / 16;
+    if (out.cap_words < n_words + 2)
+        return fail(h, BRISK_HIP_ECAPACITY, "extract_packed: " + std::to_string(n_nts) + " kept nucleotides need " + std::to_string(n_words + 2) + " words, out_cap_words is " + std::to_string(out.cap_words));
+    if (!n_out) {  // nothing kept: the empty stream
+        HIPCHK(h, hipMemsetAsync(out.starts, 0, 8, h->stream));
+        HIPCHK(h, hipMemsetAsync(out.packed, 0, 8, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    }
+    if ((rc = ensure(h, h->ext_src, n_out * 8))) return rc;
+    hipLaunchKernelGGL(k_extract_apply, dim3(nb), dim3(256), 0, h->stream, d_starts, d_iv, n_reads, (const u64*)d_bs_reads, (const u64*)d_bs_nts, out.starts, out.index,
+                       (u64*)h->ext_src.p);
+    if ((rc = launch_check(h, "k_extract_apply"))) return rc;
+    if (n_words + 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "extract_packed: more output words than one launch covers");
+    hipLaunchKernelGGL(k_extract_gather, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_packed, (const u64*)out.starts, (const u64*)h->ext_src.p, n_out, n_words, out.packed);
+    if ((rc = launch_check(h, "k_extract_gather"))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// ---- raw read intake: rule, passes, the host calls (clean_dna of counter.cpp:130-169 in bulk; kernels: brisk_intake.hip) ----
+static_assert(sizeof(brisk_hip_fragment) == 16 && sizeof(IntakeFragment) == 16 && offsetof(brisk_hip_fragment, start) == offsetof(IntakeFragment, start) &&
+                  offsetof(brisk_hip_fragment, len) == offsetof(IntakeFragment, len),
+              "the kernels write the C-ABI's fragment");
+static_assert(sizeof(brisk_hip_intake_rule) == 16 && sizeof(brisk_hip_intake_stats) == 64, "include/brisk_hip.h: 16 / 16 / 64 bytes");
+static_assert(BRISK_HIP_INTAKE_BLOCK == INTAKE_BLOCK, "the header names the kernels' block");
+
+// *min_len: the effective one, max(rule.min_len, k); *thr: 0 for no quality cut, else qual_base + min_qual
+int check_intake_rule(brisk_hip_index* h, const brisk_hip_intake_rule* rule, bool have_quals, const char* who, u32* min_len, u32* thr) {
+    if (!rule) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": null rule");
+    if (rule->struct_size < sizeof(brisk_hip_intake_rule)) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.struct_size is smaller than brisk_hip_intake_rule");
+    if (rule->min_qual > 93) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.min_qual " + std::to_string(rule->min_qual) + " is above 93");
+    if (rule->qual_base != 0 && rule->qual_base != 33 && rule->qual_base != 64) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.qual_base is " + std::to_string(rule->qual_base) + ", not 33 or 64");
+    if (rule->min_qual && !have_quals) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": rule.min_qual > 0 needs the qualities");
+    *min_len = std::max<u32>(rule->min_len, h->P.k);
+    *thr = rule->min_qual ? (rule->qual_base ? rule->qual_base : 33u) + rule->min_qual : 0u;
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held; the rule is checked.  The table is checked and the counts are taken first (two host synchronisations),
+// the fragment rows go to scratch (ink_tab: rows, then starts, then source positions), and only when the caller's room suffices
+// are they copied out and the stream gathered: a refused call writes nothing.  d_out_starts == NULL (the host calls): the rows stay
+// in scratch.  d_bases / d_quals are indexed by the table's offsets; neither is read outside [offsets[0], offsets[n_reads]).
+int intake_impl(brisk_hip_index* h, const uint8_t* d_bases, const uint8_t* d_quals, const u64* d_offsets, u64 n_reads, u32 min_len, u32 thr, u32* d_out, u64 cap_words,
+                u64* d_out_starts, IntakeFragment* d_out_frags, u64 frag_cap, brisk_hip_intake_stats* st) {
+    int rc;
+    memset(st, 0, sizeof(*st));
+    st->n_reads = n_reads;
+    // (k >= 5 on every handle that create accepts; the gather's LDS stage is sized by this bound)
+    if (min_len < INTAKE_MIN_LEN) return fail(h, BRISK_HIP_EUNSUPPORTED, "intake: fragments of fewer than " + std::to_string(INTAKE_MIN_LEN) + " nucleotides");
+    u64 lo = 0, hi = 0, a0 = 0, n_lanes = 0;
+    u32 nb = 0;
+    u64 *d_carry = nullptr, *d_first = nullptr;
+    if (n_reads) {
+        if ((rc = ensure(h, h->ink_tmp, 64))) return rc;
+        unsigned long long* d_flags = (unsigned long long*)h->ink_tmp.p;
+        HIPCHK(h, hipMemsetAsync(d_flags, 0, 8, h->stream));
+        if (n_reads > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "intake: more reads than one launch covers");
+        hipLaunchKernelGGL(k_intake_check, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_offsets, n_reads, d_flags);
+        if ((rc = launch_check(h, "k_intake_check"))) return rc;
+        u64 got[3] = {0, 0, 0};
+        HIPCHK(h, hipMemcpyAsync(got, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 1, d_offsets, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 2, d_offsets + n_reads, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (got[0] & 1) return fail(h, BRISK_HIP_EINVAL, "intake: read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (got[0] & 2) return fail(h, BRISK_HIP_EINVAL, "intake: a read of 2^32 bytes or more does not fit the fragment record");
+        lo = got[1];
+        hi = got[2];
+        st->n_bases_in = hi - lo;
+    }
+    if (hi > lo) {
+        a0 = lo - ((uintptr_t)(d_bases + lo) & 15);  // (may wrap below zero: positions are taken relative to it, modulo 2^64)
+        const u64 lo_x = lo - a0, hi_x = hi - a0;
+        const u64 nb64 = (hi_x + INTAKE_BLOCK - 1) / INTAKE_BLOCK;
+        if (nb64 > 0x7fffffffull) return fail(h, BRISK_HIP_EINVAL, "intake: more input blocks than one launch covers");
+        nb = (u32)nb64;
+        n_lanes = nb64 * 256;
+        if ((rc = ensure(h, h->ink_mask, n_lanes * 4))) return rc;
+        // [64 bytes of flags][the blocks' run begins, nb + 1][block sums: cut bases, cut qualities, fragments, nucleotides, short, nb + 1 each]
+        // [the partials of the two-level scans, nb2 + 1 for each of the six]
+        const u32 nb2 = nblocks(nb, INTAKE_SCAN);
+        // [per block, nb + 1: the first read that starts in or behind it]
+        if ((rc = ensure(h, h->ink_tmp, 64 + 7 * ((size_t)nb + 1) * 8 + 6 * ((size_t)nb2 + 1) * 8))) return rc;
+        d_carry = (u64*)((char*)h->ink_tmp.p + 64);
+        u64 *d_bs[5], *d_part[6];
+        for (int i = 0; i < 5; i++) d_bs[i] = d_carry + (size_t)(i + 1) * (nb + 1);
+        for (int i = 0; i < 6; i++) d_part[i] = d_carry + (size_t)6 * (nb + 1) + (size_t)i * (nb2 + 1);
+        d_first = d_carry + (size_t)6 * (nb + 1) + (size_t)6 * (nb2 + 1);
+        HIPCHK(h, hipMemsetAsync(h->ink_mask.p, 0, n_lanes * 4, h->stream));
+        {
+            ProfScope ps(h, S_INTAKE);
+            hipLaunchKernelGGL(k_intake_bounds, dim3(nblocks(n_reads + 1, 256)), dim3(256), 0, h->stream, d_offsets, n_reads, a0, n_lanes, (u32*)h->ink_mask.p);
+            hipLaunchKernelGGL(k_intake_first, dim3(nblocks((u64)nb + 1, 256)), dim3(256), 0, h->stream, d_offsets, n_reads, a0, (u64)nb, d_first);
+            hipLaunchKernelGGL(k_intake_mask, dim3(nb), dim3(256), 0, h->stream, d_bases, d_quals, a0, lo_x, hi_x, thr, (u32*)h->ink_mask.p, d_carry, d_bs[0], d_bs[1]);
+            hipLaunchKernelGGL(k_intake_reduce<true>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_carry, nb, d_part[5]);
+            hipLaunchKernelGGL(k_intake_top, dim3(1), dim3(1024), 0, h->stream, d_part[5], nb2);
+            hipLaunchKernelGGL(k_intake_spread<true>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, d_carry, nb, (const u64*)d_part[5]);
+            hipLaunchKernelGGL(k_intake_count, dim3(nb), dim3(256), 0, h->stream, (const u32*)h->ink_mask.p, n_lanes, (const u64*)d_carry, min_len, d_bs[2], d_bs[3], d_bs[4]);
+            for (int i = 0; i < 5; i++) {  // the totals of all five; the exclusive prefixes of the fragments and their nucleotides, which the apply pass takes
+                hipLaunchKernelGGL(k_intake_reduce<false>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_bs[i], nb, d_part[i]);
+                hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_part[i], nb2);
+                if (i == 2 || i == 3) hipLaunchKernelGGL(k_intake_spread<false>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, d_bs[i], nb, (const u64*)d_part[i]);
+            }
+            if ((rc = launch_check(h, "k_intake_bounds / k_intake_first / k_intake_mask / k_intake_reduce / k_intake_top / k_intake_spread / k_intake_count / k_slot_top"))) return rc;
+        }
+        u64 tot[5] = {0, 0, 0, 0, 0};
+        for (int i = 0; i < 5; i++) HIPCHK(h, hipMemcpyAsync(tot + i, d_part[i] + nb2, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        st->n_cut_base = tot[0];
+        st->n_cut_qual = tot[1];
+        st->n_fragments = tot[2];
+        st->n_nts = tot[3];
+        st->n_short = tot[4];
+    }
+    const u64 n_frag = st->n_fragments, n_words = (st->n_nts + 15) / 16;
+    IntakeFragment* d_rows = nullptr;
+    u64 *d_starts = nullptr, *d_src = nullptr;
+    if (n_frag) {
+        const u32 nbk = nblocks(n_frag, 256);
+        const u32 nbk2 = nblocks(nbk, INTAKE_SCAN);
+        if ((rc = ensure(h, h->ink_tab, n_frag * 16 + (n_frag + 1) * 8 + n_frag * 8 + ((size_t)nbk + 1) * 8 + ((size_t)nbk2 + 1) * 8))) return rc;
+        d_rows = (IntakeFragment*)h->ink_tab.p;
+        d_starts = (u64*)(d_rows + n_frag);
+        d_src = d_starts + n_frag + 1;
+        u64* d_kept = d_src + n_frag;
+        const u64* d_bs_frag = d_carry + (size_t)3 * (nb + 1);
+        const u64* d_bs_nts = d_carry + (size_t)4 * (nb + 1);
+        {
+            ProfScope ps(h, S_INTAKE);
+            hipLaunchKernelGGL(k_intake_apply, dim3(nb), dim3(256), 0, h->stream, (const u32*)h->ink_mask.p, n_lanes, (const u64*)d_carry, min_len, d_bs_frag, d_bs_nts, d_offsets, n_reads, a0,
+                               (const u64*)d_first, d_rows, d_starts, d_src);
+            hipLaunchKernelGGL(k_intake_kept, dim3(nbk), dim3(256), 0, h->stream, (const IntakeFragment*)d_rows, n_frag, d_kept);
+            u64* d_kept2 = d_kept + nbk + 1;
+            hipLaunchKernelGGL(k_intake_reduce<false>, dim3(nbk2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_kept, nbk, d_kept2);
+            hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_kept2, nbk2);
+            if ((rc = launch_check(h, "k_intake_apply / k_intake_kept / k_intake_reduce / k_slot_top"))) return rc;
+        }
+        HIPCHK(h, hipMemcpyAsync(&st->n_reads_kept, d_kept + nbk + 1 + nbk2, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (frag_cap < n_frag)
+        return fail(h, BRISK_HIP_ECAPACITY, "intake: " + std::to_string(n_frag) + " fragments, frag_cap is " + std::to_string(frag_cap));
+    if (d_out && cap_words < n_words + 2)
+        return fail(h, BRISK_HIP_ECAPACITY, "intake: " + std::to_string(st->n_nts) + " nucleotides need " + std::to_string(n_words + 2) + " words, out_cap_words is " + std::to_string(cap_words));
+    if (!n_frag) {  // no fragment: the empty stream
+        if (d_out_starts) HIPCHK(h, hipMemsetAsync(d_out_starts, 0, 8, h->stream));
+        if (d_out) HIPCHK(h, hipMemsetAsync(d_out, 0, 8, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    }
+    if (d_out_starts) HIPCHK(h, hipMemcpyAsync(d_out_starts, d_starts, (n_frag + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (d_out_frags) HIPCHK(h, hipMemcpyAsync(d_out_frags, d_rows, n_frag * 16, hipMemcpyDeviceToDevice, h->stream));
+    if (d_out) {
+        if (n_words + 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "intake: more output words than one launch covers");
+        ProfScope ps(h, S_INTAKE);
+        hipLaunchKernelGGL(k_intake_gather, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_bases, hi, (const u64*)d_starts, (const u64*)d_src, n_frag, n_words, d_out);
+        if ((rc = launch_check(h, "k_intake_gather"))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// host reads -> the device, as they are, in pieces of whole reads (at least one) of about h->intake_piece bytes; body(r0, nr, d_bases,
+// d_quals, d_offsets): the piece's table holds the caller's offsets, and the two pointers are displaced so that those index them;
+// group: a piece holds a multiple of so many reads
+template <class F>
+int for_each_raw_piece(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, F&& body, u64 group = 1) {
+    for (u64 r0 = 0; r0 < n_reads;) {
+        const u64 r_hi = std::min<u64>(n_reads, r0 + (1ull << 26));
+        u64 r1 = (u64)(std::upper_bound(offsets + r0, offsets + r_hi + 1, offsets[r0] + h->intake_piece) - offsets) - 1;
+        if (group > 1) r1 = r0 + (r1 - r0) / group * group;  // (the pairs calls: whole pairs, n_reads a multiple of group)
+        if (r1 <= r0) r1 = std::min<u64>(n_reads, r0 + group);
+        const u64 nb = offsets[r1] - offsets[r0], nr = r1 - r0, pad = (nb + 15) & ~15ull;
+        int rc;
+        if ((rc = ensure(h, h->ink_raw, (quals ? 2 : 1) * pad + 16))) return rc;
+        if ((rc = ensure(h, h->ink_offs, (nr + 1) * 8))) return rc;
+        uint8_t* d_b = (uint8_t*)h->ink_raw.p;
+        uint8_t* d_q = quals ? d_b + pad : nullptr;
+        if (nb) {
+            HIPCHK(h, hipMemcpyAsync(d_b, bases + offsets[r0], nb, hipMemcpyHostToDevice, h->stream));
+            if (quals) HIPCHK(h, hipMemcpyAsync(d_q, quals + offsets[r0], nb, hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCHK(h, hipMemcpyAsync(h->ink_offs.p, offsets + r0, (nr + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        if ((rc = body(r0, nr, (const uint8_t*)(d_b - offsets[r0]), quals ? (const uint8_t*)(d_q - offsets[r0]) : nullptr, (const u64*)h->ink_offs.p))) return rc;
+        r0 = r1;
+    }
+    return BRISK_HIP_OK;
+}
+
+int check_raw_reads(brisk_hip_index* h, const uint64_t* offsets, uint64_t n_reads, const char* who) {
+    for (u64 r = 0; r < n_reads; r++) {
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (offsets[r + 1] - offsets[r] > 0xffffffffull) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": a read of 2^32 bytes or more does not fit the fragment record");
+    }
+    return BRISK_HIP_OK;
+}
+// *sum += x, field by field: brisk_hip_intake_stats and brisk_hip_pair_counts are 64-bit counters throughout
+template <class T>
+void add_counters(T* sum, const T& x) {
+    static_assert(sizeof(T) % 8 == 0 && alignof(T) == 8, "a struct of 64-bit counters");
+    uint64_t* a = (uint64_t*)sum;
+    const uint64_t* b = (const uint64_t*)&x;
+    for (size_t i = 0; i < sizeof(T) / 8; i++) a[i] += b[i];
+}
+
+// ---- paired-end reads: the pair decision over intervals, pairs and singles as two streams (no reference counterpart; khmer's
+// extract-paired-reads and Trimmomatic's paired mode are the usual tools; kernels: brisk_pairs.hip).  Beside read extraction in
+// purpose; behind the intake calls because the clean_pairs calls are built from both. ----
+static_assert(sizeof(brisk_hip_pair_counts) == 64 && offsetof(brisk_hip_pair_counts, n_nts_pairs) == 40, "include/brisk_hip.h: eight 64-bit counters");
+static_assert(BRISK_HIP_PAIR_EACH == PAIR_EACH && BRISK_HIP_PAIR_ALL == PAIR_ALL && BRISK_HIP_PAIR_ANY == PAIR_ANY, "the kernel's modes are the header's");
+
+// h->pair_tab: [PAIR_CTR_ROWS rows of 64 bytes: k_pair_split's six counters, summed here][64 bytes: two flags][the intervals of intact pairs,
+// n_reads][those of singles, n_reads]
+constexpr size_t kPairCtrBytes = (size_t)PAIR_CTR_ROWS * 64, kPairHeadBytes = kPairCtrBytes + 64;
+unsigned long long* pair_flags(brisk_hip_index* h) { return (unsigned long long*)((char*)h->pair_tab.p + kPairCtrBytes); }
+
+int check_pairs(brisk_hip_index* h, u64 n_reads, u32 pair_mode, const char* who) {
+    if (n_reads & 1) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": n_reads " + std::to_string(n_reads) + " is odd (an interleaved stream holds whole pairs)");
+    if (pair_mode > BRISK_HIP_PAIR_ANY) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": unknown pair_mode " + std::to_string(pair_mode));
+    if (n_reads / 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": more pairs than one launch covers");
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held.  The table is checked first (a host synchronisation): a refused call writes nothing.
+int fragment_intervals_impl(brisk_hip_index* h, const IntakeFragment* d_frags, u64 n_frags, u64 n_reads, ReadInterval* d_iv) {
+    int rc;
+    if (n_reads > 0x7fffffffull * 256 || n_frags > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "fragment_intervals: more rows than one launch covers");
+    if (n_frags) {
+        if ((rc = ensure(h, h->pair_tab, kPairHeadBytes))) return rc;
+        unsigned long long* d_flags = pair_flags(h);
+        HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 8, h->stream));
+        hipLaunchKernelGGL(k_fragment_check, dim3(nblocks(n_frags, 256)), dim3(256), 0, h->stream, d_frags, n_frags, n_reads, d_flags);
+        if ((rc = launch_check(h, "k_fragment_check"))) return rc;
+        u64 bad = 0;
+        HIPCHK(h, hipMemcpyAsync(&bad, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (bad != ~0ull)
+            return fail(h, BRISK_HIP_EINVAL, "fragment_intervals: row " + std::to_string(bad) + " of the fragment table names a read >= n_reads or stands before the row ahead of it (by read, then by position)");
+    }
+    if (!n_reads) return BRISK_HIP_OK;
+    hipLaunchKernelGGL(k_fragment_intervals, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_frags, n_frags, n_reads, d_iv);
+    return launch_check(h, "k_fragment_intervals");
+}
+
+// the handle's lock is held; n_reads and the mode are checked
+int pair_intervals_impl(brisk_hip_index* h, const ReadInterval* d_each, const ReadInterval* d_whole, u64 n_reads, u32 pair_mode, ReadInterval* d_out) {
+    if (!n_reads) return BRISK_HIP_OK;
+    hipLaunchKernelGGL(k_pair_intervals, dim3(nblocks(n_reads / 2, 256)), dim3(256), 0, h->stream, d_each, d_whole, n_reads / 2, pair_mode, d_out);
+    return launch_check(h, "k_pair_intervals");
+}
+
+// The handle's lock is held.  The inputs are checked first (a host synchronisation): a refused call writes nothing.
+int compose_impl(brisk_hip_index* h, const ReadInterval* d_outer, u64 n_reads, const ReadInterval* d_inner, const u64* d_index, u64 n_kept, ReadInterval* d_out) {
+    int rc;
+    if (n_reads > 0x7fffffffull * 256 || n_kept > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "compose_intervals: more rows than one launch covers");
+    if (n_kept) {
+        if ((rc = ensure(h, h->pair_tab, kPairHeadBytes))) return rc;
+        unsigned long long* d_flags = pair_flags(h);
+        HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 16, h->stream));
+        hipLaunchKernelGGL(k_compose_check, dim3(nblocks(n_kept, 256)), dim3(256), 0, h->stream, d_outer, n_reads, d_inner, d_index, n_kept, d_flags);
+        if ((rc = launch_check(h, "k_compose_check"))) return rc;
+        u64 got[2] = {0, 0};
+        HIPCHK(h, hipMemcpyAsync(got, d_flags, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (got[1] != ~0ull) return fail(h, BRISK_HIP_EINVAL, "compose_intervals: d_index does not ascend at row " + std::to_string(got[1]));  // (first: the rows of an index out of order pair the wrong intervals)
+        if (got[0] != ~0ull)
+            return fail(h, BRISK_HIP_EINVAL, "compose_intervals: row " + std::to_string(got[0]) + ": the inner interval leaves the outer one (start + len > outer.len), or d_index names a read >= n_reads");
+    }
+    if (!n_reads) return BRISK_HIP_OK;
+    hipLaunchKernelGGL(k_compose_intervals, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_outer, n_reads, d_inner, d_index, n_kept, d_out);
+    return launch_check(h, "k_compose_intervals");
+}
+
+// The handle's lock is held; n_reads is even.  The two masked tables into h->pair_tab, *counts filled.  d_starts (may be NULL: the
+// intervals are then taken as they are): EINVAL where brisk_hip_extract_packed gives it, before anything is extracted.
+int pair_split_impl(brisk_hip_index* h, const ReadInterval* d_iv, u64 n_reads, const u64* d_starts, brisk_hip_pair_counts* counts, const ReadInterval** iv_pairs,
+                    const ReadInterval** iv_singles) {
+    int rc;
+    memset(counts, 0, sizeof(*counts));
+    counts->n_pairs_in = n_reads / 2;
+    *iv_pairs = *iv_singles = nullptr;
+    if (!n_reads) return BRISK_HIP_OK;
+    if ((rc = ensure(h, h->pair_tab, kPairHeadBytes + 2 * n_reads * sizeof(ReadInterval)))) return rc;
+    unsigned long long* d_ctr = (unsigned long long*)h->pair_tab.p;
+    unsigned long long* d_flags = pair_flags(h);
+    ReadInterval* d_p = (ReadInterval*)((char*)h->pair_tab.p + kPairHeadBytes);
+    ReadInterval* d_s = d_p + n_reads;
+    HIPCHK(h, hipMemsetAsync(d_ctr, 0, kPairHeadBytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 8, h->stream));
+    hipLaunchKernelGGL(k_pair_split, dim3(nblocks(n_reads / 2, 256 * PAIR_ITEMS)), dim3(256), 0, h->stream, d_iv, n_reads / 2, d_starts, d_p, d_s, d_ctr, d_flags);
+    if ((rc = launch_check(h, "k_pair_split"))) return rc;
+    std::vector<u64> rows(kPairHeadBytes / 8);
+    HIPCHK(h, hipMemcpyAsync(rows.data(), d_ctr, kPairHeadBytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    u64 got[8] = {0, 0, 0, 0, 0, 0, rows[kPairCtrBytes / 8], rows[kPairCtrBytes / 8 + 1]};
+    for (size_t r = 0; r < PAIR_CTR_ROWS; r++)
+        for (int i = 0; i < 6; i++) got[i] += rows[r * 8 + i];
+    if (got[7]) return fail(h, BRISK_HIP_EINVAL, "extract_pairs_packed: read offsets do not ascend (offsets[i + 1] < offsets[i])");
+    if (got[6] != ~0ull) return fail(h, BRISK_HIP_EINVAL, "extract_pairs_packed: the interval of read " + std::to_string(got[6]) + " ends beyond the read (start + len > its length)");
+    counts->n_pairs_kept = got[0];
+    counts->n_single_first = got[1];
+    counts->n_single_second = got[2];
+    counts->n_pairs_dropped = got[3];
+    counts->n_nts_pairs = got[4];
+    counts->n_nts_singles = got[5];
+    *iv_pairs = d_p;
+    *iv_singles = d_s;
+    return BRISK_HIP_OK;
+}
+
+int check_pair_outs(brisk_hip_index* h, const OutStream& P, const OutStream& S, const brisk_hip_pair_counts* counts, const char* who) {
+    if (!counts || !P.packed || !P.starts) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": null pointer");
+    if (!S.packed || !S.starts) {
+        if (S.packed || S.starts || S.index || S.cap_words) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": the singles output is given in part (all four NULL / 0 drops the singles)");
+    }
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held; the arguments are checked.  Split and count (one pass, a host synchronisation), refuse before either
+// stream is written, then brisk_hip_extract_packed's own block / apply / gather passes over each masked table.
+int extract_pairs_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, const ReadInterval* d_iv, const OutStream& P, const OutStream& S,
+                       brisk_hip_pair_counts* counts) {
+    int rc;
+    const ReadInterval *iv_p = nullptr, *iv_s = nullptr;
+    if ((rc = pair_split_impl(h, d_iv, n_reads, d_starts, counts, &iv_p, &iv_s))) return rc;
+    const u64 need_p = (counts->n_nts_pairs + 15) / 16 + 2, need_s = (counts->n_nts_singles + 15) / 16 + 2;
+    if (P.cap_words < need_p)
+        return fail(h, BRISK_HIP_ECAPACITY, "extract_pairs_packed: " + std::to_string(counts->n_nts_pairs) + " nucleotides of pairs need " + std::to_string(need_p) + " words, the pairs output holds " + std::to_string(P.cap_words));
+    if (S.packed && S.cap_words < need_s)
+        return fail(h, BRISK_HIP_ECAPACITY, "extract_pairs_packed: " + std::to_string(counts->n_nts_singles) + " nucleotides of singles need " + std::to_string(need_s) + " words, the singles output holds " + std::to_string(S.cap_words));
+    u64 n_out = 0, n_nts = 0;
+    if ((rc = extract_impl(h, d_packed, d_starts, n_reads, iv_p, P, &n_out, &n_nts))) return rc;
+    if (n_out != 2 * counts->n_pairs_kept || n_nts != counts->n_nts_pairs) return fail(h, BRISK_HIP_EHIP, "extract_pairs_packed: the pairs stream and the pair counts disagree");
+    if (!S.packed) return BRISK_HIP_OK;
+    if ((rc = extract_impl(h, d_packed, d_starts, n_reads, iv_s, S, &n_out, &n_nts))) return rc;
+    if (n_out != counts->n_single_first + counts->n_single_second || n_nts != counts->n_nts_singles) return fail(h, BRISK_HIP_EHIP, "extract_pairs_packed: the singles stream and the pair counts disagree");
+    return BRISK_HIP_OK;
+}
+
+// A batch's records through the rule into d_each, and (d_whole given) through the rule that keeps a read whole, subject to the same
+// minimum length: what BRISK_HIP_PAIR_ANY restores.
+int select_batch(brisk_hip_index* h, const ReadProfile* d_prof, u64 n_reads, const brisk_hip_select_rule* rule, ReadInterval* d_each, ReadInterval* d_whole) {
+    if (int rc = select_impl(h, d_prof, n_reads, rule, d_each)) return rc;
+    if (!d_whole) return BRISK_HIP_OK;
+    const brisk_hip_select_rule whole = {sizeof(whole), BRISK_HIP_SELECT_MEDIAN, rule->min_len, 0, 0xffffffffu};  // (a median is at most 255: every read with a k-mer passes)
+    return select_impl(h, d_prof, n_reads, &whole, d_whole);
+}
+
+// The handle's lock is held, pending inserts are completed.  d_each[0 .. n_reads): the rule over the profiles of a packed stream, as
+// brisk_hip_trim_packed computes them (profile_packed_batches, every batch into prof_out); d_whole (may be NULL): the same reads kept whole.
+int profile_select(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, u32 solid_min, const brisk_hip_select_rule* rule, ReadInterval* d_each,
+                   ReadInterval* d_whole) {
+    if (!n_reads) return BRISK_HIP_OK;
+    if (int rc = ensure(h, h->prof_out, std::min<u64>(profile_batch_limit(h), n_reads) * sizeof(ReadProfile))) return rc;
+    int rc = profile_packed_batches(h, d_packed, d_starts, n_reads, solid_min, [&](u64) { return (ReadProfile*)h->prof_out.p; },
+                                    [&](u64 r0, u64 nb, const ReadProfile* d_prof) { return select_batch(h, d_prof, nb, rule, d_each + r0, d_whole ? d_whole + r0 : nullptr); });
+    return rc ? rc : check_device_flags(h);
+}
+
+// The handle's lock is held; the rules and n_reads are checked; with a select rule pending inserts are completed.  Raw reads on the
+// device -> *stats, and (n_reads > 0) out->intervals: one interval per raw read after the pair decision; out->raw / out->raw_starts: the raw
+// bytes as a packed stream whose read table begins at 0 (scratch of the handle, all three).
+struct CleanedPairs {
+    const ReadInterval* intervals = nullptr;
+    const u32* raw = nullptr;
+    const u64* raw_starts = nullptr;
+};
+int clean_pairs_core(brisk_hip_index* h, const uint8_t* d_bases, const uint8_t* d_quals, const u64* d_offsets, u64 n_reads, u32 min_len, u32 thr,
+                     const brisk_hip_select_rule* select, u32 solid_min, u32 pair_mode, brisk_hip_intake_stats* stats, CleanedPairs* out) {
+    int rc;
+    *out = CleanedPairs();
+    if ((rc = intake_impl(h, d_bases, d_quals, d_offsets, n_reads, min_len, thr, nullptr, 0, nullptr, nullptr, ~0ull, stats))) return rc;  // the table only: its rows stay in ink_tab
+    if (!n_reads) return BRISK_HIP_OK;
+    if ((rc = ensure(h, h->pair_iv, 2 * n_reads * sizeof(ReadInterval)))) return rc;
+    ReadInterval* d_iv1 = (ReadInterval*)h->pair_iv.p;
+    ReadInterval* d_each = d_iv1 + n_reads;
+    if ((rc = fragment_intervals_impl(h, (const IntakeFragment*)h->ink_tab.p, stats->n_fragments, n_reads, d_iv1))) return rc;
+    // the raw bytes, packed: a byte that is no base packs to some code, and lies in no fragment
+    u64 lo = 0;
+    HIPCHK(h, hipMemcpyAsync(&lo, d_offsets, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 n_bytes = stats->n_bases_in, n_words = (n_bytes + 15) / 16, words_room = (n_words + 3) & ~1ull;
+    if ((rc = ensure(h, h->pair_raw, words_room * 4 + (n_reads + 1) * 8))) return rc;
+    u32* d_packed = (u32*)h->pair_raw.p;
+    u64* d_starts = (u64*)(d_packed + words_room);
+    HIPCHK(h, hipMemsetAsync(d_packed + n_words, 0, 8, h->stream));
+    if (n_words) {
+        if (n_words > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "clean_pairs: more input words than one launch covers");
+        ProfScope ps(h, S_PACK);
+        hipLaunchKernelGGL(k_pack_ascii, dim3(nblocks(n_words, 256)), dim3(256), 0, h->stream, d_bases + lo, n_bytes, d_packed, n_words);
+    }
+    hipLaunchKernelGGL(k_rebase_starts, dim3(nblocks(n_reads + 1, 256)), dim3(256), 0, h->stream, d_offsets, n_reads + 1, lo, d_starts);
+    if ((rc = launch_check(h, "k_pack_ascii / k_rebase_starts"))) return rc;
+    const ReadInterval* d_judged = d_iv1;
+    if (select) {
+        // the first longest fragment of every read as a stream of its own, its profile, the rule, and the cut back in the raw read's frame
+        if ((rc = ensure(h, h->pair_fs, words_room * 4 + (n_reads + 1) * 8 + n_reads * 8))) return rc;
+        u32* d_fs = (u32*)h->pair_fs.p;
+        u64* d_fs_starts = (u64*)(d_fs + words_room);
+        u64* d_fs_index = d_fs_starts + n_reads + 1;
+        u64 n_kept = 0, n_nts = 0;
+        if ((rc = extract_impl(h, d_packed, d_starts, n_reads, d_iv1, {d_fs, n_words + 2, d_fs_starts, d_fs_index}, &n_kept, &n_nts))) return rc;
+        if ((rc = ensure(h, h->ext_iv, std::max<u64>(n_kept, 1) * sizeof(ReadInterval)))) return rc;
+        if ((rc = profile_select(h, d_fs, d_fs_starts, n_kept, solid_min, select, (ReadInterval*)h->ext_iv.p, nullptr))) return rc;
+        if ((rc = compose_impl(h, d_iv1, n_reads, (const ReadInterval*)h->ext_iv.p, d_fs_index, n_kept, d_each))) return rc;
+        d_judged = d_each;
+    }
+    if ((rc = pair_intervals_impl(h, d_judged, d_iv1, n_reads, pair_mode, d_each))) return rc;
+    *out = {d_each, d_packed, d_starts};
+    return BRISK_HIP_OK;
+}
+
+int check_clean_pairs(brisk_hip_index* h, const brisk_hip_intake_rule* intake, bool have_quals, const brisk_hip_select_rule* select, u64 n_reads, u32 pair_mode, const char* who,
+                      u32* min_len, u32* thr) {
+    if (int rrc = check_intake_rule(h, intake, have_quals, who, min_len, thr)) return rrc;
+    if (select) {
+        if (int wrc = need_whole_index(h, std::string(who) + " with a select rule")) return wrc;
+        if (int src = check_rule(h, select, who)) return src;
+    }
+    return check_pairs(h, n_reads, pair_mode, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- profiles ----
+BRISK_API int brisk_hip_read_profile_reads(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t solid_min,
+                                           brisk_hip_read_profile* out) {
+    if (!h || (n_reads && (!bases || !offsets || !out))) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "read_profile_reads")) return wrc;
+    if (int orc = check_profile_offsets(h, offsets, n_reads, "read_profile")) return orc;
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    return profile_host_batches(h, bases, offsets, n_reads, solid_min, [&](u64 r0, u64 nr, const ReadProfile* d_prof) -> int {
+        HIPCHK(h, hipMemcpyAsync(out + r0, d_prof, nr * sizeof(ReadProfile), hipMemcpyDeviceToHost, h->stream));
+        return BRISK_HIP_OK;
+    });
+}
+
+BRISK_API int brisk_hip_read_profile_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min,
+                                            brisk_hip_read_profile* d_out) {
+    if (!h || (n_reads && (!d_packed || !d_starts || !d_out))) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "read_profile_packed")) return wrc;
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    // (the records are the output: nothing follows a batch)
+    if (int rc = profile_packed_batches(h, d_packed, d_starts, n_reads, solid_min, [&](u64 r0) { return (ReadProfile*)d_out + r0; }, [](u64, u64, const ReadProfile*) { return BRISK_HIP_OK; })) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return check_device_flags(h);
+}
+
+// ---- select, extract, trim ----
+
+BRISK_API int brisk_hip_select_intervals(brisk_hip_index* h, const brisk_hip_read_profile* d_profiles, uint64_t n_reads, const brisk_hip_select_rule* rule,
+                                         brisk_hip_read_interval* d_intervals) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int rrc = check_rule(h, rule, "select_intervals")) return rrc;
+    if (n_reads && (!d_profiles || !d_intervals)) return fail(h, BRISK_HIP_EINVAL, "select_intervals: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int rc = select_impl(h, (const ReadProfile*)d_profiles, n_reads, rule, (ReadInterval*)d_intervals)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_extract_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, const brisk_hip_read_interval* d_intervals,
+                                       uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, uint64_t* d_out_index, uint64_t* n_out_reads,
+                                       uint64_t* n_out_nts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!n_out_reads || !n_out_nts || !d_out_packed || !d_out_starts || (n_reads && (!d_packed || !d_starts || !d_intervals))) return fail(h, BRISK_HIP_EINVAL, "extract_packed: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    return extract_impl(h, d_packed, d_starts, n_reads, (const ReadInterval*)d_intervals, {d_out_packed, out_cap_words, d_out_starts, d_out_index}, n_out_reads, n_out_nts);
+}
+
+BRISK_API int brisk_hip_trim_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, const brisk_hip_select_rule* rule,
+                                    uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, uint64_t* d_out_index, uint64_t* n_out_reads, uint64_t* n_out_nts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "trim_packed")) return wrc;
+    if (int rrc = check_rule(h, rule, "trim_packed")) return rrc;
+    if (!n_out_reads || !n_out_nts || !d_out_packed || !d_out_starts || (n_reads && (!d_packed || !d_starts))) return fail(h, BRISK_HIP_EINVAL, "trim_packed: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    int rc;
+    if (n_reads) {
+        if ((rc = ensure(h, h->ext_iv, n_reads * sizeof(ReadInterval)))) return rc;
+        if ((rc = profile_select(h, d_packed, d_starts, n_reads, solid_min, rule, (ReadInterval*)h->ext_iv.p, nullptr))) return rc;
+    }
+    return extract_impl(h, d_packed, d_starts, n_reads, (const ReadInterval*)h->ext_iv.p, {d_out_packed, out_cap_words, d_out_starts, d_out_index}, n_out_reads, n_out_nts);
+}
+
+BRISK_API int brisk_hip_trim_reads(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t solid_min, const brisk_hip_select_rule* rule,
+                                   brisk_hip_read_interval* out) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "trim_reads")) return wrc;
+    if (int rrc = check_rule(h, rule, "trim_reads")) return rrc;
+    if (n_reads && (!bases || !offsets || !out)) return fail(h, BRISK_HIP_EINVAL, "trim_reads: null pointer");
+    if (int orc = check_profile_offsets(h, offsets, n_reads, "trim_reads")) return orc;
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    return profile_host_batches(h, bases, offsets, n_reads, solid_min, [&](u64 r0, u64 nr, const ReadProfile* d_prof) -> int {
+        int rc;
+        if ((rc = ensure(h, h->ext_iv, nr * sizeof(ReadInterval)))) return rc;
+        if ((rc = select_impl(h, d_prof, nr, rule, (ReadInterval*)h->ext_iv.p))) return rc;
+        HIPCHK(h, hipMemcpyAsync(out + r0, h->ext_iv.p, nr * sizeof(ReadInterval), hipMemcpyDeviceToHost, h->stream));
+        return BRISK_HIP_OK;
+    });
+}
+
+// ---- intake ----
+BRISK_API int brisk_hip_intake_ascii(brisk_hip_index* h, const char* d_bases, const char* d_quals, const uint64_t* d_offsets, uint64_t n_reads, const brisk_hip_intake_rule* rule,
+                                     uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, brisk_hip_fragment* d_out_frags, uint64_t frag_cap,
+                                     brisk_hip_intake_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    u32 min_len = 0, thr = 0;
+    if (int rrc = check_intake_rule(h, rule, d_quals != nullptr, "intake_ascii", &min_len, &thr)) return rrc;
+    if (!stats || !d_out_starts || (n_reads && (!d_bases || !d_offsets))) return fail(h, BRISK_HIP_EINVAL, "intake_ascii: null pointer");
+    if (!d_out_packed && out_cap_words) return fail(h, BRISK_HIP_EINVAL, "intake_ascii: out_cap_words without d_out_packed");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    return intake_impl(h, (const uint8_t*)d_bases, (const uint8_t*)d_quals, d_offsets, n_reads, min_len, thr, d_out_packed, out_cap_words, d_out_starts, (IntakeFragment*)d_out_frags,
+                       frag_cap, stats);
+}
+
+BRISK_API int brisk_hip_intake_reads(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, const brisk_hip_intake_rule* rule,
+                                     brisk_hip_fragment* out_frags, uint64_t frag_cap, brisk_hip_intake_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    u32 min_len = 0, thr = 0;
+    if (int rrc = check_intake_rule(h, rule, quals != nullptr, "intake_reads", &min_len, &thr)) return rrc;
+    if (!stats || (frag_cap && !out_frags) || (n_reads && (!bases || !offsets))) return fail(h, BRISK_HIP_EINVAL, "intake_reads: null pointer");
+    if (int orc = check_raw_reads(h, offsets, n_reads, "intake_reads")) return orc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    memset(stats, 0, sizeof(*stats));
+    int rc = for_each_raw_piece(h, bases, thr ? quals : nullptr, offsets, n_reads, [&](u64 r0, u64 nr, const uint8_t* d_b, const uint8_t* d_q, const u64* d_offs) -> int {
+        brisk_hip_intake_stats st;
+        if (int rc2 = intake_impl(h, d_b, d_q, d_offs, nr, min_len, thr, nullptr, 0, nullptr, nullptr, ~0ull, &st)) return rc2;
+        const u64 at = stats->n_fragments;
+        if (st.n_fragments && at + st.n_fragments <= frag_cap) {  // (past the caller's room the pieces are still counted: the stats are whole)
+            HIPCHK(h, hipMemcpyAsync(out_frags + at, h->ink_tab.p, st.n_fragments * 16, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            for (u64 j = 0; j < st.n_fragments; j++) out_frags[at + j].read += r0;  // the device counted the piece's reads
+        }
+        add_counters(stats, st);
+        return BRISK_HIP_OK;
+    });
+    if (rc) return rc;
+    if (stats->n_fragments > frag_cap) return fail(h, BRISK_HIP_ECAPACITY, "intake_reads: " + std::to_string(stats->n_fragments) + " fragments, frag_cap is " + std::to_string(frag_cap));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_insert_raw_reads(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, const brisk_hip_intake_rule* rule,
+                                         brisk_hip_intake_stats* stats) {
+    if (!h || (n_reads && (!bases || !offsets))) return BRISK_HIP_EINVAL;
+    if (h->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "insert_reads on a sharded index: use scan/route/insert_records");
+    if (h->entry_ids) return fail(h, BRISK_HIP_EINVAL, "bulk count on an entry-id index");
+    u32 min_len = 0, thr = 0;
+    if (int rrc = check_intake_rule(h, rule, quals != nullptr, "insert_raw_reads", &min_len, &thr)) return rrc;
+    if (int orc = check_raw_reads(h, offsets, n_reads, "insert_raw_reads")) return orc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    brisk_hip_intake_stats sum = {};
+    if (stats) *stats = sum;
+    int rc = for_each_raw_piece(h, bases, thr ? quals : nullptr, offsets, n_reads, [&](u64 r0, u64 nr, const uint8_t* d_b, const uint8_t* d_q, const u64* d_offs) -> int {
+        // the piece's packed stream and its starts: what always suffices (include/brisk_hip.h)
+        const u64 nb = offsets[r0 + nr] - offsets[r0], cap_words = (nb + 15) / 16 + 2, cap_frag = nb / min_len, words_room = (cap_words + 1) & ~1ull;
+        if (int rc2 = ensure(h, h->ink_packed, words_room * 4 + (cap_frag + 1) * 8)) return rc2;
+        u32* d_packed = (u32*)h->ink_packed.p;
+        u64* d_starts = (u64*)(d_packed + words_room);
+        brisk_hip_intake_stats st;
+        if (int rc2 = intake_impl(h, d_b, d_q, d_offs, nr, min_len, thr, d_packed, cap_words, d_starts, nullptr, cap_frag, &st)) return rc2;
+        add_counters(&sum, st);
+        // the scan of this stream is queued before insert_packed_impl returns (a deferred insert keeps records, not the stream), and the
+        // next piece's writes follow it on the handle's stream: the scratch is free for them
+        return insert_packed_impl(h, d_packed, d_starts, st.n_fragments);
+    });
+    if (stats) *stats = sum;
+    return rc;
+}
+
+// ---- paired-end reads ----
+BRISK_API int brisk_hip_fragment_intervals(brisk_hip_index* h, const brisk_hip_fragment* d_frags, uint64_t n_frags, uint64_t n_reads, brisk_hip_read_interval* d_intervals) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if ((n_frags && !d_frags) || (n_reads && !d_intervals)) return fail(h, BRISK_HIP_EINVAL, "fragment_intervals: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int rc = fragment_intervals_impl(h, (const IntakeFragment*)d_frags, n_frags, n_reads, (ReadInterval*)d_intervals)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_pair_intervals(brisk_hip_index* h, const brisk_hip_read_interval* d_each, const brisk_hip_read_interval* d_whole, uint64_t n_reads, uint32_t pair_mode,
+                                       brisk_hip_read_interval* d_out) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int crc = check_pairs(h, n_reads, pair_mode, "pair_intervals")) return crc;
+    if (pair_mode == BRISK_HIP_PAIR_ANY && !d_whole) return fail(h, BRISK_HIP_EINVAL, "pair_intervals: BRISK_HIP_PAIR_ANY needs d_whole");
+    if (n_reads && (!d_each || !d_out)) return fail(h, BRISK_HIP_EINVAL, "pair_intervals: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int rc = pair_intervals_impl(h, (const ReadInterval*)d_each, (const ReadInterval*)d_whole, n_reads, pair_mode, (ReadInterval*)d_out)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_compose_intervals(brisk_hip_index* h, const brisk_hip_read_interval* d_outer, uint64_t n_reads, const brisk_hip_read_interval* d_inner, const uint64_t* d_index,
+                                          uint64_t n_kept, brisk_hip_read_interval* d_out) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if ((n_reads && !d_out) || (n_kept && (!d_outer || !d_inner || !d_index))) return fail(h, BRISK_HIP_EINVAL, "compose_intervals: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int rc = compose_impl(h, (const ReadInterval*)d_outer, n_reads, (const ReadInterval*)d_inner, d_index, n_kept, (ReadInterval*)d_out)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_extract_pairs_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, const brisk_hip_read_interval* d_intervals,
+                                             uint32_t* d_pairs_packed, uint64_t pairs_cap_words, uint64_t* d_pairs_starts, uint64_t* d_pairs_index, uint32_t* d_singles_packed,
+                                             uint64_t singles_cap_words, uint64_t* d_singles_starts, uint64_t* d_singles_index, brisk_hip_pair_counts* counts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    const OutStream P = {d_pairs_packed, pairs_cap_words, d_pairs_starts, d_pairs_index}, S = {d_singles_packed, singles_cap_words, d_singles_starts, d_singles_index};
+    if (int orc = check_pair_outs(h, P, S, counts, "extract_pairs_packed")) return orc;
+    if (n_reads && (!d_packed || !d_starts || !d_intervals)) return fail(h, BRISK_HIP_EINVAL, "extract_pairs_packed: null pointer");
+    if (int crc = check_pairs(h, n_reads, BRISK_HIP_PAIR_EACH, "extract_pairs_packed")) return crc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    return extract_pairs_impl(h, d_packed, d_starts, n_reads, (const ReadInterval*)d_intervals, P, S, counts);
+}
+
+BRISK_API int brisk_hip_trim_pairs_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, const brisk_hip_select_rule* rule,
+                                          uint32_t pair_mode, uint32_t* d_pairs_packed, uint64_t pairs_cap_words, uint64_t* d_pairs_starts, uint64_t* d_pairs_index,
+                                          uint32_t* d_singles_packed, uint64_t singles_cap_words, uint64_t* d_singles_starts, uint64_t* d_singles_index, brisk_hip_pair_counts* counts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "trim_pairs_packed")) return wrc;
+    if (int rrc = check_rule(h, rule, "trim_pairs_packed")) return rrc;
+    if (int crc = check_pairs(h, n_reads, pair_mode, "trim_pairs_packed")) return crc;
+    const OutStream P = {d_pairs_packed, pairs_cap_words, d_pairs_starts, d_pairs_index}, S = {d_singles_packed, singles_cap_words, d_singles_starts, d_singles_index};
+    if (int orc = check_pair_outs(h, P, S, counts, "trim_pairs_packed")) return orc;
+    if (n_reads && (!d_packed || !d_starts)) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_packed: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    int rc;
+    const bool any = pair_mode == BRISK_HIP_PAIR_ANY;
+    if (n_reads) {
+        if ((rc = ensure(h, h->ext_iv, n_reads * sizeof(ReadInterval)))) return rc;
+        if (any && (rc = ensure(h, h->pair_iv, n_reads * sizeof(ReadInterval)))) return rc;
+        ReadInterval* d_each = (ReadInterval*)h->ext_iv.p;
+        ReadInterval* d_whole = any ? (ReadInterval*)h->pair_iv.p : nullptr;
+        if ((rc = profile_select(h, d_packed, d_starts, n_reads, solid_min, rule, d_each, d_whole))) return rc;
+        if ((rc = pair_intervals_impl(h, d_each, d_whole, n_reads, pair_mode, d_each))) return rc;
+    }
+    return extract_pairs_impl(h, d_packed, d_starts, n_reads, (const ReadInterval*)h->ext_iv.p, P, S, counts);
+}
+
+BRISK_API int brisk_hip_trim_pairs_reads(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t solid_min, const brisk_hip_select_rule* rule,
+                                         uint32_t pair_mode, brisk_hip_read_interval* out, brisk_hip_pair_counts* counts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "trim_pairs_reads")) return wrc;
+    if (int rrc = check_rule(h, rule, "trim_pairs_reads")) return rrc;
+    if (int crc = check_pairs(h, n_reads, pair_mode, "trim_pairs_reads")) return crc;
+    if (!counts || (n_reads && (!bases || !offsets || !out))) return fail(h, BRISK_HIP_EINVAL, "trim_pairs_reads: null pointer");
+    if (int orc = check_profile_offsets(h, offsets, n_reads, "trim_pairs_reads")) return orc;
+    memset(counts, 0, sizeof(*counts));
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    int rc;
+    // the whole call's intervals stay on the device until the pair decision: a batch may end between two mates
+    const bool any = pair_mode == BRISK_HIP_PAIR_ANY;
+    if ((rc = ensure(h, h->ext_iv, n_reads * sizeof(ReadInterval)))) return rc;
+    if (any && (rc = ensure(h, h->pair_iv, n_reads * sizeof(ReadInterval)))) return rc;
+    ReadInterval* d_each = (ReadInterval*)h->ext_iv.p;
+    ReadInterval* d_whole = any ? (ReadInterval*)h->pair_iv.p : nullptr;
+    rc = profile_host_batches(h, bases, offsets, n_reads, solid_min,
+                              [&](u64 r0, u64 nr, const ReadProfile* d_prof) { return select_batch(h, d_prof, nr, rule, d_each + r0, any ? d_whole + r0 : nullptr); });
+    if (rc) return rc;
+    if ((rc = pair_intervals_impl(h, d_each, d_whole, n_reads, pair_mode, d_each))) return rc;
+    const ReadInterval *iv_p, *iv_s;
+    if ((rc = pair_split_impl(h, d_each, n_reads, nullptr, counts, &iv_p, &iv_s))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, d_each, n_reads * sizeof(ReadInterval), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_clean_pairs_ascii(brisk_hip_index* h, const char* d_bases, const char* d_quals, const uint64_t* d_offsets, uint64_t n_reads, const brisk_hip_intake_rule* intake,
+                                          const brisk_hip_select_rule* select, uint32_t solid_min, uint32_t pair_mode, uint32_t* d_pairs_packed, uint64_t pairs_cap_words,
+                                          uint64_t* d_pairs_starts, uint64_t* d_pairs_index, uint32_t* d_singles_packed, uint64_t singles_cap_words, uint64_t* d_singles_starts,
+                                          uint64_t* d_singles_index, brisk_hip_read_interval* d_out_intervals, brisk_hip_pair_counts* counts, brisk_hip_intake_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    u32 min_len = 0, thr = 0;
+    if (int crc = check_clean_pairs(h, intake, d_quals != nullptr, select, n_reads, pair_mode, "clean_pairs_ascii", &min_len, &thr)) return crc;
+    const OutStream P = {d_pairs_packed, pairs_cap_words, d_pairs_starts, d_pairs_index}, S = {d_singles_packed, singles_cap_words, d_singles_starts, d_singles_index};
+    if (int orc = check_pair_outs(h, P, S, counts, "clean_pairs_ascii")) return orc;
+    if (!stats || (n_reads && (!d_bases || !d_offsets))) return fail(h, BRISK_HIP_EINVAL, "clean_pairs_ascii: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (select)
+        if (int frc = enter(h)) return frc;
+    int rc;
+    CleanedPairs c;
+    if ((rc = clean_pairs_core(h, (const uint8_t*)d_bases, (const uint8_t*)d_quals, d_offsets, n_reads, min_len, thr, select, solid_min, pair_mode, stats, &c))) return rc;
+    if ((rc = extract_pairs_impl(h, c.raw, c.raw_starts, n_reads, c.intervals, P, S, counts))) return rc;
+    if (d_out_intervals && n_reads) {
+        HIPCHK(h, hipMemcpyAsync(d_out_intervals, c.intervals, n_reads * sizeof(ReadInterval), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_clean_pairs_reads(brisk_hip_index* h, const char* bases, const char* quals, const uint64_t* offsets, uint64_t n_reads, const brisk_hip_intake_rule* intake,
+                                          const brisk_hip_select_rule* select, uint32_t solid_min, uint32_t pair_mode, brisk_hip_read_interval* out, brisk_hip_pair_counts* counts,
+                                          brisk_hip_intake_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    u32 min_len = 0, thr = 0;
+    if (int crc = check_clean_pairs(h, intake, quals != nullptr, select, n_reads, pair_mode, "clean_pairs_reads", &min_len, &thr)) return crc;
+    if (!stats || !counts || (n_reads && (!bases || !offsets || !out))) return fail(h, BRISK_HIP_EINVAL, "clean_pairs_reads: null pointer");
+    if (int orc = check_raw_reads(h, offsets, n_reads, "clean_pairs_reads")) return orc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    memset(stats, 0, sizeof(*stats));
+    memset(counts, 0, sizeof(*counts));
+    if (select)
+        if (int frc = enter(h)) return frc;
+    return for_each_raw_piece(h, bases, thr ? quals : nullptr, offsets, n_reads, [&](u64 r0, u64 nr, const uint8_t* d_b, const uint8_t* d_q, const u64* d_offs) -> int {
+        int rc2;
+        brisk_hip_intake_stats st;
+        brisk_hip_pair_counts pc;
+        CleanedPairs c;
+        const ReadInterval *iv_p, *iv_s;
+        if ((rc2 = clean_pairs_core(h, d_b, d_q, d_offs, nr, min_len, thr, select, solid_min, pair_mode, &st, &c))) return rc2;
+        if ((rc2 = pair_split_impl(h, c.intervals, nr, nullptr, &pc, &iv_p, &iv_s))) return rc2;
+        HIPCHK(h, hipMemcpyAsync(out + r0, c.intervals, nr * sizeof(ReadInterval), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        add_counters(stats, st);
+        add_counters(counts, pc);
+        return BRISK_HIP_OK;
+    }, 2);
+}
+
+}  // extern "C"

@@ -33,13 +33,13 @@ def library_path() -> str:
 def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU). In-tree output."""
     out = library_path()
-    srcs = [os.path.join(HERE, "csrc", f) for f in ("brisk_capi.hip", "brisk_kernels.hip", "brisk_scan.hip", "brisk_partition.hip", "brisk_insert.hip",
-                                                    "brisk_readout.hip", "brisk_answers.hip", "brisk_setops.hip", "brisk_snapshot.hip", "brisk_profile.hip", "brisk_extract.hip", "brisk_intake.hip", "brisk_pairs.hip", "brisk_device.h")]
+    csrc = os.path.join(HERE, "csrc")  # one translation unit, brisk_capi.hip, which includes every other part: all of them make the library stale
+    srcs = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
     srcs.append(os.path.join(ROOT, "include", "brisk_hip.h"))
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-fvisibility=hidden",
-           "-Wno-unused-value", "-o", out, srcs[0]]
+           "-Wno-unused-value", "-o", out, os.path.join(csrc, "brisk_capi.hip")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
