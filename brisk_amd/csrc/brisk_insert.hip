@@ -571,6 +571,78 @@ __device__ __forceinline__ bool fold_records(const FoldFrame& f, u32 nrec, u32 l
     return folded;
 }
 
+// ---- The same fold with the head of every core-key group taken in the same round (k_insert_first, section 4 finding 21).  Where
+// no record is `unsure`, every record's mask covers the core, so a record is contained only in a head of its own ck and makes
+// only records of its own ck dirty: the groups' rounds do not interact, and a partition of four loci need not spend four
+// wave-wide rounds on them.  A lane's slot is a 6-bit hash of its ck (fold_slot).  A round: the open lanes ds_max their
+// [round | sv] into their slot of `s_slot` (64 words, cleared once: a later round's values lie above every earlier one's), read
+// the slot back, and meet the head they find there -- its rng, ck and frame words fetched by lane index (ds_bpermute), a word at
+// a time, where fold_records broadcasts them through scalar registers.  The lane whose own value came back is a head and closes
+// unfolded.  Two groups in one slot cost rounds, not correctness: the smaller head's group fails the ck compare, stays open and
+// finds its own head in a later round; within a group heads are still taken in decreasing sv, so lead, off, folded and clean
+// are fold_records' wherever that takes at most WI_FOLD_TRIPS heads.  Returns false -- nothing of the result is to be used, the
+// caller runs fold_records -- where a record is unsure (containment then need not imply equal ck), where more heads than that
+// were taken, or where a lane is open after the last round.
+#ifndef FOLD_GROUPED
+#define FOLD_GROUPED 1   // -DFOLD_GROUPED=0: fold_records alone in k_insert_first, for A/B
+#endif
+#ifdef INSERT_ATTR_ONEROUND  // attribution build: the fold stops after one round.  Wrong results, timing only
+#define FOLD_GROUPED_TRIPS 1u
+#else
+#define FOLD_GROUPED_TRIPS WI_FOLD_TRIPS
+#endif
+__device__ __forceinline__ u32 fold_slot(u32 ck) { return (ck * 0x9E3779B1u) >> 26; }
+__device__ __forceinline__ u32 lane_fetch(u32 v, u32 a4) { return (u32)__builtin_amdgcn_ds_bpermute((int)a4, (int)v); }
+__device__ __forceinline__ u64 lane_fetch64(u64 v, u32 a4) { return ((u64)lane_fetch((u32)(v >> 32), a4) << 32) | lane_fetch((u32)v, a4); }
+template <u32 NW>
+__device__ __forceinline__ bool fold_records_grouped(const FoldFrame& f, u32 nrec, u32 lane, u32* s_slot, u32* lead, u32* off, bool* folded_out, u32* trips, u32 ck, bool unsure,
+                                                     bool* clean) {
+    static_assert(WI_FOLD_TRIPS < (1u << 18), "[round | n | 63 - lane] in 32 bits: n < 256, so sv < 1 << 14");
+    if (__any(unsure)) return false;
+    u32 sv = lane < nrec ? f.s : 0;
+    bool folded = false;
+    u32 dirty = 0, heads = 0;
+    *lead = lane;
+    *off = 0;
+    u32* my_slot = s_slot + fold_slot(ck);
+    s_slot[lane] = 0;
+    wave_sync();
+    for (u32 t = 1; t <= FOLD_GROUPED_TRIPS; t++) {
+        if (!__any(sv != 0) || heads > WI_FOLD_TRIPS) break;
+        *trips += 1;
+        const u32 mine = (t << 14) | sv;
+        if (sv != 0) atomicMax(my_slot, mine);
+        wave_sync();
+        const u32 top = *my_slot;  // (a closed lane reads what it likes: every use below is under sv != 0)
+        heads += (u32)__popcll(__ballot(sv != 0 && top == mine));
+        const u32 a = 63 - (top & 63), a4 = a << 2;
+        const u32 rng_a = lane_fetch(f.rng, a4), ck_a = lane_fetch(ck, a4);
+        const u32 i0 = f.rng & 0xffu, e = f.rng >> 8, i0a = rng_a & 0xffu, ea = rng_a >> 8;
+        bool in = sv != 0 && ck_a == ck && i0a <= i0 && e <= ea;  // (equal ck: equal routing ids, a partition's differ in nothing else)
+        bool same = (lane_fetch64(f.u.w0, a4) & f.m.w0) == f.u.w0;
+        if (NW > 1) same = same & ((lane_fetch64(f.u.w1, a4) & f.m.w1) == f.u.w1);
+        if (NW > 2) same = same & ((lane_fetch64(f.u.w2, a4) & f.m.w2) == f.u.w2);
+        if (NW > 3) same = same & ((lane_fetch64(f.u.w3, a4) & f.m.w3) == f.u.w3);
+        in = in && same;
+        if (in) {  // (a head closes here, unfolded)
+            sv = 0;
+            if (lane != a) {
+                folded = true;
+                *lead = a;
+                *off = i0 - i0a;
+            }
+        }
+        const u32 meets = ((i0 - ea) & (i0a - e)) >> 31;  // 1: i0 < ea && i0a < e (all below 256)
+        dirty |= (ck_a == ck && sv != 0) ? meets : 0u;
+    }
+#ifndef INSERT_ATTR_ONEROUND
+    if (heads > WI_FOLD_TRIPS || __any(sv != 0)) return false;
+#endif
+    *clean = !__any(dirty != 0);
+    *folded_out = folded;
+    return true;
+}
+
 // MAXI: k-mer instances per chunk.  256 (10 KB of LDS, 128 registers: 4 waves per SIMD) for the usual partitions of a
 // few hundred instances; 512 (2 waves per SIMD) when partitions are big -- few distinct minimizers, as with m <= 11 --
 // and the passes over a partition's entries saved by half as many chunks outweigh the occupancy.
@@ -1209,7 +1281,10 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                 const bool unsure = lane < nrec && (ff.s == 0 || hdr_idx0(my_hdr) < core_from);
                 bool clean = false;
                 const u32 ck = ((hdr_bucket(my_hdr) & ((1u << SHIFT) - 1)) << (2 * (KB - CW))) | fold_core<KB, CW>(ff.u);
-                const bool dup = fold_records<NW, true>(ff, nrec, lane, &lead, &lead_off, &dbg_trips, ck, unsure, &clean);
+                bool dup = false;
+                // (the slot words lie over s_key / s_idiff, which nothing holds before the instance map below)
+                if (!FOLD_GROUPED || !fold_records_grouped<NW>(ff, nrec, lane, (u32*)s_mem, &lead, &lead_off, &dup, &dbg_trips, ck, unsure, &clean))  // wave-uniform
+                    dup = fold_records<NW, true>(ff, nrec, lane, &lead, &lead_off, &dbg_trips, ck, unsure, &clean);
 #ifdef INSERT_ATTR_NOTABLE  // attribution build: every partition taken goes down the table-free path.  Wrong results, timing only
                 clean = true;
 #endif
