@@ -70,7 +70,7 @@ struct Counters {
     struct Scan { unsigned long long n_rec; u32 overflow, pad; } scan;          // ScanOut::n_rec (records wanted, also beyond cap), ::overflow
     struct Touched { u32 n_touched, pad; unsigned long long need; } touched;    // k_touched: partitions with records; k_need: arena slots they may take
     struct Kmers { unsigned long long bound, n_long; } kmers;                   // k_count_kmers: k-mers; sequences beyond SCAN_LONG | offsets do not ascend << 63
-    struct Work { u32 wc[2], n_left, n_clean; } work;  // work counters of the persistent insert / query waves; k_insert_first: partitions left to k_insert_fast_listed, and those it took table-free
+    struct Work { u32 wc[2], n_left, n_clean, n_pair, pad; } work;  // work counters of the persistent insert / query waves; k_insert_first: partitions left to k_insert_fast_listed, those it took table-free, and those of them it took two to a wave
     struct Plan { u32 n_long, n_vr; } plan;        // k_plan_chunks: long sequences, and the chunks they are cut into
     u32 n_rerun, pad;                              // k_chunk_commit: chunks to re-scan this round
     unsigned long long kept;                       // k_filter_records / k_query_filter / k_pos_filter: records that stand
@@ -82,7 +82,7 @@ struct Counters {
 };
 static_assert(sizeof(Counters::Scan) == sizeof(unsigned long long) + 2 * sizeof(u32) && sizeof(Counters::Touched) == 2 * sizeof(u32) + sizeof(unsigned long long), "ScanOut; k_touched, k_need");
 static_assert(sizeof(Counters::Kmers) == 2 * sizeof(unsigned long long) && sizeof(Counters::Result) == 3 * sizeof(unsigned long long), "k_count_kmers: out[0..1]; k_checksum: out[0..2]");
-static_assert(sizeof(Counters::Work) == 4 * sizeof(u32) && sizeof(Counters::Plan) == 2 * sizeof(u32), "32-bit counters throughout");
+static_assert(sizeof(Counters::Work) == 6 * sizeof(u32) && sizeof(Counters::Plan) == 2 * sizeof(u32), "32-bit counters throughout");
 struct PinnedCounters : Counters {  // host only; pinned because copies land in them or leave from them
     u32 n_huge;                     // number of huge partitions, from h->huge
     unsigned long long arena_used;  // copy of ix.cursor (on load: the cursor to upload)
@@ -106,6 +106,7 @@ struct brisk_hip_index {
     double* d_coef = nullptr;
     double* d_tabs = nullptr;   // coef[128] + packed fixed-point decycling chunk tables (u64 bits), staged to LDS by k_scan2
     ScanCfg scfg{};
+    u32 dbg_touched_last = 0;   // partitions the last record insert touched: the first so many of d_touched, in the order its kernels walked them (brisk_hip_debug_touched)
     u64 dbg_guard_last = 0;     // brisk_hip_debug_order_keys: keys of its last call that took the exact fold (brisk_hip_debug_guard_count)
     bool fresh = true;          // nothing has been inserted since create / clear: every partition is empty (k_insert_first's route).  Whatever may
                                 // put entries into the index clears it: inserts (deferred ones when they complete), merge, reallocate, snapshot load, upserts
@@ -594,6 +595,7 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
     }
     HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->touched.n_touched));
     const u32 n_touched = h->h_ctr->touched.n_touched;
+    h->dbg_touched_last = n_touched;
     if (n_touched == 0) return BRISK_HIP_OK;
     // partitions of more k-mer instances than this go to k_insert_huge, a workgroup each (0: none; entry-id indexes keep ids per entry,
     // which that kernel does not)
@@ -655,6 +657,7 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         static const bool generic_only = getenv("BRISK_INSERT_GENERIC") != nullptr;  // A/B and tests: force the run-time body
         static const bool lean_off = getenv("BRISK_INSERT_LEAN") && !strcmp(getenv("BRISK_INSERT_LEAN"), "0");  // A/B and tests: never take k_insert_first's route
         static const bool clean_off = getenv("BRISK_INSERT_CLEAN") && !strcmp(getenv("BRISK_INSERT_CLEAN"), "0");  // A/B and tests: k_insert_first's table path for every partition
+        static const bool pair_off = getenv("BRISK_INSERT_PAIR") && !strcmp(getenv("BRISK_INSERT_PAIR"), "0");  // A/B and tests: k_insert_first never takes two partitions in one wave
         const bool lean = fresh && !generic_only && !lean_off && !h->entry_ids && !big && P.nw == 3 && P.kb == 49 && P.shift >= 1 && P.shift <= 4;
         if (lean) {
             if ((rc = ensure(h, h->left, (size_t)n_touched * 4))) return rc;
@@ -699,10 +702,11 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
         u32* const wc = h->d_ctr->work.wc;                                                                                                                          \
         u32* const n_left = &h->d_ctr->work.n_left;                                                                                                                 \
         u32* const n_clean = clean_off ? nullptr : &h->d_ctr->work.n_clean;                                                                                         \
+        u32* const n_pair = (clean_off || pair_off) ? nullptr : &h->d_ctr->work.n_pair;                                                                             \
         body = "k_insert_first<3,49," #SH;                                                                                                                          \
         const dim3 grid(std::min<u32>(batches, resident((const void*)k_insert_first<3, 49, SH, SAT>, 4 * WI_WAVES_PER_EU_FIRST_MAX)));                                                            \
         hipLaunchKernelGGL((k_insert_first<3, 49, SH, SAT>), grid, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix, wc,                \
-                           (u32*)h->left.p, n_left, n_clean);                                                                                                       \
+                           (u32*)h->left.p, n_left, n_clean, n_pair);                                                                                               \
         if ((rc = launch_check(h, "k_insert_first"))) return rc;                                                                                                    \
         const dim3 grid2(std::min<u32>(batches, resident((const void*)k_insert_fast_listed<3, 49, SH, SAT>)));                                                     \
         hipLaunchKernelGGL((k_insert_fast_listed<3, 49, SH, SAT>), grid2, dim3(64), 0, h->stream, P, src, (const PartDesc*)h->desc.p, n_touched, h->ix, wc + 1,     \
@@ -743,6 +747,14 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
             fprintf(stderr, "[brisk_hip] path: insert of %llu records (%s layout, histogram %s) into %u partitions: %s, %u partitions to k_insert_huge%s\n", (unsigned long long)n_rec,
                     bl ? "binned" : "classic", have_hist ? "from the scan" : "counted here", n_touched, path.c_str(), n_huge, tail.c_str());
             fprintf(stderr, "[brisk_hip] body: %s,%s>%s\n", body, sat ? "sat" : "wrap", lean ? ", then k_insert_fast_listed" : "");
+        }
+        if (lean) {  // (debugging only: the counts are waited for)
+            static const bool dbg = getenv("BRISK_DEBUG_INSERT") != nullptr;
+            if (dbg) {
+                HIPCHK(h, fetch_ctr_sync(h, &h->d_ctr->work));
+                fprintf(stderr, "[brisk_hip] k_insert_first: %u of %u partitions taken in pairs, %u table-free, %u left over\n", h->h_ctr->work.n_pair, n_touched,
+                        h->h_ctr->work.n_clean, h->h_ctr->work.n_left);
+            }
         }
         if (n_huge) {
             if (sat) hipLaunchKernelGGL(k_insert_huge<true>, dim3(std::min<u32>(n_huge, 256u)), dim3(HG_THREADS), 0, h->stream, P, src, (const PartDesc*)h->desc.p,
@@ -3877,6 +3889,33 @@ BRISK_API int brisk_hip_debug_guard_count(brisk_hip_index* h, uint64_t* n_guard)
     if (!h || !n_guard) return BRISK_HIP_EINVAL;
     std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
     *n_guard = h->dbg_guard_last;
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_debug_touched(brisk_hip_index* h, uint32_t* parts, uint64_t cap, uint64_t* n) {
+    if (!h || !n || (cap && !parts)) return BRISK_HIP_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    *n = h->dbg_touched_last;
+    const u64 take = std::min<u64>(cap, h->dbg_touched_last);
+    if (take) HIPCHK(h, hipMemcpyAsync(parts, h->d_touched, take * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_debug_directory(brisk_hip_index* h, const uint32_t* parts, uint64_t n, uint32_t* cnt, uint32_t* cap) {
+    if (!h || (n && (!parts || !cnt || !cap))) return BRISK_HIP_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    for (u64 i = 0; i < n; i++)
+        if (parts[i] >= h->n_parts) return BRISK_HIP_EINVAL;
+    std::vector<DirEnt> dir(h->n_parts);  // (a test hook: the whole directory, 16 bytes a partition, in one copy)
+    HIPCHK(h, hipMemcpyAsync(dir.data(), h->ix.dir, h->n_parts * sizeof(DirEnt), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (u64 i = 0; i < n; i++) {
+        cnt[i] = dir[parts[i]].cnt;
+        cap[i] = dir[parts[i]].cap;
+    }
     return BRISK_HIP_OK;
 }
 

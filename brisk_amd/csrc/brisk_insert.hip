@@ -583,6 +583,8 @@ __device__ __forceinline__ bool fold_records(const FoldFrame& f, u32 nrec, u32 l
 // are fold_records' wherever that takes at most WI_FOLD_TRIPS heads.  Returns false -- nothing of the result is to be used, the
 // caller runs fold_records -- where a record is unsure (containment then need not imply equal ck), where more heads than that
 // were taken, or where a lane is open after the last round.
+// Two partitions in one wave (finding 22) are just more groups: the caller sets a partition bit in B's ck, so a record meets
+// only heads of its own partition; *dirty_lanes is the ballot of the lanes found dirty, which the caller reduces per partition.
 #ifndef FOLD_GROUPED
 #define FOLD_GROUPED 1   // -DFOLD_GROUPED=0: fold_records alone in k_insert_first, for A/B
 #endif
@@ -596,7 +598,7 @@ __device__ __forceinline__ u32 lane_fetch(u32 v, u32 a4) { return (u32)__builtin
 __device__ __forceinline__ u64 lane_fetch64(u64 v, u32 a4) { return ((u64)lane_fetch((u32)(v >> 32), a4) << 32) | lane_fetch((u32)v, a4); }
 template <u32 NW>
 __device__ __forceinline__ bool fold_records_grouped(const FoldFrame& f, u32 nrec, u32 lane, u32* s_slot, u32* lead, u32* off, bool* folded_out, u32* trips, u32 ck, bool unsure,
-                                                     bool* clean) {
+                                                     bool* clean, unsigned long long* dirty_lanes = nullptr) {
     static_assert(WI_FOLD_TRIPS < (1u << 18), "[round | n | 63 - lane] in 32 bits: n < 256, so sv < 1 << 14");
     if (__any(unsure)) return false;
     u32 sv = lane < nrec ? f.s : 0;
@@ -638,7 +640,9 @@ __device__ __forceinline__ bool fold_records_grouped(const FoldFrame& f, u32 nre
 #ifndef INSERT_ATTR_ONEROUND
     if (heads > WI_FOLD_TRIPS || __any(sv != 0)) return false;
 #endif
-    *clean = !__any(dirty != 0);
+    const unsigned long long dl = __ballot(dirty != 0);  // (a lane is made dirty only by a head of its own ck: of its own partition, where two share the wave)
+    if (dirty_lanes) *dirty_lanes = dl;
+    *clean = dl == 0;
     *folded_out = folded;
     return true;
 }
@@ -1210,9 +1214,45 @@ struct LeanLds {
 __device__ __forceinline__ unsigned long long first_lane64(unsigned long long v) {
     return ((unsigned long long)(u32)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)v);
 }
+// ---- Two small partitions in one wave (section 4 finding 22).  The flagship job's partitions hold 12 records on 64 lanes, and most
+// of what the body issues per partition does not depend on how many lanes hold something.  Where the next two descriptors A and B of
+// the wave's batch are both first-fill candidates (empty, no slice, not huge) with n_rec(A) + n_rec(B) <= 64, B's records are loaded
+// behind A's -- lanes [nA, nA + nB) -- and the two run one fold (ck carries a partition bit, so a record meets only heads of its own
+// partition), one instance map, one table-free expansion and one store tail with two slices, two directory entries and two
+// bucket_bits words.  The pair goes on only where the joint grouped fold stands, both partitions are clean and their instances
+// together are at most MAXI; otherwise A goes alone -- from the joint fold's results for its lanes, which are what its own fold
+// yields, groups do not interact; from the top where the joint fold did not stand -- and B heads the next candidate pair.
+// Entries, their order and each cap are what the single route yields; only the slices' places in the arena may differ.
+#ifndef INSERT_PAIR
+#define INSERT_PAIR 1   // -DINSERT_PAIR=0: the single-partition body alone, for A/B
+#endif
+#define PAIR_B_BIT 18u  // ck's partition bit, above [routing id low bits (SHIFT <= 4) | core (14)]
+// a pair's records: lane r < nA loads record r of partition A, lane nA + r (r < nB) record r of partition B (nB == 0: load_part_recs)
+__device__ __forceinline__ RecRegs load_pair_recs(const BriskParams& P, const RecSrc& src, u32 part_a, u32 begin_a, u32 nA, u32 part_b, u32 begin_b, u32 nB, u32 lane) {
+    RecRegs r{0, 0, 0, 0, 0};
+    // (everything per partition is wave-uniform, in scalar registers: record 0 of the bin -- classic: of the partition -- and the
+    // place record 0 would have in the overflow area; a lane picks one of the four and adds its record's index)
+    const u32 in_bin = src.bin_cap ? src.bin_cap : ~0u;
+    const u64 bytes = (u64)P.stride * 8, rec0 = (u64)(uintptr_t)src.rec, ovf0 = (u64)(uintptr_t)src.ovf;
+    const u64 bin_a = rec0 + (src.bin_cap ? (u64)part_a * src.bin_cap : (u64)begin_a) * bytes, ovf_a = ovf0 + ((u64)begin_a - src.bin_cap) * bytes;
+    const u64 bin_b = rec0 + (src.bin_cap ? (u64)part_b * src.bin_cap : (u64)begin_b) * bytes, ovf_b = ovf0 + ((u64)begin_b - src.bin_cap) * bytes;
+    if (lane < nA + nB) {
+        const bool is_b = lane >= nA;
+        const u32 i = is_b ? lane - nA : lane;
+        const u64 base = i < in_bin ? (is_b ? bin_b : bin_a) : (is_b ? ovf_b : ovf_a);
+        const u64* c = (const u64*)(uintptr_t)(base + i * bytes);
+        r.w0 = c[0];
+        r.w1 = c[1];
+        if (P.stride > 2) r.w2 = c[2];
+        if (P.stride > 3) r.w3 = c[3];
+        if (P.stride > 4) r.w4 = c[4];
+    }
+    return r;
+}
 template <u32 NIL, u32 NW, u32 KB, u32 SHIFT, bool SAT>
 __device__ __forceinline__ void insert_first_body(const BriskParams& P, const RecSrc& src, const PartDesc* __restrict__ desc, u32 n_touched, const IndexDev& ix,
-                                                  u32* __restrict__ work_counter, u32* __restrict__ left_list, u32* __restrict__ n_left, u32* __restrict__ n_clean) {
+                                                  u32* __restrict__ work_counter, u32* __restrict__ left_list, u32* __restrict__ n_left, u32* __restrict__ n_clean,
+                                                  u32* __restrict__ n_pair) {
     using L = LeanLds<NIL, NW>;
     constexpr u32 MAXI = L::MAXI, TABLE = L::TABLE, RS = RecGeom<NW>::RS, INFO = RecGeom<NW>::INFO, KBITS = 2 * KB + 6;
     constexpr u32 KW = KBITS + SHIFT <= 64 ? 1u : 2u;
@@ -1242,6 +1282,24 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
     const u32 frame_end = P.suff_reduc + P.w + 1;
     // the idx' from which on a window covers the core; beyond every idx' (no record is sure, no partition table-free) where the path is off
     const u32 core_from = (n_clean != nullptr && P.w == CW) ? P.suff_reduc : 0x100u;
+    // pairs only where the table-free path is on: a pair has no table path
+    const bool pair_on = INSERT_PAIR && n_pair != nullptr && core_from != 0x100u;
+    // Requests the records of head `a` (descriptor index ta) and, where the pair rule holds for desc[ta] and desc[ta + 1], of its
+    // neighbour behind them; returns the neighbour's record count, 0 where `a` goes alone.  B must lie inside the batch.
+    auto request = [&](const PartDesc& a, u32 ta, u32 t_end, RecRegs& rr) -> u32 {
+        u32 nB = 0, part_b = 0, begin_b = 0;
+        if (pair_on && ta + 1 < t_end && !(a.n_exist | a.cap) && a.n_rec - 1u < (u32)WI_MAX_REC - 1u && !(ix.huge_at && a.n_inst > ix.huge_at)) {
+            const PartDesc b = desc[ta + 1];
+            if (!(b.n_exist | b.cap) && b.n_rec != 0 && a.n_rec + b.n_rec <= (u32)WI_MAX_REC && !(ix.huge_at && b.n_inst > ix.huge_at)) {
+                nB = b.n_rec;
+                part_b = b.part;
+                begin_b = b.r_begin;
+            }
+        }
+        // (one load for both cases: alone, no lane lies in B's range)
+        rr = load_pair_recs(P, src, a.part, a.r_begin, min(a.n_rec, (u32)WI_MAX_REC), part_b, begin_b, nB, lane);
+        return nB;
+    };
 
     for (;;) {
         u32 t0 = 0;
@@ -1251,13 +1309,17 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
         const u32 t_end = min(t0 + WI_BATCH, n_touched);
         unsigned long long left_mask = 0;  // partitions t0 + i of this batch that are left to k_insert_fast (wave-uniform)
         unsigned long long clean_mask = 0;  // those that took the table-free path (counted for the trace)
+        u32 pairs = 0;                      // partitions of this batch taken in pairs
         PartDesc d = desc[t0];
-        RecRegs rr = load_part_recs(P, src, d.part, d.r_begin, d.r_begin, min(d.n_rec, (u32)WI_MAX_REC), lane);
+        RecRegs rr;
+        u32 nB = INSERT_PAIR ? request(d, t0, t_end, rr) : 0u;  // records of desc[t + 1] behind d's in rr (0: d alone)
+        if (!INSERT_PAIR) rr = load_part_recs(P, src, d.part, d.r_begin, d.r_begin, min(d.n_rec, (u32)WI_MAX_REC), lane);
 
-        for (u32 t = t0; t < t_end; t++) {
-            const u32 tn = t + 1;
+        for (u32 t = t0, step = 1; t < t_end; t += step) {
+            u32 tn = t + 1;
+            step = 1;
             PartDesc dn{};
-            if (tn < t_end) dn = desc[tn];
+            if (tn < t_end) dn = desc[tn];  // (of a pair: B's)
             // (the records of the next partition are requested at the end of this one, and must have landed on every path: insert_body)
             asm volatile("" ::"v"(rr.w0), "v"(rr.w1), "v"(rr.w2), "v"(rr.w3), "v"(rr.w4));
             do {
@@ -1268,7 +1330,8 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                     break;
                 }
                 PHASE(0)
-                const u32 part = d.part, nrec = d.n_rec;
+                const u32 part = d.part, nA = d.n_rec;
+                u32 nrec = nA + nB;  // (the pair rule: at most WI_MAX_REC)
                 const u64 my_hdr = NW == 3 ? rr.w3 : rr.w4;
                 const u32 raw_n = lane < nrec ? hdr_n(my_hdr) : 0;
                 const u32 my_mult = (my_hdr & HDR_HAS_MULT) ? (u32)(my_hdr >> 48) & 0xffu : 1u;
@@ -1278,19 +1341,47 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                 if (lane < nrec) store_rec_words<NW>(s_rw + lane * RS, rr, 0);
                 u32 lead = lane, lead_off = 0, dbg_trips = 0;
                 // (a record that takes no part in the fold, or reaches below suff_reduc: its windows may miss the core)
-                const bool unsure = lane < nrec && (ff.s == 0 || hdr_idx0(my_hdr) < core_from);
+                const bool unsure_any = ff.s == 0 || hdr_idx0(my_hdr) < core_from;
                 bool clean = false;
-                const u32 ck = ((hdr_bucket(my_hdr) & ((1u << SHIFT) - 1)) << (2 * (KB - CW))) | fold_core<KB, CW>(ff.u);
+                // (of a pair: B's lanes carry the partition bit, so equal ck stays equal routing id; alone, no lane below nrec has it)
+                const u32 ck = ((hdr_bucket(my_hdr) & ((1u << SHIFT) - 1)) << (2 * (KB - CW))) | fold_core<KB, CW>(ff.u) |
+                               (INSERT_PAIR && lane >= nA ? 1u << PAIR_B_BIT : 0u);
+                static_assert(SHIFT + 2 * (KB - CW) <= PAIR_B_BIT, "ck: the partition bit lies above the routing id's low bits and the core");
                 bool dup = false;
+                unsigned long long dirty_lanes = 0;
                 // (the slot words lie over s_key / s_idiff, which nothing holds before the instance map below)
-                if (!FOLD_GROUPED || !fold_records_grouped<NW>(ff, nrec, lane, (u32*)s_mem, &lead, &lead_off, &dup, &dbg_trips, ck, unsure, &clean))  // wave-uniform
+                for (;;) {  // wave-uniform; a second turn only where the joint fold of a pair does not stand: A alone, from the top
+                    const bool unsure = lane < nrec && unsure_any;
+                    if (FOLD_GROUPED && fold_records_grouped<NW>(ff, nrec, lane, (u32*)s_mem, &lead, &lead_off, &dup, &dbg_trips, ck, unsure, &clean, &dirty_lanes)) break;
+                    if (INSERT_PAIR && nB) {
+                        nB = 0;
+                        nrec = nA;
+                        continue;
+                    }
                     dup = fold_records<NW, true>(ff, nrec, lane, &lead, &lead_off, &dbg_trips, ck, unsure, &clean);
+                    break;
+                }
 #ifdef INSERT_ATTR_NOTABLE  // attribution build: every partition taken goes down the table-free path.  Wrong results, timing only
                 clean = true;
 #endif
-                const u32 my_n = (lane < nrec && !dup) ? raw_n : 0;
+                u32 my_n = (lane < nrec && !dup) ? raw_n : 0;
                 const u32 x = wave_incl_scan(my_n, lane);
-                const u32 ninst = (u32)__builtin_amdgcn_readlane((int)x, 63);
+                u32 ninst = (u32)__builtin_amdgcn_readlane((int)x, 63);
+                u32 ninstA = ninst;  // (of a pair: A's instances are [0, ninstA) of the joint list, B's the rest)
+                if (INSERT_PAIR && nB) {  // wave-uniform: pair or not, decided after the fold
+                    ninstA = (u32)__builtin_amdgcn_readlane((int)x, (int)(nA - 1));
+                    const bool clean_a = (dirty_lanes & ((1ull << nA) - 1)) == 0;
+                    if (clean && ninst <= MAXI) {  // (clean: no lane of either is dirty)
+                        step = 2;
+                        pairs += 2;
+                    } else {  // A alone, from the joint fold's results for its lanes; B heads the next candidate pair
+                        nB = 0;
+                        nrec = nA;
+                        clean = clean_a;
+                        if (lane >= nA) my_n = 0;
+                        ninst = ninstA;
+                    }
+                }
                 if (ninst > MAXI) {  // (nothing but LDS has been written)
                     left_mask |= 1ull << (t - t0);
                     break;
@@ -1313,6 +1404,8 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                     if (my_n) s_irec[x - my_n] = (uint8_t)(lane + 1);
                     if (lane < nrec) {
                         atomicAdd(&s_idiff[m_first], my_mult);
+                        // (of a pair the map runs over the concatenated list unchanged: a record of A that ends on A's last instance
+                        // steps down at ninstA < ninst, B's first instance, so the running sum is back at zero where B begins)
                         if (m_first + raw_n < ninst) atomicAdd(&s_idiff[m_first + raw_n], 0u - my_mult);
                     }
                     wave_sync();
@@ -1363,7 +1456,7 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                 li.won = 0;
                 u32 n_new = 0, new_rank[NIL], new_word[NIL];
                 if (clean) {  // wave-uniform: the table-free path.  Instance i is entry i, its count what s_imult holds
-                    clean_mask |= 1ull << (t - t0);
+                    clean_mask |= (INSERT_PAIR && nB ? 3ull : 1ull) << (t - t0);
                     // (the lane as this path sees it, opaque: what is derived from it here is computed here, not kept in registers
                     // from before the partition loop, where the table path's own addresses already fill the 80)
                     u32 ln = lane;
@@ -1406,26 +1499,64 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
 #endif
                 PHASE(6)
                 CNT(7, n_new)
+                // the slice insert_body takes for a fresh partition of one chunk, from the private chunk (of a pair: A's, then B's,
+                // a refill may fall between the two); n: the partition's new entries, 0 where the slice could not be had
+                auto take_slice = [&](u32& n, unsigned long long& off, u32& cap) {
+                    cap = 0;
+                    if (n) {
+                        const unsigned long long want = grow_cap(n);  // <= grow_cap(MAXI) = 248 at three slots: far below ARENA_CHUNK / 8 (asserted above)
+                        if (acur + want > aend) {
+                            garbage += aend - acur;
+                            unsigned long long got = 0;
+                            if (lane == 0) got = atomicAdd(ix.cursor, (unsigned long long)ARENA_CHUNK);
+                            acur = first_lane64(got);
+                            aend = acur + ARENA_CHUNK;
+                        }
+                        if (acur + want > ix.arena_cap) {  // must not happen (the host reserves the bound): drop, flag
+                            if (lane == 0) atomicOr(ix.err, 2u);
+                            n = 0;
+                        } else {
+                            off = acur;
+                            acur += want;
+                            cap = (u32)want;
+                        }
+                    }
+                };
+                if (INSERT_PAIR && nB) {  // wave-uniform: the pair's tail, a block of its own (the single tail below is the parent's)
+                    // instance i is entry i of A's slice, or entry i - ninstA of B's; B's bucket bits go to the high half of the word
+                    unsigned long long off = d.off, off_b = dn.off;
+                    u32 cap = 0, cap_b = 0, n_new_b = n_new - ninstA;
+                    n_new = ninstA;
+                    take_slice(n_new, off, cap);
+                    take_slice(n_new_b, off_b, cap_b);
+                    u32 ln = lane, bm0 = 0;
+                    asm volatile("" : "+v"(ln));
+#pragma unroll
+                    for (u32 it = 0; it < NIL; it++) {
+                        const u32 i = it * 64 + ln;
+                        const bool in_b = i >= ninstA;
+                        if (i < ninst && (in_b ? n_new_b : n_new)) {
+                            const unsigned long long at = (in_b ? off_b - ninstA : off) + i;
+                            store_key<KW>(ix, at, li.klo[it], li.khi[it]);
+                            ix.counts[at] = (uint8_t)count8<SAT>(new_word[it] >> WI_CNT_SHIFT);
+                            const u32 bl = (u32)shr128(mk128(li.klo[it], li.khi[it]), KBITS).lo & ((1u << SHIFT) - 1);
+                            bm0 |= 1u << (bl + (in_b ? 16u : 0u));  // (this form: the others tried cost two registers beyond the 80)
+                        }
+                    }
+                    bm0 = wave_or_all(bm0);
+                    if (ln == 0) {
+                        ix.dir[part] = DirEnt{off, n_new, cap};
+                        ix.dir[dn.part] = DirEnt{off_b, n_new_b, cap_b};
+                        const u64 first = ((u64)part << SHIFT) >> P.ext_bits, first_b = ((u64)dn.part << SHIFT) >> P.ext_bits;
+                        const u32 bits = (bm0 & 0xffffu) << (first & 31), bits_b = (bm0 >> 16) << (first_b & 31);
+                        if (bits && (!ix.bits_check || (ix.bucket_bits[first >> 5] & bits) != bits)) atomicOr(&ix.bucket_bits[first >> 5], bits);
+                        if (bits_b && (!ix.bits_check || (ix.bucket_bits[first_b >> 5] & bits_b) != bits_b)) atomicOr(&ix.bucket_bits[first_b >> 5], bits_b);
+                    }
+                    break;
+                }
                 unsigned long long off = d.off;
                 u32 cap = 0;
-                if (n_new) {  // the slice insert_body takes for a fresh partition of one chunk, from the private chunk
-                    const unsigned long long want = grow_cap(n_new);  // <= grow_cap(MAXI) = 248 at three slots: far below ARENA_CHUNK / 8 (asserted above)
-                    if (acur + want > aend) {
-                        garbage += aend - acur;
-                        unsigned long long got = 0;
-                        if (lane == 0) got = atomicAdd(ix.cursor, (unsigned long long)ARENA_CHUNK);
-                        acur = first_lane64(got);
-                        aend = acur + ARENA_CHUNK;
-                    }
-                    if (acur + want > ix.arena_cap) {  // must not happen (the host reserves the bound): drop, flag
-                        if (lane == 0) atomicOr(ix.err, 2u);
-                        n_new = 0;
-                    } else {
-                        off = acur;
-                        acur += want;
-                        cap = (u32)want;
-                    }
-                }
+                take_slice(n_new, off, cap);
                 PHASE(7)
                 u32 bm0 = 0;
 #pragma unroll
@@ -1448,10 +1579,19 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
                     if (bits && (!ix.bits_check || (ix.bucket_bits[first >> 5] & bits) != bits)) atomicOr(&ix.bucket_bits[first >> 5], bits);
                 }
             } while (0);
+            if (INSERT_PAIR && step == 2) {  // wave-uniform: B went with A, the next head is the one behind it
+                tn = t + 2;
+                dn = PartDesc{};
+                if (tn < t_end) dn = desc[tn];
+            }
             d = dn;
-            if (tn < t_end) rr = load_part_recs(P, src, d.part, d.r_begin, d.r_begin, min(d.n_rec, (u32)WI_MAX_REC), lane);
+            if (INSERT_PAIR) {
+                nB = 0;
+                if (tn < t_end) nB = request(d, tn, t_end, rr);
+            } else if (tn < t_end) rr = load_part_recs(P, src, d.part, d.r_begin, d.r_begin, min(d.n_rec, (u32)WI_MAX_REC), lane);
             PHASE(9)
         }
+        if (INSERT_PAIR && pairs && lane == 0) atomicAdd(n_pair, pairs);
         if (left_mask) {  // wave-uniform
             const u32 n = (u32)__popcll(left_mask);
             u32 at = 0;
@@ -1474,8 +1614,9 @@ __device__ __forceinline__ void insert_first_body(const BriskParams& P, const Re
 template <u32 NW, u32 KB, u32 SHIFT, bool SAT = false, u32 NIL = NI_LEAN>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WI_WAVES_PER_EU_FIRST, WI_WAVES_PER_EU_FIRST_MAX))) k_insert_first(BriskParams P, RecSrc src, const PartDesc* __restrict__ desc,
                                                                                                           u32 n_touched, IndexDev ix, u32* __restrict__ work_counter,
-                                                                                                          u32* __restrict__ left_list, u32* __restrict__ n_left, u32* __restrict__ n_clean) {
-    insert_first_body<NIL, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter, left_list, n_left, n_clean);
+                                                                                                          u32* __restrict__ left_list, u32* __restrict__ n_left, u32* __restrict__ n_clean,
+                                                                                                          u32* __restrict__ n_pair) {
+    insert_first_body<NIL, NW, KB, SHIFT, SAT>(P, src, desc, n_touched, ix, work_counter, left_list, n_left, n_clean, n_pair);
 }
 
 // bucket occupancy for partitions wider than 64 buckets (small part_bits): one pass over all entries

@@ -120,7 +120,7 @@ SYMBOLS = [
     "brisk_hip_abi_version", "brisk_hip_create", "brisk_hip_destroy", "brisk_hip_clear", "brisk_hip_last_error", "brisk_hip_sync",
     "brisk_hip_get_layout", "brisk_hip_insert_reads", "brisk_hip_insert_packed", "brisk_hip_get_reads", "brisk_hip_lookup",
     "brisk_hip_enumerate", "brisk_hip_stats", "brisk_hip_memory_info", "brisk_hip_insert_slack", "brisk_hip_reallocate", "brisk_hip_checksum", "brisk_hip_scan_packed", "brisk_hip_scan_bound", "brisk_hip_route_records",
-    "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_debug_guard_count", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
+    "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_debug_guard_count", "brisk_hip_debug_touched", "brisk_hip_debug_directory", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
     "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune",
     "brisk_hip_read_profile_reads", "brisk_hip_read_profile_packed",
     "brisk_hip_scan_kmers", "brisk_hip_record_kmers", "brisk_hip_answer_records", "brisk_hip_place_answers", "brisk_hip_profile_slots",
@@ -1243,6 +1243,25 @@ class BriskHip:
         self.L.brisk_hip_debug_guard_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]  # (bound on use: a test hook, not part of load())
         self._chk(self.L.brisk_hip_debug_guard_count(self.h, C.byref(n)))
         return int(n.value)
+
+    def debug_touched(self) -> np.ndarray:
+        """The partitions the last record insert touched, in the order its insert kernels walked them (a test hook)."""
+        f = self.L.brisk_hip_debug_touched  # (bound on use: a test hook, not part of load())
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        n = C.c_uint64(0)
+        self._chk(f(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(int(n.value), 1), np.uint32)
+        self._chk(f(self.h, out.ctypes.data, len(out), C.byref(n)))
+        return out[: int(n.value)]
+
+    def debug_directory(self, parts):
+        """(entries in use, slice capacity) of the given partitions, two uint32 arrays (a test hook)."""
+        f = self.L.brisk_hip_debug_directory  # (bound on use)
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        p = np.ascontiguousarray(parts, np.uint32)
+        cnt, cap = np.zeros(max(len(p), 1), np.uint32), np.zeros(max(len(p), 1), np.uint32)
+        self._chk(f(self.h, p.ctypes.data, len(p), cnt.ctypes.data, cap.ctypes.data))
+        return cnt[: len(p)], cap[: len(p)]
 
     # ---- measurement
     def profile_enable(self, on: bool = True):

@@ -804,6 +804,12 @@ int brisk_hip_debug_order_keys(brisk_hip_index *h, const uint64_t *mmers, uint64
  * brisk_hip_debug_guard_count: how many keys of the handle's LAST brisk_hip_debug_order_keys call had a class sum inside the
  * guard band and were decided by the exact FP64 fold (0 after an exact != 0 call; all of them in a -DCLS_FORCE_GUARD build). */
 int brisk_hip_debug_guard_count(brisk_hip_index *h, uint64_t *n_guard);
+/* brisk_hip_debug_touched: the partitions the handle's LAST record insert touched, in the order its insert kernels walked them
+ * (ascending inside a block of 8192 partitions; the blocks in the order the device took them, which is not the same from run to
+ * run).  *n: their number; the first min(cap, *n) go to parts.  Valid until the handle's next insert or query.  HOST arrays. */
+int brisk_hip_debug_touched(brisk_hip_index *h, uint32_t *parts, uint64_t cap, uint64_t *n);
+/* brisk_hip_debug_directory: entries in use and slice capacity of n partitions.  HOST arrays. */
+int brisk_hip_debug_directory(brisk_hip_index *h, const uint32_t *parts, uint64_t n, uint32_t *cnt, uint32_t *cap);
 
 /* ---- measurement ----------------------------------------------------------- */
 /* With profiling on, every kernel launch is bracketed by HIP events on the
