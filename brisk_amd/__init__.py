@@ -11,3 +11,4 @@ from .hipapi import READ_INTERVAL_DTYPE, SELECT_KINDS, intervals_from_profile, s
 from .hipapi import JOINT_ABSENT, joint_figures, joint_spectrum_from_entries  # noqa: F401
 from .hipapi import FRAGMENT_DTYPE, INTAKE_BLOCK, INTAKE_STATS_FIELDS, fragments_from_reads, intake_rule  # noqa: F401
 from .hipapi import PAIR_COUNTS_FIELDS, PAIR_MODES, compose_intervals, intervals_from_fragments, pair_intervals, split_pairs  # noqa: F401
+from .hipapi import SPLIT_STATS_FIELDS, fragments_from_slots  # noqa: F401

@@ -39,6 +39,10 @@
 //                    ">read_index start len".  trim (the default): the stretch covered by the first longest run of k-mers with count
 //                    >= N (--solid, default 2); median:LO:HI: the whole read when LO <= its median count <= HI; present:LO:HI: when
 //                    LO <= the permille of its k-mers that are in the index <= HI.  --min-len L: at least L nucleotides (default k)
+//   --extract FILE --rule split [--solid N] [--min-len L]
+//                    the same reads through brisk_hip_split_reads: a read is cut at its weak k-mers, and every run of k-mers with count >= N
+//                    that covers at least L nucleotides (default k) is a record of its own, ">read_index start len", ordered by read, then
+//                    by start; the counters of brisk_hip_split_stats go to stderr.  Not with --paired (exit status 2)
 //   --paired [--mate FILE] [--pair-mode each|all|any]
 //                    the input holds paired reads, one record a read: interleaved (records 2p and 2p + 1 are the mates of pair p), or,
 //                    with --mate FILE, record i of the input and record i of FILE (of the same kind, FASTA or FASTQ) are a pair.  A
@@ -423,6 +427,7 @@ int main(int argc_in, char** argv_in) {
         "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]] [--paired [--mate FILE] [--pair-mode each|all|any]]; FASTA \"-\": no reads; a FILE may be a snapshot; an input that starts with '@' is FASTQ)\n"
         "  --min-qual Q   FASTQ input: a base of quality below Q (0..93) is cut like an N, on the device; --qual-base 33|64 (default 33)\n"
         "  --paired   one record a read, interleaved or zipped with --mate FILE; --extract PREFIX then writes PREFIX.1.fa PREFIX.2.fa PREFIX.s.fa (FASTQ input allowed)\n"
+        "  --rule split   with --extract FILE: every run of k-mers with count >= N (--solid) as a record of its own, \">read_index start len\"; the counters go to stderr\n"
         "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+";
     for (int i = 0; i < argc_in; i++) {
         if (i > 0 && (!strcmp(argv_in[i], "--help") || !strcmp(argv_in[i], "-h"))) {
@@ -571,7 +576,8 @@ int main(int argc_in, char** argv_in) {
     rule.kind = BRISK_HIP_SELECT_SOLID_RUN;
     rule.min_len = (uint32_t)min_len;
     rule.hi = 0xffffffffu;
-    if (rule_text && strcmp(rule_text, "trim")) {  // median:LO:HI or present:LO:HI
+    const bool rule_split = rule_text && !strcmp(rule_text, "split");  // every solid run of a read, not one interval: brisk_hip_split_reads
+    if (rule_text && strcmp(rule_text, "trim") && !rule_split) {  // median:LO:HI or present:LO:HI
         unsigned long lo = 0, hi = 0;
         char tail = 0;
         if (sscanf(rule_text, "median:%lu:%lu%c", &lo, &hi, &tail) == 2) rule.kind = BRISK_HIP_SELECT_MEDIAN;
@@ -618,6 +624,10 @@ int main(int argc_in, char** argv_in) {
     }
     if (fastq_main && (profile_file || (extract_file && !paired))) {
         std::cerr << (profile_file ? "--profile" : "--extract") << " reads the input again as FASTA: not with a FASTQ input" << std::endl;
+        return 2;
+    }
+    if (rule_split && paired) {
+        std::cerr << "--rule split cuts reads into several fragments: not with --paired" << std::endl;
         return 2;
     }
     if (paired) {  // whole pairs, before anything is counted
@@ -904,6 +914,44 @@ int main(int argc_in, char** argv_in) {
             }
             if (extract_file && paired) {
                 if (int erc = extract_paired(h, argv[2], mate_file, fastq_main, extract_file, rule, (uint32_t)solid, intake, pair_mode, batch_bases)) return erc;
+            } else if (extract_file && rule_split) {  // the reads of the input again, against the final index: one record per fragment, in table order
+                std::ofstream out(extract_file);
+                brisk_hip_split_stats sum{};
+                uint64_t read_index = 0;
+                if (!no_reads) {
+                    FastaBatcher batches(argv[2], batch_bases);
+                    FastaBatch bt;
+                    std::vector<brisk_hip_fragment> frags;
+                    while (batches.next(bt)) {
+                        brisk_hip_split_stats st{};
+                        int src = brisk_hip_split_reads(h, bt.flat.data(), bt.offs.data(), bt.size(), (uint32_t)solid, (uint32_t)min_len, frags.data(), frags.size(), &st);
+                        if (src == BRISK_HIP_ECAPACITY) {  // (the refused call has counted them)
+                            frags.resize(st.n_fragments);
+                            src = brisk_hip_split_reads(h, bt.flat.data(), bt.offs.data(), bt.size(), (uint32_t)solid, (uint32_t)min_len, frags.data(), frags.size(), &st);
+                        }
+                        if (src != BRISK_HIP_OK) {
+                            std::cerr << "--extract: " << brisk_hip_last_error(h) << std::endl;
+                            return 1;
+                        }
+                        for (uint64_t j = 0; j < st.n_fragments; j++) {
+                            const brisk_hip_fragment& f = frags[j];
+                            out << ">" << read_index + f.read << " " << f.start << " " << f.len << "\n";
+                            out.write(bt.flat.data() + bt.offs[f.read] + f.start, f.len);
+                            out << "\n";
+                        }
+                        read_index += bt.size();
+                        const uint64_t* add = (const uint64_t*)&st;
+                        for (size_t i = 0; i < sizeof(st) / 8; i++) ((uint64_t*)&sum)[i] += add[i];
+                    }
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "--extract " << extract_file << ": write failed" << std::endl;
+                    return 1;
+                }
+                std::cerr << "extract " << extract_file << ": " << sum.n_fragments << " fragments of " << sum.n_reads_kept << " of " << sum.n_reads << " reads, " << sum.n_nts_out << " of "
+                          << sum.n_nts_in << " nucleotides, " << sum.n_solid << " of " << sum.n_slots << " k-mers solid, " << sum.n_short << " in short runs (--rule split, solid >= "
+                          << solid << ")" << std::endl;
             } else if (extract_file) {  // the reads of the input again, against the final index: what the rule keeps of them, as FASTA
                 std::ofstream out(extract_file);
                 uint64_t read_index = 0, kept = 0, kept_nts = 0;

@@ -611,6 +611,188 @@ int check_clean_pairs(brisk_hip_index* h, const brisk_hip_intake_rule* intake, b
     return check_pairs(h, n_reads, pair_mode, who);
 }
 
+// ---- read splitting: the solid runs of every read as fragments (no reference counterpart; kernels: brisk_split.hip over the
+// intake's passes; the gather is brisk_extract.hip's) ----
+static_assert(sizeof(brisk_hip_split_stats) == 64 && offsetof(brisk_hip_split_stats, n_nts_out) == 56, "include/brisk_hip.h: eight 64-bit counters");
+
+// a run of s slots covers s + k - 1 nucleotides: at least max(min_len, k) of them when s >= this
+u32 split_min_slots(const brisk_hip_index* h, u32 min_len) { return std::max<u32>(min_len, h->P.k) - h->P.k + 1; }
+
+// The read table of a device call, checked as a whole (one pass, a host synchronisation); *n_nts: starts[n_reads] - starts[0].
+// fit_record: a read whose nucleotides pass the fragment record's 32 bits is refused too.
+int split_check_table(brisk_hip_index* h, const u64* d_starts, u64 n_reads, const char* who, bool fit_record, u64* n_nts) {
+    int rc;
+    if (n_reads > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": more reads than one launch covers");
+    if ((rc = ensure(h, h->ink_tmp, 64))) return rc;
+    unsigned long long* d_flags = (unsigned long long*)h->ink_tmp.p;
+    HIPCHK(h, hipMemsetAsync(d_flags, 0, 8, h->stream));
+    hipLaunchKernelGGL(k_intake_check, dim3(nblocks(n_reads, 256)), dim3(256), 0, h->stream, d_starts, n_reads, d_flags);
+    if ((rc = launch_check(h, "k_intake_check"))) return rc;
+    u64 got[3] = {0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(got, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(got + 1, d_starts, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(got + 2, d_starts + n_reads, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (got[0] & 1) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": read offsets do not ascend (offsets[i + 1] < offsets[i])");
+    if (fit_record && (got[0] & 2)) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": a read of 2^32 nucleotides or more does not fit the fragment record");
+    *n_nts = got[2] - got[1];
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held.  One batch: d_slots[n_slots > 0] are the slots of the reads of d_starts[0 .. n_reads], and h->slot_buf
+// holds their slot bases (slot_bases / kmers_packed_impl).  The intake's passes over a mask of solid slots: the counts first (a host
+// synchronisation), then the runs {read, first slot, slots} into h->ink_tab, in input order, and *n_kept reads that have one.
+// *run_slots: the slots of the runs of at least min_slots; *n_short: the solid slots of the shorter ones.
+int split_runs_impl(brisk_hip_index* h, const uint16_t* d_slots, const u64* d_starts, u64 n_reads, u64 n_slots, u32 solid_min, u32 min_slots, u64* n_frag, u64* n_kept,
+                    u64* run_slots, u64* n_short) {
+    int rc;
+    *n_frag = *n_kept = *run_slots = *n_short = 0;
+    const u64 nb64 = (n_slots + INTAKE_BLOCK - 1) / INTAKE_BLOCK;
+    if (nb64 > 0x7fffffffull || n_reads > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "split: more slots or reads than one launch covers");
+    const u32 nb = (u32)nb64, nb2 = nblocks(nb, INTAKE_SCAN);
+    const u64 n_lanes = nb64 * 256;
+    if ((rc = ensure(h, h->split_off, (n_reads + 1) * 8))) return rc;
+    if ((rc = ensure(h, h->ink_mask, n_lanes * 4))) return rc;
+    // [the blocks' run begins, nb + 1][block sums: fragments, their slots, short, nb + 1 each][the partials of the two-level scans, nb2 + 1
+    // for each of the four][per block, nb + 1: the first read that starts in or behind it]
+    if ((rc = ensure(h, h->ink_tmp, (5 * ((size_t)nb + 1) + 4 * ((size_t)nb2 + 1)) * 8))) return rc;
+    u64* d_soff = (u64*)h->split_off.p;
+    u32* d_mask = (u32*)h->ink_mask.p;
+    u64* d_carry = (u64*)h->ink_tmp.p;
+    u64 *d_bs[3], *d_part[4];
+    for (int i = 0; i < 3; i++) d_bs[i] = d_carry + (size_t)(i + 1) * (nb + 1);
+    for (int i = 0; i < 4; i++) d_part[i] = d_carry + (size_t)4 * (nb + 1) + (size_t)i * (nb2 + 1);
+    u64* d_first = d_carry + (size_t)4 * (nb + 1) + (size_t)4 * (nb2 + 1);
+    HIPCHK(h, hipMemsetAsync(d_mask, 0, n_lanes * 4, h->stream));
+    hipLaunchKernelGGL(k_split_offsets, dim3(nblocks(n_reads + 1, 256)), dim3(256), 0, h->stream, d_starts, (const u64*)h->slot_buf.p, n_reads, n_slots, d_soff);
+    hipLaunchKernelGGL(k_intake_bounds, dim3(nblocks(n_reads + 1, 256)), dim3(256), 0, h->stream, (const u64*)d_soff, n_reads, (u64)0, n_lanes, d_mask);
+    hipLaunchKernelGGL(k_intake_first, dim3(nblocks((u64)nb + 1, 256)), dim3(256), 0, h->stream, (const u64*)d_soff, n_reads, (u64)0, (u64)nb, d_first);
+    hipLaunchKernelGGL(k_split_mask, dim3(nb), dim3(256), 0, h->stream, d_slots, n_slots, solid_min, d_mask, d_carry);
+    hipLaunchKernelGGL(k_intake_reduce<true>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_carry, nb, d_part[3]);
+    hipLaunchKernelGGL(k_intake_top, dim3(1), dim3(1024), 0, h->stream, d_part[3], nb2);
+    hipLaunchKernelGGL(k_intake_spread<true>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, d_carry, nb, (const u64*)d_part[3]);
+    hipLaunchKernelGGL(k_intake_count, dim3(nb), dim3(256), 0, h->stream, (const u32*)d_mask, n_lanes, (const u64*)d_carry, min_slots, d_bs[0], d_bs[1], d_bs[2]);
+    for (int i = 0; i < 3; i++) {  // the totals of all three; the exclusive prefixes of the fragments and their slots, which the apply pass takes
+        hipLaunchKernelGGL(k_intake_reduce<false>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_bs[i], nb, d_part[i]);
+        hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_part[i], nb2);
+        if (i < 2) hipLaunchKernelGGL(k_intake_spread<false>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, d_bs[i], nb, (const u64*)d_part[i]);
+    }
+    if ((rc = launch_check(h, "k_split_offsets / k_intake_bounds / k_intake_first / k_split_mask / k_intake_reduce / k_intake_top / k_intake_spread / k_intake_count / k_slot_top"))) return rc;
+    u64 tot[3] = {0, 0, 0};
+    for (int i = 0; i < 3; i++) HIPCHK(h, hipMemcpyAsync(tot + i, d_part[i] + nb2, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n_frag = tot[0];
+    *run_slots = tot[1];
+    *n_short = tot[2];
+    const u64 nf = tot[0];
+    if (!nf) return BRISK_HIP_OK;
+    if (nf > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "split: more fragments than one launch covers");
+    const u32 nbk = nblocks(nf, 256), nbk2 = nblocks(nbk, INTAKE_SCAN);
+    // [rows][their starts in slots, nf + 1, and source positions, nf: k_intake_apply writes them, nothing reads them][kept reads per block of rows, and the partials]
+    if ((rc = ensure(h, h->ink_tab, nf * 16 + (nf + 1) * 8 + nf * 8 + ((size_t)nbk + 1) * 8 + ((size_t)nbk2 + 1) * 8))) return rc;
+    IntakeFragment* d_rows = (IntakeFragment*)h->ink_tab.p;
+    u64* d_st = (u64*)(d_rows + nf);
+    u64* d_src = d_st + nf + 1;
+    u64* d_kept = d_src + nf;
+    u64* d_kept2 = d_kept + nbk + 1;
+    hipLaunchKernelGGL(k_intake_apply, dim3(nb), dim3(256), 0, h->stream, (const u32*)d_mask, n_lanes, (const u64*)d_carry, min_slots, (const u64*)d_bs[0], (const u64*)d_bs[1],
+                       (const u64*)d_soff, n_reads, (u64)0, (const u64*)d_first, d_rows, d_st, d_src);
+    hipLaunchKernelGGL(k_intake_kept, dim3(nbk), dim3(256), 0, h->stream, (const IntakeFragment*)d_rows, nf, d_kept);
+    hipLaunchKernelGGL(k_intake_reduce<false>, dim3(nbk2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_kept, nbk, d_kept2);
+    hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_kept2, nbk2);
+    if ((rc = launch_check(h, "k_intake_apply / k_intake_kept / k_intake_reduce / k_slot_top"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(n_kept, d_kept2 + nbk2, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+// the runs in h->ink_tab as fragments of the call's reads (the batch begins at read r0), queued on the stream
+int split_rows(brisk_hip_index* h, u64 n_frag, u64 r0, IntakeFragment* d_out) {
+    hipLaunchKernelGGL(k_split_rows, dim3(nblocks(n_frag, 256)), dim3(256), 0, h->stream, (const IntakeFragment*)h->ink_tab.p, n_frag, (u32)h->P.k, r0, d_out);
+    return launch_check(h, "k_split_rows");
+}
+
+// One batch of a composed call: its runs counted into *st and appended, as fragments, to the call's table in h->split_tab (which
+// grows by copying: a call's table is small beside its reads).  st->n_fragments: the rows the table holds before the batch.
+int split_batch(brisk_hip_index* h, const uint16_t* d_slots, const u64* d_starts, u64 n_reads, u64 n_slots, u64 r0, u32 solid_min, u32 min_slots, brisk_hip_split_stats* st) {
+    int rc;
+    st->n_slots += n_slots;
+    if (!n_slots) return BRISK_HIP_OK;
+    u64 nf = 0, kept = 0, run_slots = 0, n_short = 0;
+    if ((rc = split_runs_impl(h, d_slots, d_starts, n_reads, n_slots, solid_min, min_slots, &nf, &kept, &run_slots, &n_short))) return rc;
+    const u64 have = st->n_fragments;
+    st->n_fragments += nf;
+    st->n_reads_kept += kept;
+    st->n_solid += run_slots + n_short;
+    st->n_short += n_short;
+    st->n_nts_out += run_slots + nf * (h->P.k - 1);
+    if (!nf) return BRISK_HIP_OK;
+    if (h->split_tab.bytes < (have + nf) * 16) {
+        DevBuf grown;
+        if ((rc = ensure(h, grown, std::max<size_t>((have + nf) * 16, 2 * h->split_tab.bytes)))) return rc;
+        if (have) HIPCHK(h, hipMemcpyAsync(grown.p, h->split_tab.p, have * 16, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->split_tab.p) HIPCHK(h, hipFree(h->split_tab.p));
+        h->split_tab = grown;
+    }
+    return split_rows(h, nf, r0, (IntakeFragment*)h->split_tab.p + have);
+}
+
+// The handle's lock is held.  The rows of a fragment table out of a packed stream: the rows checked and their nucleotides counted
+// first (one pass, a host synchronisation), then -- only when the rows are valid and the output has room -- the starts, the source
+// positions and brisk_hip_extract_packed's gather: a refused call writes nothing.  out.packed == NULL: the starts only.
+// check_table: the read table is not known to ascend.
+int fragment_gather_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, const IntakeFragment* d_frags, u64 n_frags, const OutStream& out, bool check_table,
+                         const char* who, u64* n_out_nts) {
+    int rc;
+    *n_out_nts = 0;
+    u64 n_nts = 0;
+    if (check_table && n_reads) {
+        u64 unused = 0;
+        if ((rc = split_check_table(h, d_starts, n_reads, who, false, &unused))) return rc;  // (a long read is no fault here: rows address its first 2^32 nucleotides)
+    }
+    const u32 nb = nblocks(n_frags, 256 * SPLIT_ITEMS);
+    u64* d_bs = nullptr;
+    if (n_frags) {
+        if (n_frags > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": more rows than one launch covers");
+        // [64 bytes: the flag][block sums of the rows' nucleotides, nb + 1]
+        if ((rc = ensure(h, h->ext_tmp, 64 + ((size_t)nb + 1) * 8))) return rc;
+        unsigned long long* d_flags = (unsigned long long*)h->ext_tmp.p;
+        d_bs = (u64*)((char*)h->ext_tmp.p + 64);
+        HIPCHK(h, hipMemsetAsync(d_flags, 0xff, 8, h->stream));
+        hipLaunchKernelGGL(k_split_frag_block, dim3(nb), dim3(256), 0, h->stream, d_frags, n_frags, d_starts, n_reads, d_bs, d_flags);
+        hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bs, nb);
+        if ((rc = launch_check(h, "k_split_frag_block / k_slot_top"))) return rc;
+        u64 got[2] = {0, 0};
+        HIPCHK(h, hipMemcpyAsync(got, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(got + 1, d_bs + nb, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (got[0] != ~0ull)
+            return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": row " + std::to_string(got[0]) + " of the fragment table names a read >= n_reads, has len == 0, or ends beyond its read (start + len > its length)");
+        n_nts = got[1];
+    }
+    *n_out_nts = n_nts;
+    const u64 n_words = (n_nts + 15) / 16;
+    if (out.packed && out.cap_words < n_words + 2)
+        return fail(h, BRISK_HIP_ECAPACITY, std::string(who) + ": " + std::to_string(n_nts) + " nucleotides need " + std::to_string(n_words + 2) + " words, out_cap_words is " + std::to_string(out.cap_words));
+    if (!n_frags) {  // no row: the empty stream
+        HIPCHK(h, hipMemsetAsync(out.starts, 0, 8, h->stream));
+        if (out.packed) HIPCHK(h, hipMemsetAsync(out.packed, 0, 8, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    }
+    if ((rc = ensure(h, h->ext_src, n_frags * 8))) return rc;
+    hipLaunchKernelGGL(k_split_frag_apply, dim3(nb), dim3(256), 0, h->stream, d_frags, n_frags, d_starts, (const u64*)d_bs, out.starts, (u64*)h->ext_src.p);
+    if ((rc = launch_check(h, "k_split_frag_apply"))) return rc;
+    if (out.packed) {
+        if (n_words + 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": more output words than one launch covers");
+        hipLaunchKernelGGL(k_extract_gather, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_packed, (const u64*)out.starts, (const u64*)h->ext_src.p, n_frags, n_words, out.packed);
+        if ((rc = launch_check(h, "k_extract_gather"))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -935,6 +1117,121 @@ BRISK_API int brisk_hip_clean_pairs_reads(brisk_hip_index* h, const char* bases,
         add_counters(counts, pc);
         return BRISK_HIP_OK;
     }, 2);
+}
+
+// ---- read splitting ----
+BRISK_API int brisk_hip_solid_runs(brisk_hip_index* h, const uint16_t* d_slots, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, uint32_t min_len,
+                                   brisk_hip_fragment* d_out_frags, uint64_t frag_cap, brisk_hip_split_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!stats || (n_reads && !d_starts) || (frag_cap && !d_out_frags)) return fail(h, BRISK_HIP_EINVAL, "solid_runs: null pointer");
+    memset(stats, 0, sizeof(*stats));
+    stats->n_reads = n_reads;
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    int rc;
+    u64 ns = 0, nf = 0, run_slots = 0;
+    if ((rc = split_check_table(h, d_starts, n_reads, "solid_runs", true, &stats->n_nts_in))) return rc;
+    if ((rc = count_kmers(h, d_starts, n_reads, &ns))) return rc;
+    stats->n_slots = ns;
+    if (!ns) return BRISK_HIP_OK;
+    if (!d_slots) return fail(h, BRISK_HIP_EINVAL, "solid_runs: null pointer");
+    if ((rc = slot_bases(h, d_starts, n_reads))) return rc;
+    if ((rc = split_runs_impl(h, d_slots, d_starts, n_reads, ns, solid_min, split_min_slots(h, min_len), &nf, &stats->n_reads_kept, &run_slots, &stats->n_short))) return rc;
+    stats->n_fragments = nf;
+    stats->n_solid = run_slots + stats->n_short;
+    stats->n_nts_out = run_slots + nf * (h->P.k - 1);
+    if (frag_cap < nf) return fail(h, BRISK_HIP_ECAPACITY, "solid_runs: " + std::to_string(nf) + " fragments, frag_cap is " + std::to_string(frag_cap));
+    if (!nf) return BRISK_HIP_OK;
+    if ((rc = split_rows(h, nf, 0, (IntakeFragment*)d_out_frags))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_extract_fragments_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, const brisk_hip_fragment* d_frags,
+                                                 uint64_t n_frags, uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, uint64_t* n_out_nts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!n_out_nts || !d_out_packed || !d_out_starts || (n_reads && (!d_packed || !d_starts)) || (n_frags && !d_frags)) return fail(h, BRISK_HIP_EINVAL, "extract_fragments_packed: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    return fragment_gather_impl(h, d_packed, d_starts, n_reads, (const IntakeFragment*)d_frags, n_frags, {d_out_packed, out_cap_words, d_out_starts, nullptr}, true,
+                                "extract_fragments_packed", n_out_nts);
+}
+
+BRISK_API int brisk_hip_split_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, uint32_t min_len,
+                                     uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, brisk_hip_fragment* d_out_frags, uint64_t frag_cap,
+                                     brisk_hip_split_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "split_packed")) return wrc;
+    if (!stats || !d_out_starts || (n_reads && (!d_packed || !d_starts))) return fail(h, BRISK_HIP_EINVAL, "split_packed: null pointer");
+    if (!d_out_packed && out_cap_words) return fail(h, BRISK_HIP_EINVAL, "split_packed: out_cap_words without d_out_packed");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    int rc;
+    memset(stats, 0, sizeof(*stats));
+    stats->n_reads = n_reads;
+    if (n_reads) {
+        if ((rc = split_check_table(h, d_starts, n_reads, "split_packed", true, &stats->n_nts_in))) return rc;
+        // a sibling of profile_packed_batches: a batch's slots into kout_tmp, and its runs instead of its records
+        const u64 batch = profile_batch_limit(h);
+        const u32 min_slots = split_min_slots(h, min_len);
+        for (u64 r0 = 0; r0 < n_reads; r0 += batch) {
+            const u64 nb = std::min<u64>(batch, n_reads - r0);
+            u64 ns = 0;
+            if ((rc = count_kmers(h, d_starts + r0, nb, &ns))) return rc;
+            if (ns) {
+                if ((rc = ensure(h, h->kout_tmp, ns * 2))) return rc;
+                HIPCHK(h, hipMemsetAsync(h->kout_tmp.p, 0, ns * 2, h->stream));
+                if ((rc = kmers_packed_impl(h, d_packed, d_starts + r0, nb, (uint16_t*)h->kout_tmp.p, ns))) return rc;
+            }
+            if ((rc = split_batch(h, (const uint16_t*)h->kout_tmp.p, d_starts + r0, nb, ns, r0, solid_min, min_slots, stats))) return rc;
+        }
+        if ((rc = check_device_flags(h))) return rc;
+    }
+    const u64 nf = stats->n_fragments, need_words = (stats->n_nts_out + 15) / 16 + 2;
+    if (frag_cap < nf) return fail(h, BRISK_HIP_ECAPACITY, "split_packed: " + std::to_string(nf) + " fragments, frag_cap is " + std::to_string(frag_cap));
+    if (d_out_packed && out_cap_words < need_words)
+        return fail(h, BRISK_HIP_ECAPACITY, "split_packed: " + std::to_string(stats->n_nts_out) + " nucleotides need " + std::to_string(need_words) + " words, out_cap_words is " + std::to_string(out_cap_words));
+    u64 n_nts = 0;
+    if ((rc = fragment_gather_impl(h, d_packed, d_starts, n_reads, (const IntakeFragment*)h->split_tab.p, nf, {d_out_packed, out_cap_words, d_out_starts, nullptr}, false, "split_packed", &n_nts))) return rc;
+    if (n_nts != stats->n_nts_out) return fail(h, BRISK_HIP_EHIP, "split_packed: the stream and the counters disagree");
+    if (d_out_frags && nf) {
+        HIPCHK(h, hipMemcpyAsync(d_out_frags, h->split_tab.p, nf * 16, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_split_reads(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t solid_min, uint32_t min_len,
+                                    brisk_hip_fragment* out_frags, uint64_t frag_cap, brisk_hip_split_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "split_reads")) return wrc;
+    if (!stats || (frag_cap && !out_frags) || (n_reads && (!bases || !offsets))) return fail(h, BRISK_HIP_EINVAL, "split_reads: null pointer");
+    for (u64 r = 0; r < n_reads; r++) {
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (offsets[r + 1] - offsets[r] > 0xffffffffull) return fail(h, BRISK_HIP_EINVAL, "split_reads: a read of 2^32 nucleotides or more does not fit the fragment record");
+    }
+    memset(stats, 0, sizeof(*stats));
+    stats->n_reads = n_reads;
+    if (!n_reads) return BRISK_HIP_OK;
+    stats->n_nts_in = offsets[n_reads] - offsets[0];
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    const u32 min_slots = split_min_slots(h, min_len);
+    // profile_batch has left the batch's slots in kout_tmp and their bases in slot_buf: the runs are taken from them
+    int rc = profile_host_batches(h, bases, offsets, n_reads, solid_min, [&](u64 r0, u64 nr, const ReadProfile*) -> int {
+        return split_batch(h, (const uint16_t*)h->kout_tmp.p, (const u64*)h->starts_tmp.p, nr, host_slots(offsets, r0, r0 + nr, h->P.k), r0, solid_min, min_slots, stats);
+    });
+    if (rc) return rc;
+    const u64 nf = stats->n_fragments;
+    if (frag_cap < nf) return fail(h, BRISK_HIP_ECAPACITY, "split_reads: " + std::to_string(nf) + " fragments, frag_cap is " + std::to_string(frag_cap));
+    if (nf) {
+        HIPCHK(h, hipMemcpyAsync(out_frags, h->split_tab.p, nf * 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return BRISK_HIP_OK;
 }
 
 }  // extern "C"

@@ -128,6 +128,7 @@ SYMBOLS = [
     "brisk_hip_intake_ascii", "brisk_hip_intake_reads", "brisk_hip_insert_raw_reads",
     "brisk_hip_fragment_intervals", "brisk_hip_pair_intervals", "brisk_hip_compose_intervals", "brisk_hip_extract_pairs_packed",
     "brisk_hip_trim_pairs_packed", "brisk_hip_trim_pairs_reads", "brisk_hip_clean_pairs_ascii", "brisk_hip_clean_pairs_reads",
+    "brisk_hip_solid_runs", "brisk_hip_extract_fragments_packed", "brisk_hip_split_packed", "brisk_hip_split_reads",
     "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_joint_spectrum", "brisk_hip_filter_joint", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
     "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
@@ -185,6 +186,10 @@ def load() -> C.CDLL:
                                              [vp, C.POINTER(_PairCounts), C.POINTER(_IntakeStats)]
     L.brisk_hip_clean_pairs_reads.argtypes = [vp, vp, vp, _u64p, u64, C.POINTER(_IntakeRule), C.POINTER(_SelectRule), u32, u32, _ivp, C.POINTER(_PairCounts),
                                               C.POINTER(_IntakeStats)]
+    L.brisk_hip_solid_runs.argtypes = [vp, vp, vp, u64, u32, u32, vp, u64, C.POINTER(_SplitStats)]
+    L.brisk_hip_extract_fragments_packed.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
+    L.brisk_hip_split_packed.argtypes = [vp, vp, vp, u64, u32, u32, vp, u64, vp, vp, u64, C.POINTER(_SplitStats)]
+    L.brisk_hip_split_reads.argtypes = [vp, _u8p, _u64p, u64, u32, u32, _fragp, u64, C.POINTER(_SplitStats)]
     L.brisk_hip_enumerate.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64)]
     L.brisk_hip_stats.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.brisk_hip_checksum.argtypes = [vp, _u64p]
@@ -434,6 +439,52 @@ def _pack_raw(seqs, quals):
             raise ValueError("a quality string differs in length from its read")
         qflat, _ = _pack_reads(qs)
     return flat, qflat, offs
+
+
+# ---- read splitting (include/brisk_hip.h, "read splitting"): every solid run of a read as a fragment of its own ----
+SPLIT_STATS_FIELDS = ("n_reads", "n_reads_kept", "n_fragments", "n_slots", "n_solid", "n_short", "n_nts_in", "n_nts_out")
+
+
+class _SplitStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in SPLIT_STATS_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in SPLIT_STATS_FIELDS}
+
+
+def fragments_from_slots(counts, found, base, k: int, solid_min: int = 2, min_len: int = 0, n_nts_in: Optional[int] = None):
+    """The rule of brisk_hip_solid_runs / _split_* on the host: (FRAGMENT_DTYPE[n_fragments], stats dict) from the three outputs of
+    BriskHip.get_kmers.  The definition, written out; no device needed.  A slot is solid when it is found and its count is >=
+    solid_min (none is when solid_min > 255; every found one when it is 0); a run is a maximal stretch of consecutive solid slots of
+    one read; a run of s slots from slot i on is the fragment {read, start = i, len = s + k - 1} when that length is at least
+    max(min_len, k); fragments are ordered by read, then by start.  seqs[f.read][f.start:f.start + f.len] is fragment f's string.
+    n_nts_in: the reads' nucleotides, which the slots do not tell for a read shorter than k (None: such a read counts as empty)."""
+    counts = np.asarray(counts, np.uint8)
+    solid = np.asarray(found, bool) & (counts.astype(np.int64) >= int(solid_min))
+    base = np.asarray(base, np.uint64).astype(np.int64)
+    n_reads = len(base) - 1
+    min_nts = max(int(min_len), k)
+    slots = base[1:] - base[:-1]
+    st = dict.fromkeys(SPLIT_STATS_FIELDS, 0)
+    st["n_reads"] = n_reads
+    st["n_slots"] = int(base[-1]) if n_reads > 0 else 0
+    st["n_nts_in"] = int((slots[slots > 0] + k - 1).sum()) if n_nts_in is None else int(n_nts_in)
+    rows = []
+    for r in range(n_reads):
+        s = solid[base[r]:base[r + 1]]
+        if not s.any():
+            continue
+        edge = np.diff(np.concatenate(([0], s.astype(np.int8), [0])))  # runs: where the padded mask rises and falls
+        starts, ends = np.nonzero(edge == 1)[0], np.nonzero(edge == -1)[0]
+        lens = ends - starts
+        keep = lens + k - 1 >= min_nts
+        st["n_solid"] += int(lens.sum())
+        st["n_short"] += int(lens[~keep].sum())
+        st["n_nts_out"] += int((lens[keep] + k - 1).sum())
+        st["n_fragments"] += int(keep.sum())
+        st["n_reads_kept"] += bool(keep.any())
+        rows.extend((r, int(a), int(n) + k - 1) for a, n in zip(starts[keep], lens[keep]))
+    return np.array(rows, FRAGMENT_DTYPE) if rows else np.zeros(0, FRAGMENT_DTYPE), st
 
 
 # ---- paired-end reads (include/brisk_hip.h, "paired-end reads"): an interleaved stream, reads 2p and 2p + 1 the mates of pair p ----
@@ -756,6 +807,20 @@ class BriskHip:
         rule = select_rule("solid_run") if rule is None else rule
         self._chk(self.L.brisk_hip_trim_reads(self.h, flat, offs, len(offs) - 1, solid_min, C.byref(rule), out))
         return out[:len(offs) - 1]
+
+    def split_reads(self, seqs: Sequence, solid_min: int = 2, min_len: int = 0):
+        """Every read cut at its weak k-mers (brisk_hip_split_reads): (FRAGMENT_DTYPE[n_fragments], stats dict) -- what
+        fragments_from_slots(*get_kmers(seqs), k, solid_min, min_len) gives, computed on the device: one fragment per run of solid
+        k-mers that covers at least max(min_len, k) nucleotides.  seqs[f.read][f.start:f.start + f.len] is fragment f's string; two
+        fragments of one read may overlap by up to k - 2 nucleotides.  stats: SPLIT_STATS_FIELDS."""
+        flat, offs = _pack_reads(seqs)
+        cap = max(1, (int(kmer_slots(offs, self.k)[-1]) + len(offs)) // 2)  # a read of n slots has at most (n + 1) / 2 runs
+        out = np.zeros(cap, FRAGMENT_DTYPE)
+        if len(flat) == 0:
+            flat = np.zeros(1, np.uint8)
+        st = _SplitStats()
+        self._chk(self.L.brisk_hip_split_reads(self.h, flat, offs, len(offs) - 1, solid_min, min_len, out, cap, C.byref(st)))
+        return out[:st.n_fragments].copy(), st.as_dict()
 
     def intake(self, seqs: Sequence, quals: Optional[Sequence] = None, rule: Optional[_IntakeRule] = None):
         """The fragments of raw reads (brisk_hip_intake_reads): (FRAGMENT_DTYPE[n_fragments], stats dict) -- what
@@ -1117,6 +1182,39 @@ class BriskHip:
     def profile_slots(self, d_slots: int, d_starts: int, n_reads: int, d_out: int, solid_min: int = 2):
         """read_profile_packed over slots the caller holds (brisk_hip_profile_slots)"""
         self._chk(self.L.brisk_hip_profile_slots(self.h, d_slots, d_starts, n_reads, solid_min, d_out))
+
+    def _split_call(self, rc: int, st: _SplitStats, raise_on_capacity: bool) -> dict:
+        if rc == ECAPACITY and not raise_on_capacity:
+            return dict(st.as_dict(), rc=rc)
+        self._chk(rc)
+        return st.as_dict()
+
+    def solid_runs(self, d_slots: int, d_starts: int, n_reads: int, d_out_frags: int, frag_cap: int, solid_min: int = 2, min_len: int = 0,
+                   raise_on_capacity: bool = True) -> dict:
+        """The fragment table of slots the caller holds (brisk_hip_solid_runs), everything on the device; fragments_from_slots is the
+        definition.  Returns the stats; with raise_on_capacity=False an ECAPACITY answer returns them too, with "rc" set, so that
+        the call can be repeated with room.  Needs no index state."""
+        st = _SplitStats()
+        return self._split_call(self.L.brisk_hip_solid_runs(self.h, d_slots or None, d_starts or None, n_reads, solid_min, min_len, d_out_frags or None, frag_cap, C.byref(st)),
+                                st, raise_on_capacity)
+
+    def extract_fragments_packed(self, d_packed: int, d_starts: int, n_reads: int, d_frags: int, n_frags: int, d_out_packed: int, out_cap_words: int, d_out_starts: int) -> int:
+        """The rows of a fragment table out of a packed stream, back to back, as a new packed stream (brisk_hip_extract_fragments_packed),
+        everything on the device; rows may overlap and repeat a read.  d_out_starts holds n_frags + 1 uint64.  Returns the nucleotides
+        written.  Needs no index state."""
+        n_nts = C.c_uint64()
+        self._chk(self.L.brisk_hip_extract_fragments_packed(self.h, d_packed or None, d_starts or None, n_reads, d_frags or None, n_frags, d_out_packed or None, out_cap_words,
+                                                            d_out_starts or None, C.byref(n_nts)))
+        return n_nts.value
+
+    def split_packed(self, d_packed: int, d_starts: int, n_reads: int, d_out_packed: int, out_cap_words: int, d_out_starts: int, d_out_frags: int, frag_cap: int,
+                     solid_min: int = 2, min_len: int = 0, raise_on_capacity: bool = True) -> dict:
+        """The per-k-mer lookups, the runs and the gather in one call (brisk_hip_split_packed): the fragments of a packed stream as a
+        packed stream that insert_packed, get_packed and read_profile_packed take; d_out_packed (with out_cap_words 0) and d_out_frags
+        may be 0.  Returns the stats, as solid_runs does."""
+        st = _SplitStats()
+        return self._split_call(self.L.brisk_hip_split_packed(self.h, d_packed or None, d_starts or None, n_reads, solid_min, min_len, d_out_packed or None, out_cap_words,
+                                                              d_out_starts or None, d_out_frags or None, frag_cap, C.byref(st)), st, raise_on_capacity)
 
     def pack_ascii(self, d_bases: int, n_bases: int, d_packed: int):
         self._chk(self.L.brisk_hip_pack_ascii(self.h, d_bases, n_bases, d_packed))

@@ -63,6 +63,9 @@
  *                               no reference counterpart; khmer's extract-paired-reads and Trimmomatic's paired mode are the usual
  *                               tools: paired-end reads kept in sync through intake, trim and extraction -- the pair decision is
  *                               taken over the mates' intervals, and intact pairs and singles leave as two packed streams
+ *   brisk_hip_solid_runs / brisk_hip_extract_fragments_packed / brisk_hip_split_packed / brisk_hip_split_reads
+ *                               no reference counterpart; Quake, BFC and khmer's trim-low-abund -V are the usual tools: a read is
+ *                               cut at its weak k-mers and every run of solid k-mers leaves as a fragment of its own
  *   brisk_hip_lookup            Brisk::get (brisk/Brisk.hpp:64-69)
  *   brisk_hip_enumerate         Brisk::next / restart_kmer_enumeration
  *                               (brisk/Brisk.hpp:166-179, brisk/DenseMenuYo.hpp:476-521)
@@ -495,6 +498,69 @@ int brisk_hip_clean_pairs_reads(brisk_hip_index *h, const char *bases, const cha
                                 uint64_t n_reads, const brisk_hip_intake_rule *intake, const brisk_hip_select_rule *select /* NULL ok */,
                                 uint32_t solid_min, uint32_t pair_mode, brisk_hip_read_interval *out /* HOST, n_reads */,
                                 brisk_hip_pair_counts *counts /* HOST */, brisk_hip_intake_stats *stats /* HOST */);
+
+/* ---- read splitting: every solid run of a read as its own fragment (no reference counterpart; kernels: brisk_split.hip) ---- */
+/* SLOT, PRESENT and SOLID mean what they mean in brisk_hip_read_profile: read r owns max(0, len_r - k + 1) slots, a slot is solid
+ * when it is present and its stored count is >= solid_min (solid_min > 255: none is; solid_min == 0: every present slot is, one
+ * whose count wrapped to 0 included).  A RUN is a maximal stretch of consecutive solid slots of one read: the last slot of read r and
+ * the first slot of read r + 1 are neighbours in the slot array and never in one run.  A run of s slots that starts at slot i covers
+ * nucleotides [i, i + s + k - 1) of its read, and is a FRAGMENT {read, start = i, len = s + k - 1} when s + k - 1 >= L = max(min_len,
+ * k).  Fragments are ordered by read, then by start.  Two fragments of one read may OVERLAP by up to k - 2 nucleotides (the weak
+ * k-mers between them share nucleotides with both): no solid k-mer is in two fragments and no weak k-mer is in any, but the output
+ * can hold MORE nucleotides than the input -- an output as large as the input does not always suffice.  What always does:
+ * frag_cap = (n_slots + n_reads) / 2 and out_cap_words = ceil((n_slots + frag_cap * (k - 1)) / 16) + 2; or ask first (a refused call
+ * fills *stats).  For every read the first longest fragment at min_len = k is the interval of BRISK_HIP_SELECT_SOLID_RUN, and a
+ * read has no fragment exactly when that interval has len 0.  brisk_amd.fragments_from_slots is the same rule in numpy: the
+ * definition the tests compare with. */
+typedef struct brisk_hip_split_stats {
+    uint64_t n_reads;
+    uint64_t n_reads_kept;  /* reads with at least one fragment */
+    uint64_t n_fragments;
+    uint64_t n_slots;
+    uint64_t n_solid;       /* solid slots */
+    uint64_t n_short;       /* solid slots in runs that cover fewer than L nucleotides */
+    uint64_t n_nts_in;      /* starts[n_reads] - starts[0] */
+    uint64_t n_nts_out;     /* the sum of len */
+} brisk_hip_split_stats;    /* n_solid == (n_nts_out - n_fragments * (k - 1)) + n_short, always */
+/* The fragment table of slots the caller holds (d_slots, DEVICE, read by d_starts exactly as brisk_hip_profile_slots reads them) ->
+ * d_out_frags (DEVICE, frag_cap rows of room).  BRISK_HIP_ECAPACITY when frag_cap < n_fragments: nothing is written, *stats (HOST) is
+ * filled, and the call can be repeated with room.  EINVAL: a read table that does not ascend, a read of 2^32 nucleotides or more,
+ * null pointers.  Every row is stored once, by a plain vector store.  Needs no index state: works on any handle (sharded and
+ * entry-id ones included; the slots of the brisk_hip_scan_kmers round trip can feed it).  Scratch memory of the handle: 8 bytes a
+ * read, 4 bytes per 16 slots, 32 bytes a fragment. */
+int brisk_hip_solid_runs(brisk_hip_index *h, const uint16_t *d_slots, const uint64_t *d_starts, uint64_t n_reads,
+                         uint32_t solid_min, uint32_t min_len, brisk_hip_fragment *d_out_frags, uint64_t frag_cap,
+                         brisk_hip_split_stats *stats /* HOST */);
+/* The rows of a fragment table (d_frags[n_frags], DEVICE; any table, not only one written here) out of a packed stream, back to back
+ * in table order, as a new packed stream in the layout of brisk_hip_extract_packed: d_out_starts[0 .. n_frags] ascending from 0, the
+ * unused low bits of the last word zero and the two words after it zero.  Rows may overlap and may repeat a read.  EINVAL, nothing
+ * written: a row with read >= n_reads, len == 0 or start + len beyond its read (found on the device; the message names the first
+ * such row), a read table that does not ascend, null pointers.  BRISK_HIP_ECAPACITY, nothing written, *n_out_nts (HOST) filled: when
+ * out_cap_words < ceil(n_nts / 16) + 2.  The output may not overlap the inputs.  Every output word is stored once by a plain vector
+ * store.  Needs no index state: works on any handle. */
+int brisk_hip_extract_fragments_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                                       const brisk_hip_fragment *d_frags, uint64_t n_frags,
+                                       uint32_t *d_out_packed, uint64_t out_cap_words, uint64_t *d_out_starts /* n_frags + 1 room */,
+                                       uint64_t *n_out_nts /* HOST */);
+/* brisk_hip_get_kmers_packed, brisk_hip_solid_runs and brisk_hip_extract_fragments_packed in one call: the fragments of a packed
+ * stream as a packed stream that brisk_hip_insert_packed / _get_packed / _read_profile_packed take, without leaving the device.  The
+ * slots exist for one internal batch at a time; the fragment table accumulates in scratch memory of the handle (16 bytes a
+ * fragment, reads numbered as in the call) and the capacities are checked after the last batch: only then is anything copied or
+ * gathered.  BRISK_HIP_ECAPACITY when frag_cap < n_fragments or out_cap_words < ceil(n_nts_out / 16) + 2: nothing is written to the
+ * device outputs, *stats is filled, and the call can be repeated with room.  d_out_frags (frag_cap rows) may be NULL; d_out_starts
+ * holds frag_cap + 1; d_out_packed == NULL with out_cap_words == 0: the table, the starts and the stats only.  Inherits
+ * brisk_hip_trim_packed: pending deferred inserts are completed first; EINVAL on a sharded index, on an entry-id index, on offsets
+ * that do not ascend (and on a read of 2^32 nucleotides or more); the answer does not depend on max_batch_reads,
+ * BRISK_PROFILE_BATCH, BRISK_PROFILE_SEG or on which kernels run.  split_reads takes HOST reads (layout of brisk_hip_get_reads) and
+ * returns only the table, out_frags[frag_cap] HOST, written when it fits: the caller slices its own strings. */
+int brisk_hip_split_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                           uint32_t solid_min, uint32_t min_len,
+                           uint32_t *d_out_packed, uint64_t out_cap_words, uint64_t *d_out_starts /* frag_cap + 1 room */,
+                           brisk_hip_fragment *d_out_frags /* frag_cap room, may be NULL */, uint64_t frag_cap,
+                           brisk_hip_split_stats *stats /* HOST */);
+int brisk_hip_split_reads(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
+                          uint32_t solid_min, uint32_t min_len, brisk_hip_fragment *out_frags /* HOST */, uint64_t frag_cap,
+                          brisk_hip_split_stats *stats /* HOST */);
 
 /* point lookups of UNHASHED (kmer_s, minimizer_idx) pairs, as Brisk::get takes them.
  * HOST arrays; out_found[i] in {0,1}; out_data[i] valid when found. */
