@@ -12,3 +12,4 @@ from .hipapi import JOINT_ABSENT, joint_figures, joint_spectrum_from_entries  # 
 from .hipapi import FRAGMENT_DTYPE, INTAKE_BLOCK, INTAKE_STATS_FIELDS, fragments_from_reads, intake_rule  # noqa: F401
 from .hipapi import PAIR_COUNTS_FIELDS, PAIR_MODES, compose_intervals, intervals_from_fragments, pair_intervals, split_pairs  # noqa: F401
 from .hipapi import SPLIT_STATS_FIELDS, fragments_from_slots  # noqa: F401
+from .hipapi import CORRECT_STATS_FIELDS, CORRECTION_DTYPE, SITE_DTYPE, corrections_from_candidates, site_windows, sites_from_slots  # noqa: F401

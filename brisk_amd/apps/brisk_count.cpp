@@ -43,6 +43,11 @@
 //                    the same reads through brisk_hip_split_reads: a read is cut at its weak k-mers, and every run of k-mers with count >= N
 //                    that covers at least L nucleotides (default k) is a record of its own, ">read_index start len", ordered by read, then
 //                    by start; the counters of brisk_hip_split_stats go to stderr.  Not with --paired (exit status 2)
+//   --extract FILE --rule correct [--solid N] [--min-cover C]
+//                    the same reads through brisk_hip_correct_reads: every read leaves whole, as one record ">read_index n_corrected", with
+//                    its isolated substitutions repaired (a run of weak k-mers that one substitution explains, exactly one other base
+//                    making every k-mer of the run solid); C: the fewest weak k-mers a run at a read's edge may have (default k); the
+//                    counters of brisk_hip_correct_stats go to stderr.  Not with --paired (exit status 2)
 //   --paired [--mate FILE] [--pair-mode each|all|any]
 //                    the input holds paired reads, one record a read: interleaved (records 2p and 2p + 1 are the mates of pair p), or,
 //                    with --mate FILE, record i of the input and record i of FILE (of the same kind, FASTA or FASTQ) are a pair.  A
@@ -406,6 +411,7 @@ int main(int argc_in, char** argv_in) {
     const char* extract_file = nullptr;
     const char* rule_text = nullptr;
     long min_len = 0;
+    long min_cover = -1;  // --min-cover C of --rule correct (-1: not given; 0: k)
     long min_qual = 0, qual_base = 33;
     bool have_qual = false;
     long min_count = 0, max_count = 255, solid = 2;
@@ -427,6 +433,7 @@ int main(int argc_in, char** argv_in) {
         "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]] [--paired [--mate FILE] [--pair-mode each|all|any]]; FASTA \"-\": no reads; a FILE may be a snapshot; an input that starts with '@' is FASTQ)\n"
         "  --min-qual Q   FASTQ input: a base of quality below Q (0..93) is cut like an N, on the device; --qual-base 33|64 (default 33)\n"
         "  --paired   one record a read, interleaved or zipped with --mate FILE; --extract PREFIX then writes PREFIX.1.fa PREFIX.2.fa PREFIX.s.fa (FASTQ input allowed)\n"
+        "  --rule correct [--min-cover C]   with --extract FILE: every read whole, \">read_index n_corrected\", its isolated substitutions repaired; the counters go to stderr\n"
         "  --rule split   with --extract FILE: every run of k-mers with count >= N (--solid) as a record of its own, \">read_index start len\"; the counters go to stderr\n"
         "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+";
     for (int i = 0; i < argc_in; i++) {
@@ -447,7 +454,7 @@ int main(int argc_in, char** argv_in) {
             if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
         const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count") ||
                                     !strcmp(argv_in[i], "--profile") || !strcmp(argv_in[i], "--solid") || !strcmp(argv_in[i], "--extract") || !strcmp(argv_in[i], "--rule") ||
-                                    !strcmp(argv_in[i], "--min-len") || !strcmp(argv_in[i], "--joint") || !strcmp(argv_in[i], "--joint-histo") || !strcmp(argv_in[i], "--filter-joint") ||
+                                    !strcmp(argv_in[i], "--min-len") || !strcmp(argv_in[i], "--min-cover") || !strcmp(argv_in[i], "--joint") || !strcmp(argv_in[i], "--joint-histo") || !strcmp(argv_in[i], "--filter-joint") ||
                                     !strcmp(argv_in[i], "--window") || !strcmp(argv_in[i], "--min-qual") || !strcmp(argv_in[i], "--qual-base") || !strcmp(argv_in[i], "--mate") ||
                                     !strcmp(argv_in[i], "--pair-mode"));
         if (!named) {
@@ -487,6 +494,14 @@ int main(int argc_in, char** argv_in) {
             min_len = strtol(argv_in[i], &end, 10);
             if (end == argv_in[i] || *end || min_len < 0 || min_len > 0xffffffffl) {
                 std::cerr << "--min-len: a number of nucleotides, got " << argv_in[i] << std::endl;
+                return 2;
+            }
+        }
+        else if (!strcmp(opt, "--min-cover")) {
+            char* end = nullptr;
+            min_cover = strtol(argv_in[i], &end, 10);
+            if (end == argv_in[i] || *end || min_cover < 0 || min_cover > 0xffffffffl) {
+                std::cerr << "--min-cover: a number of k-mers, got " << argv_in[i] << std::endl;
                 return 2;
             }
         }
@@ -536,6 +551,10 @@ int main(int argc_in, char** argv_in) {
         std::cerr << "--mate FILE and --pair-mode belong to --paired" << std::endl;
         return 2;
     }
+    if (min_cover >= 0 && !(extract_file && rule_text && !strcmp(rule_text, "correct"))) {
+        std::cerr << "--min-cover belongs to --extract FILE --rule correct" << std::endl;
+        return 2;
+    }
     uint32_t pair_mode = BRISK_HIP_PAIR_EACH;
     if (pair_mode_text) {
         if (!strcmp(pair_mode_text, "each")) pair_mode = BRISK_HIP_PAIR_EACH;
@@ -577,7 +596,8 @@ int main(int argc_in, char** argv_in) {
     rule.min_len = (uint32_t)min_len;
     rule.hi = 0xffffffffu;
     const bool rule_split = rule_text && !strcmp(rule_text, "split");  // every solid run of a read, not one interval: brisk_hip_split_reads
-    if (rule_text && strcmp(rule_text, "trim") && !rule_split) {  // median:LO:HI or present:LO:HI
+    const bool rule_correct = rule_text && !strcmp(rule_text, "correct");  // every read whole, its isolated substitutions repaired: brisk_hip_correct_reads
+    if (rule_text && strcmp(rule_text, "trim") && !rule_split && !rule_correct) {  // median:LO:HI or present:LO:HI
         unsigned long lo = 0, hi = 0;
         char tail = 0;
         if (sscanf(rule_text, "median:%lu:%lu%c", &lo, &hi, &tail) == 2) rule.kind = BRISK_HIP_SELECT_MEDIAN;
@@ -628,6 +648,10 @@ int main(int argc_in, char** argv_in) {
     }
     if (rule_split && paired) {
         std::cerr << "--rule split cuts reads into several fragments: not with --paired" << std::endl;
+        return 2;
+    }
+    if (rule_correct && paired) {
+        std::cerr << "--rule correct writes every read as one record of one file: not with --paired (correct the interleaved file, the records stay in step)" << std::endl;
         return 2;
     }
     if (paired) {  // whole pairs, before anything is counted
@@ -952,6 +976,49 @@ int main(int argc_in, char** argv_in) {
                 std::cerr << "extract " << extract_file << ": " << sum.n_fragments << " fragments of " << sum.n_reads_kept << " of " << sum.n_reads << " reads, " << sum.n_nts_out << " of "
                           << sum.n_nts_in << " nucleotides, " << sum.n_solid << " of " << sum.n_slots << " k-mers solid, " << sum.n_short << " in short runs (--rule split, solid >= "
                           << solid << ")" << std::endl;
+            } else if (extract_file && rule_correct) {  // the reads of the input again, against the final index: every read, repaired, one record each
+                std::ofstream out(extract_file);
+                brisk_hip_correct_stats sum{};
+                uint64_t read_index = 0, reads_changed = 0;
+                const uint32_t cover = min_cover < 0 ? 0u : (uint32_t)min_cover;
+                if (!no_reads) {
+                    FastaBatcher batches(argv[2], batch_bases);
+                    FastaBatch bt;
+                    std::vector<brisk_hip_correction> corr;
+                    std::string seq;
+                    while (batches.next(bt)) {
+                        brisk_hip_correct_stats st{};
+                        int crc = brisk_hip_correct_reads(h, bt.flat.data(), bt.offs.data(), bt.size(), (uint32_t)solid, cover, corr.data(), corr.size(), &st);
+                        if (crc == BRISK_HIP_ECAPACITY) {  // (the refused call has counted them)
+                            corr.resize(st.n_corrected);
+                            crc = brisk_hip_correct_reads(h, bt.flat.data(), bt.offs.data(), bt.size(), (uint32_t)solid, cover, corr.data(), corr.size(), &st);
+                        }
+                        if (crc != BRISK_HIP_OK) {
+                            std::cerr << "--extract: " << brisk_hip_last_error(h) << std::endl;
+                            return 1;
+                        }
+                        uint64_t j = 0;  // the table is ordered by read, then by position
+                        for (uint64_t r = 0; r < bt.size(); r++) {
+                            seq.assign(bt.flat.data() + bt.offs[r], bt.offs[r + 1] - bt.offs[r]);
+                            uint64_t n = 0;
+                            for (; j < st.n_corrected && corr[j].read == r; j++, n++) seq[corr[j].pos] = "ACTG"[corr[j].to & 3];
+                            reads_changed += n > 0;
+                            out << ">" << read_index + r << " " << n << "\n" << seq << "\n";
+                        }
+                        read_index += bt.size();
+                        const uint64_t* add = (const uint64_t*)&st;
+                        for (size_t i = 0; i < sizeof(st) / 8; i++) ((uint64_t*)&sum)[i] += add[i];
+                    }
+                }
+                out.close();
+                if (!out) {
+                    std::cerr << "--extract " << extract_file << ": write failed" << std::endl;
+                    return 1;
+                }
+                std::cerr << "extract " << extract_file << ": " << sum.n_corrected << " corrections in " << reads_changed << " of " << sum.n_reads << " reads, " << sum.n_sites << " sites ("
+                          << sum.n_ambiguous << " ambiguous, " << sum.n_unresolved << " unresolved) of " << sum.n_runs << " weak runs (" << sum.n_skip_whole << " whole, " << sum.n_skip_long
+                          << " long, " << sum.n_skip_short << " short), " << sum.n_weak << " of " << sum.n_slots << " k-mers weak (--rule correct, solid >= " << solid << ", min-cover "
+                          << cover << ")" << std::endl;
             } else if (extract_file) {  // the reads of the input again, against the final index: what the rule keeps of them, as FASTA
                 std::ofstream out(extract_file);
                 uint64_t read_index = 0, kept = 0, kept_nts = 0;

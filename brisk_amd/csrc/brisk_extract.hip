@@ -143,9 +143,15 @@ __device__ __forceinline__ u32 packed_window(const u32* __restrict__ packed, u64
 }
 
 // out_starts[0 .. n_out]: ascending from 0, strictly (a kept read has a nucleotide); n_words = ceil(out_starts[n_out] / 16) > 0; the
-// grid covers n_words + 2 words: the two after the last one are zero
+// grid covers n_words + 2 words: the two after the last one are zero.  patch(v, w, j, out_starts, n_out) has the last say on word w
+// before its one store (j: the row that holds the word's first nucleotide): ExtractNoPatch for a plain gather, brisk_correct.hip's
+// CorrectCandPatch for candidate windows.
+struct ExtractNoPatch {
+    __device__ __forceinline__ u32 operator()(u32 v, u64, u64, const u64*, u64) const { return v; }
+};
+template <class Patch>
 __global__ void __launch_bounds__(256) k_extract_gather(const u32* __restrict__ packed, const u64* __restrict__ out_starts, const u64* __restrict__ src_pos, u64 n_out,
-                                                        u64 n_words, u32* __restrict__ out) {
+                                                        u64 n_words, u32* __restrict__ out, Patch patch) {
     __shared__ u64 s_j0;
     const u64 w0 = (u64)blockIdx.x * 256;
     if (threadIdx.x == 0 && w0 < n_words) {  // the kept read that holds the block's first nucleotide: the last j with out_starts[j] <= p
@@ -175,6 +181,7 @@ __global__ void __launch_bounds__(256) k_extract_gather(const u32* __restrict__ 
     }
     u32 v = 0, filled = 0;
     u64 begin = out_starts[j];
+    const u64 j_first = j;
     while (filled < 16 && j < n_out) {
         const u64 end = out_starts[j + 1], q = p + filled;
         const u32 take = (u32)ext_min(16 - filled, end - q);
@@ -185,7 +192,7 @@ __global__ void __launch_bounds__(256) k_extract_gather(const u32* __restrict__ 
             begin = end;
         }
     }
-    out[w] = v;
+    out[w] = patch(v, w, j_first, out_starts, n_out);
 }
 
 // bases[i] = "ACTG"[code of nucleotide first_nt + i], 16 per lane

@@ -202,7 +202,8 @@ int extract_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u
                        (u64*)h->ext_src.p);
     if ((rc = launch_check(h, "k_extract_apply"))) return rc;
     if (n_words + 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "extract_packed: more output words than one launch covers");
-    hipLaunchKernelGGL(k_extract_gather, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_packed, (const u64*)out.starts, (const u64*)h->ext_src.p, n_out, n_words, out.packed);
+    hipLaunchKernelGGL(k_extract_gather<ExtractNoPatch>, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_packed, (const u64*)out.starts, (const u64*)h->ext_src.p, n_out, n_words, out.packed,
+                       ExtractNoPatch{});
     if ((rc = launch_check(h, "k_extract_gather"))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BRISK_HIP_OK;
@@ -643,8 +644,9 @@ int split_check_table(brisk_hip_index* h, const u64* d_starts, u64 n_reads, cons
 // holds their slot bases (slot_bases / kmers_packed_impl).  The intake's passes over a mask of solid slots: the counts first (a host
 // synchronisation), then the runs {read, first slot, slots} into h->ink_tab, in input order, and *n_kept reads that have one.
 // *run_slots: the slots of the runs of at least min_slots; *n_short: the solid slots of the shorter ones.
+// weak (brisk_hip_weak_sites): the runs of slots that are NOT solid, over the same passes.
 int split_runs_impl(brisk_hip_index* h, const uint16_t* d_slots, const u64* d_starts, u64 n_reads, u64 n_slots, u32 solid_min, u32 min_slots, u64* n_frag, u64* n_kept,
-                    u64* run_slots, u64* n_short) {
+                    u64* run_slots, u64* n_short, bool weak = false) {
     int rc;
     *n_frag = *n_kept = *run_slots = *n_short = 0;
     const u64 nb64 = (n_slots + INTAKE_BLOCK - 1) / INTAKE_BLOCK;
@@ -667,7 +669,8 @@ int split_runs_impl(brisk_hip_index* h, const uint16_t* d_slots, const u64* d_st
     hipLaunchKernelGGL(k_split_offsets, dim3(nblocks(n_reads + 1, 256)), dim3(256), 0, h->stream, d_starts, (const u64*)h->slot_buf.p, n_reads, n_slots, d_soff);
     hipLaunchKernelGGL(k_intake_bounds, dim3(nblocks(n_reads + 1, 256)), dim3(256), 0, h->stream, (const u64*)d_soff, n_reads, (u64)0, n_lanes, d_mask);
     hipLaunchKernelGGL(k_intake_first, dim3(nblocks((u64)nb + 1, 256)), dim3(256), 0, h->stream, (const u64*)d_soff, n_reads, (u64)0, (u64)nb, d_first);
-    hipLaunchKernelGGL(k_split_mask, dim3(nb), dim3(256), 0, h->stream, d_slots, n_slots, solid_min, d_mask, d_carry);
+    if (weak) hipLaunchKernelGGL(k_split_mask<true>, dim3(nb), dim3(256), 0, h->stream, d_slots, n_slots, solid_min, d_mask, d_carry);
+    else hipLaunchKernelGGL(k_split_mask<false>, dim3(nb), dim3(256), 0, h->stream, d_slots, n_slots, solid_min, d_mask, d_carry);
     hipLaunchKernelGGL(k_intake_reduce<true>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, (const u64*)d_carry, nb, d_part[3]);
     hipLaunchKernelGGL(k_intake_top, dim3(1), dim3(1024), 0, h->stream, d_part[3], nb2);
     hipLaunchKernelGGL(k_intake_spread<true>, dim3(nb2), dim3(INTAKE_SCAN), 0, h->stream, d_carry, nb, (const u64*)d_part[3]);
@@ -742,8 +745,10 @@ int split_batch(brisk_hip_index* h, const uint16_t* d_slots, const u64* d_starts
 // first (one pass, a host synchronisation), then -- only when the rows are valid and the output has room -- the starts, the source
 // positions and brisk_hip_extract_packed's gather: a refused call writes nothing.  out.packed == NULL: the starts only.
 // check_table: the read table is not known to ascend.
+// cand_sites (brisk_hip_candidate_windows): the rows are the candidate windows of these sites, three a site, and the gather puts each
+// candidate's substitution into its window.
 int fragment_gather_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, const IntakeFragment* d_frags, u64 n_frags, const OutStream& out, bool check_table,
-                         const char* who, u64* n_out_nts) {
+                         const char* who, u64* n_out_nts, const CorrectSite* cand_sites = nullptr) {
     int rc;
     *n_out_nts = 0;
     u64 n_nts = 0;
@@ -786,11 +791,216 @@ int fragment_gather_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_s
     if ((rc = launch_check(h, "k_split_frag_apply"))) return rc;
     if (out.packed) {
         if (n_words + 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": more output words than one launch covers");
-        hipLaunchKernelGGL(k_extract_gather, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_packed, (const u64*)out.starts, (const u64*)h->ext_src.p, n_frags, n_words, out.packed);
+        const dim3 grid(nblocks(n_words + 2, 256));
+        if (cand_sites)
+            hipLaunchKernelGGL(k_extract_gather<CorrectCandPatch>, grid, dim3(256), 0, h->stream, d_packed, (const u64*)out.starts, (const u64*)h->ext_src.p, n_frags, n_words, out.packed,
+                               CorrectCandPatch{cand_sites, (u32)h->P.k});
+        else
+            hipLaunchKernelGGL(k_extract_gather<ExtractNoPatch>, grid, dim3(256), 0, h->stream, d_packed, (const u64*)out.starts, (const u64*)h->ext_src.p, n_frags, n_words, out.packed,
+                               ExtractNoPatch{});
         if ((rc = launch_check(h, "k_extract_gather"))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BRISK_HIP_OK;
+}
+
+// ---- spectral read correction: isolated substitutions repaired (no reference counterpart; kernels: brisk_correct.hip over the
+// split's run passes; the candidate windows are gathered by brisk_extract.hip's gather) ----
+static_assert(sizeof(brisk_hip_correct_stats) == 88 && offsetof(brisk_hip_correct_stats, n_unresolved) == 80, "include/brisk_hip.h: eleven 64-bit counters");
+static_assert(sizeof(brisk_hip_site) == sizeof(CorrectSite) && offsetof(brisk_hip_site, pos) == offsetof(CorrectSite, pos) && offsetof(brisk_hip_site, cover) == offsetof(CorrectSite, cover) &&
+                  sizeof(brisk_hip_correction) == sizeof(CorrectRow) && offsetof(brisk_hip_correction, pos) == offsetof(CorrectRow, pos) &&
+                  offsetof(brisk_hip_correction, from) == offsetof(CorrectRow, from) && offsetof(brisk_hip_correction, to) == offsetof(CorrectRow, to) &&
+                  offsetof(brisk_hip_correction, cover) == offsetof(CorrectRow, cover),
+              "the kernels write the C-ABI's rows");
+
+// a candidate round holds at most this many sites: their windows and the windows' slots are the round's device memory
+u64 correct_batch_sites() {
+    static const u64 n = getenv("BRISK_CORRECT_BATCH") && atoll(getenv("BRISK_CORRECT_BATCH")) > 0 ? (u64)atoll(getenv("BRISK_CORRECT_BATCH")) : (1ull << 22);
+    return n;
+}
+int check_min_cover(brisk_hip_index* h, u32 min_cover, const char* who, u32* c) {
+    if (min_cover > h->P.k) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": min_cover " + std::to_string(min_cover) + " is above k = " + std::to_string(h->P.k));
+    *c = min_cover ? min_cover : (u32)h->P.k;
+    return BRISK_HIP_OK;
+}
+
+// h->corr_tmp: [128 bytes: [0..2] the skipped runs whole / long / short, [4..6] the sites corrected / ambiguous / unresolved, [8] the
+// first bad row of a caller's table][block sums behind them, as the pass at hand lays them out]
+constexpr size_t kCorrHead = 128;
+
+// The handle's lock is held.  One batch, as split_runs_impl takes it: its weak runs into h->ink_tab, classified and counted into *st
+// (a host synchronisation); *n_sites of them are sites, and the block sums that correct_sites_rows needs stay in h->corr_tmp.
+int correct_sites_count(brisk_hip_index* h, const uint16_t* d_slots, const u64* d_starts, u64 n_reads, u64 n_slots, u32 solid_min, u32 min_cover, brisk_hip_correct_stats* st,
+                        u64* n_runs, u64* n_sites) {
+    int rc;
+    u64 kept = 0, run_slots = 0, n_short = 0;
+    *n_runs = *n_sites = 0;
+    if ((rc = split_runs_impl(h, d_slots, d_starts, n_reads, n_slots, solid_min, 1, n_runs, &kept, &run_slots, &n_short, true))) return rc;
+    st->n_weak += run_slots;
+    st->n_runs += *n_runs;
+    if (!*n_runs) return BRISK_HIP_OK;
+    const u32 nb = nblocks(*n_runs, 256);
+    if ((rc = ensure(h, h->corr_tmp, kCorrHead + ((size_t)nb + 1) * 8))) return rc;
+    unsigned long long* d_ctr = (unsigned long long*)h->corr_tmp.p;
+    u64* d_bs = (u64*)((char*)h->corr_tmp.p + kCorrHead);
+    HIPCHK(h, hipMemsetAsync(d_ctr, 0, kCorrHead, h->stream));
+    hipLaunchKernelGGL(k_correct_class, dim3(nb), dim3(256), 0, h->stream, (const IntakeFragment*)h->ink_tab.p, *n_runs, d_starts, (u32)h->P.k, min_cover, d_bs, d_ctr);
+    hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_bs, nb);
+    if ((rc = launch_check(h, "k_correct_class / k_slot_top"))) return rc;
+    u64 got[4] = {0, 0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(got, d_ctr, 24, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(got + 3, d_bs + nb, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    st->n_skip_whole += got[0];
+    st->n_skip_long += got[1];
+    st->n_skip_short += got[2];
+    st->n_sites += got[3];
+    *n_sites = got[3];
+    if (got[0] + got[1] + got[2] + got[3] != *n_runs) return fail(h, BRISK_HIP_EHIP, "weak_sites: the classes and the runs disagree");
+    return BRISK_HIP_OK;
+}
+// the sites of the runs that correct_sites_count has just classified, queued on the stream
+int correct_sites_rows(brisk_hip_index* h, const u64* d_starts, u64 n_runs, u32 min_cover, CorrectSite* d_out) {
+    hipLaunchKernelGGL(k_correct_sites, dim3(nblocks(n_runs, 256)), dim3(256), 0, h->stream, (const IntakeFragment*)h->ink_tab.p, n_runs, d_starts, (u32)h->P.k, min_cover,
+                       (const u64*)((char*)h->corr_tmp.p + kCorrHead), d_out);
+    return launch_check(h, "k_correct_sites");
+}
+
+// a caller's site table against its reads (the read table ascends): EINVAL naming the first bad row
+int correct_check_sites(brisk_hip_index* h, const CorrectSite* d_sites, u64 n_sites, const u64* d_starts, u64 n_reads, const char* who) {
+    int rc;
+    if (!n_sites) return BRISK_HIP_OK;
+    if (n_sites > 0x7fffffffull * 256 / 3) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": more rows than one launch covers");
+    if ((rc = ensure(h, h->corr_tmp, kCorrHead))) return rc;
+    unsigned long long* d_flag = (unsigned long long*)h->corr_tmp.p + 8;
+    HIPCHK(h, hipMemsetAsync(d_flag, 0xff, 8, h->stream));
+    hipLaunchKernelGGL(k_correct_site_check, dim3(nblocks(n_sites, 256)), dim3(256), 0, h->stream, d_sites, n_sites, d_starts, n_reads, (u32)h->P.k, d_flag);
+    if ((rc = launch_check(h, "k_correct_site_check"))) return rc;
+    u64 bad = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad, d_flag, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (bad != ~0ull)
+        return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": row " + std::to_string(bad) + " of the site table names a read >= n_reads, has a cover of 0 or above k, or its pos or window lies beyond its read");
+    return BRISK_HIP_OK;
+}
+
+// The handle's lock is held; the sites are valid.  Their 3 * n_sites candidate windows, substituted, as a packed stream (fragment_gather_impl
+// over three rows a site in h->corr_rows, with the candidates' patch).
+int correct_windows_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, const CorrectSite* d_sites, u64 n_sites, const OutStream& out, const char* who,
+                         u64* n_out_nts) {
+    int rc;
+    if (n_sites) {
+        if ((rc = ensure(h, h->corr_rows, 3 * n_sites * 16))) return rc;
+        hipLaunchKernelGGL(k_correct_cand_rows, dim3(nblocks(3 * n_sites, 256)), dim3(256), 0, h->stream, d_sites, n_sites, (u32)h->P.k, (IntakeFragment*)h->corr_rows.p);
+        if ((rc = launch_check(h, "k_correct_cand_rows"))) return rc;
+    }
+    return fragment_gather_impl(h, d_packed, d_starts, n_reads, (const IntakeFragment*)h->corr_rows.p, 3 * n_sites, out, false, who, n_out_nts, d_sites);
+}
+
+// The handle's lock is held; the sites (n_sites > 0) are valid.  The decisions over the candidates' slots, counted (a host
+// synchronisation): cnt[0..2] = corrected / ambiguous / unresolved.  The decisions and the block sums that correct_rows needs stay
+// in h->corr_tmp.
+int correct_decide_impl(brisk_hip_index* h, const uint16_t* d_cand_slots, const CorrectSite* d_sites, u64 n_sites, const u32* d_packed, const u64* d_starts, u32 solid_min, u64 cnt[3]) {
+    int rc;
+    const u32 nb = nblocks(n_sites, 256);
+    // [head][block sums of the covers, nb + 1][of the corrected sites, nb + 1][a decision a site]
+    if ((rc = ensure(h, h->corr_tmp, kCorrHead + 2 * ((size_t)nb + 1) * 8 + n_sites * 4))) return rc;
+    unsigned long long* d_ctr = (unsigned long long*)h->corr_tmp.p;
+    u64* d_cover = (u64*)((char*)h->corr_tmp.p + kCorrHead);
+    u64* d_corr = d_cover + nb + 1;
+    u32* d_dec = (u32*)(d_corr + nb + 1);
+    HIPCHK(h, hipMemsetAsync(d_ctr, 0, kCorrHead, h->stream));
+    hipLaunchKernelGGL(k_correct_cover, dim3(nb), dim3(256), 0, h->stream, d_sites, n_sites, d_cover);
+    hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_cover, nb);
+    hipLaunchKernelGGL(k_correct_decide, dim3(nb), dim3(256), 0, h->stream, d_cand_slots, d_sites, n_sites, (const u64*)d_cover, d_packed, d_starts, solid_min, d_dec, d_corr, d_ctr + 4);
+    hipLaunchKernelGGL(k_slot_top, dim3(1), dim3(1024), 0, h->stream, d_corr, nb);
+    if ((rc = launch_check(h, "k_correct_cover / k_slot_top / k_correct_decide"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(cnt, d_ctr + 4, 24, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (cnt[0] + cnt[1] + cnt[2] != n_sites) return fail(h, BRISK_HIP_EHIP, "decide_sites: the decisions and the sites disagree");
+    return BRISK_HIP_OK;
+}
+// the rows of the sites that correct_decide_impl has just found corrected, queued on the stream; r0 is added to their reads
+int correct_rows(brisk_hip_index* h, const CorrectSite* d_sites, u64 n_sites, u64 r0, CorrectRow* d_out) {
+    const u32 nb = nblocks(n_sites, 256);
+    const u64* d_corr = (const u64*)((char*)h->corr_tmp.p + kCorrHead) + nb + 1;
+    hipLaunchKernelGGL(k_correct_rows, dim3(nb), dim3(256), 0, h->stream, d_sites, (const u32*)(d_corr + nb + 1), n_sites, d_corr, r0, d_out);
+    return launch_check(h, "k_correct_rows");
+}
+
+// The handle's lock is held.  brisk_hip_get_kmers_packed's loop over a stream in scratch memory: d_out[n_slots], zeroed here.
+int correct_lookups(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_reads, uint16_t* d_out, u64 n_slots) {
+    int rc;
+    HIPCHK(h, hipMemsetAsync(d_out, 0, n_slots * 2, h->stream));
+    u64 done = 0;
+    for (u64 q0 = 0; q0 < n_reads; q0 += h->max_batch_reads) {
+        const u64 nq = std::min<u64>(h->max_batch_reads, n_reads - q0);
+        u64 ns = 0;
+        if ((rc = count_kmers(h, d_starts + q0, nq, &ns))) return rc;
+        if (!ns) continue;
+        if (done + ns > n_slots) return fail(h, BRISK_HIP_EHIP, "correct: the candidate stream and its slots disagree");
+        if ((rc = kmers_packed_impl(h, d_packed, d_starts + q0, nq, d_out + done, ns))) return rc;
+        done += ns;
+    }
+    if (done != n_slots) return fail(h, BRISK_HIP_EHIP, "correct: the candidate stream and its slots disagree");
+    return BRISK_HIP_OK;
+}
+
+// One batch of a composed call: d_slots[n_slots] are the slots of the reads of d_starts[0 .. n_reads] (the call's reads from r0 on)
+// and h->slot_buf holds their slot bases.  Its sites into h->corr_sites; then, in rounds of at most correct_batch_sites() sites, the
+// candidate windows into h->corr_cand, their slots into h->corr_slots (the batch's own slots are no longer needed: the lookups reuse
+// the handle's scratch), the decisions, and the correction rows appended to the call's table in h->corr_tab (which grows by copying).
+// st->n_corrected: the rows the table holds before the batch.
+int correct_batch(brisk_hip_index* h, const u32* d_packed, const uint16_t* d_slots, const u64* d_starts, u64 n_reads, u64 n_slots, u64 r0, u32 solid_min, u32 min_cover,
+                  brisk_hip_correct_stats* st) {
+    int rc;
+    st->n_slots += n_slots;
+    if (!n_slots) return BRISK_HIP_OK;
+    u64 n_runs = 0, n_sites = 0;
+    if ((rc = correct_sites_count(h, d_slots, d_starts, n_reads, n_slots, solid_min, min_cover, st, &n_runs, &n_sites))) return rc;
+    if (!n_sites) return BRISK_HIP_OK;
+    if ((rc = ensure(h, h->corr_sites, n_sites * 16))) return rc;
+    if ((rc = correct_sites_rows(h, d_starts, n_runs, min_cover, (CorrectSite*)h->corr_sites.p))) return rc;
+    const u64 k = h->P.k, round = correct_batch_sites();
+    for (u64 s0 = 0; s0 < n_sites; s0 += round) {
+        const u64 m = std::min<u64>(round, n_sites - s0);
+        const CorrectSite* d_sites = (const CorrectSite*)h->corr_sites.p + s0;
+        // a window has at most 2 k - 1 nucleotides: [the starts, 3 m + 1][the stream]
+        const u64 cap_words = (3 * m * (2 * k - 1) + 15) / 16 + 2;
+        const size_t off_packed = ((3 * m + 1) * 8 + 15) / 16 * 16;
+        if ((rc = ensure(h, h->corr_cand, off_packed + cap_words * 4))) return rc;
+        u64* d_cst = (u64*)h->corr_cand.p;
+        u32* d_cpk = (u32*)((char*)h->corr_cand.p + off_packed);
+        u64 n_nts = 0;
+        if ((rc = correct_windows_impl(h, d_packed, d_starts, n_reads, d_sites, m, {d_cpk, cap_words, d_cst, nullptr}, "correct", &n_nts))) return rc;
+        const u64 n_cs = n_nts - 3 * m * (k - 1);  // a window of cover + k - 1 nucleotides has `cover` slots
+        if ((rc = ensure(h, h->corr_slots, n_cs * 2))) return rc;
+        if ((rc = correct_lookups(h, d_cpk, d_cst, 3 * m, (uint16_t*)h->corr_slots.p, n_cs))) return rc;
+        u64 cnt[3] = {0, 0, 0};
+        if ((rc = correct_decide_impl(h, (const uint16_t*)h->corr_slots.p, d_sites, m, d_packed, d_starts, solid_min, cnt))) return rc;
+        const u64 have = st->n_corrected;
+        st->n_corrected += cnt[0];
+        st->n_ambiguous += cnt[1];
+        st->n_unresolved += cnt[2];
+        if (!cnt[0]) continue;
+        if (h->corr_tab.bytes < (have + cnt[0]) * 16) {
+            DevBuf grown;
+            if ((rc = ensure(h, grown, std::max<size_t>((have + cnt[0]) * 16, 2 * h->corr_tab.bytes)))) return rc;
+            if (have) HIPCHK(h, hipMemcpyAsync(grown.p, h->corr_tab.p, have * 16, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (h->corr_tab.p) HIPCHK(h, hipFree(h->corr_tab.p));
+            h->corr_tab = grown;
+        }
+        if ((rc = correct_rows(h, d_sites, m, r0, (CorrectRow*)h->corr_tab.p + have))) return rc;
+    }
+    return BRISK_HIP_OK;
+}
+
+// the patched copy of words [0, n_words + 2), queued on the stream; the table is valid
+int correct_apply_impl(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, const CorrectRow* d_rows, u64 n_rows, u64 n_words, u32* d_out, const char* who) {
+    if (n_words + 2 > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, std::string(who) + ": more output words than one launch covers");
+    hipLaunchKernelGGL(k_correct_apply, dim3(nblocks(n_words + 2, 256)), dim3(256), 0, h->stream, d_packed, d_starts, d_rows, n_rows, n_words, d_out);
+    return launch_check(h, "k_correct_apply");
 }
 
 }  // namespace
@@ -1229,6 +1439,207 @@ BRISK_API int brisk_hip_split_reads(brisk_hip_index* h, const char* bases, const
     if (frag_cap < nf) return fail(h, BRISK_HIP_ECAPACITY, "split_reads: " + std::to_string(nf) + " fragments, frag_cap is " + std::to_string(frag_cap));
     if (nf) {
         HIPCHK(h, hipMemcpyAsync(out_frags, h->split_tab.p, nf * 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return BRISK_HIP_OK;
+}
+
+// ---- spectral read correction ----
+BRISK_API int brisk_hip_weak_sites(brisk_hip_index* h, const uint16_t* d_slots, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, uint32_t min_cover,
+                                   brisk_hip_site* d_out_sites, uint64_t site_cap, brisk_hip_correct_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!stats || (n_reads && !d_starts) || (site_cap && !d_out_sites)) return fail(h, BRISK_HIP_EINVAL, "weak_sites: null pointer");
+    u32 c = 0;
+    if (int crc = check_min_cover(h, min_cover, "weak_sites", &c)) return crc;
+    memset(stats, 0, sizeof(*stats));
+    stats->n_reads = n_reads;
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    int rc;
+    u64 ns = 0, n_nts = 0, n_runs = 0, n_sites = 0;
+    if ((rc = split_check_table(h, d_starts, n_reads, "weak_sites", true, &n_nts))) return rc;
+    if ((rc = count_kmers(h, d_starts, n_reads, &ns))) return rc;
+    stats->n_slots = ns;
+    if (!ns) return BRISK_HIP_OK;
+    if (!d_slots) return fail(h, BRISK_HIP_EINVAL, "weak_sites: null pointer");
+    if ((rc = slot_bases(h, d_starts, n_reads))) return rc;
+    if ((rc = correct_sites_count(h, d_slots, d_starts, n_reads, ns, solid_min, c, stats, &n_runs, &n_sites))) return rc;
+    if (site_cap < n_sites) return fail(h, BRISK_HIP_ECAPACITY, "weak_sites: " + std::to_string(n_sites) + " sites, site_cap is " + std::to_string(site_cap));
+    if (!n_sites) return BRISK_HIP_OK;
+    if ((rc = correct_sites_rows(h, d_starts, n_runs, c, (CorrectSite*)d_out_sites))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_candidate_windows(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, const brisk_hip_site* d_sites, uint64_t n_sites,
+                                          uint32_t* d_out_packed, uint64_t out_cap_words, uint64_t* d_out_starts, uint64_t* n_out_nts) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!n_out_nts || !d_out_packed || !d_out_starts || (n_reads && (!d_packed || !d_starts)) || (n_sites && !d_sites)) return fail(h, BRISK_HIP_EINVAL, "candidate_windows: null pointer");
+    *n_out_nts = 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    int rc;
+    u64 unused = 0;
+    if (n_reads && (rc = split_check_table(h, d_starts, n_reads, "candidate_windows", false, &unused))) return rc;
+    if ((rc = correct_check_sites(h, (const CorrectSite*)d_sites, n_sites, d_starts, n_reads, "candidate_windows"))) return rc;
+    return correct_windows_impl(h, d_packed, d_starts, n_reads, (const CorrectSite*)d_sites, n_sites, {d_out_packed, out_cap_words, d_out_starts, nullptr}, "candidate_windows", n_out_nts);
+}
+
+BRISK_API int brisk_hip_decide_sites(brisk_hip_index* h, const uint16_t* d_cand_slots, const brisk_hip_site* d_sites, uint64_t n_sites, const uint32_t* d_packed,
+                                     const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, brisk_hip_correction* d_out_corrections, uint64_t corr_cap,
+                                     brisk_hip_correct_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!stats || (n_reads && (!d_packed || !d_starts)) || (n_sites && (!d_sites || !d_cand_slots)) || (corr_cap && !d_out_corrections))
+        return fail(h, BRISK_HIP_EINVAL, "decide_sites: null pointer");
+    memset(stats, 0, sizeof(*stats));
+    if (!n_sites) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    int rc;
+    u64 unused = 0, cnt[3] = {0, 0, 0};
+    if (n_reads && (rc = split_check_table(h, d_starts, n_reads, "decide_sites", false, &unused))) return rc;
+    if ((rc = correct_check_sites(h, (const CorrectSite*)d_sites, n_sites, d_starts, n_reads, "decide_sites"))) return rc;
+    if ((rc = correct_decide_impl(h, d_cand_slots, (const CorrectSite*)d_sites, n_sites, d_packed, d_starts, solid_min, cnt))) return rc;
+    stats->n_sites = n_sites;
+    stats->n_corrected = cnt[0];
+    stats->n_ambiguous = cnt[1];
+    stats->n_unresolved = cnt[2];
+    if (corr_cap < cnt[0]) return fail(h, BRISK_HIP_ECAPACITY, "decide_sites: " + std::to_string(cnt[0]) + " corrections, corr_cap is " + std::to_string(corr_cap));
+    if (!cnt[0]) return BRISK_HIP_OK;
+    if ((rc = correct_rows(h, (const CorrectSite*)d_sites, n_sites, 0, (CorrectRow*)d_out_corrections))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_apply_corrections(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, const brisk_hip_correction* d_corr,
+                                          uint64_t n_corr, uint32_t* d_out_packed, uint64_t out_cap_words) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (!d_out_packed || (n_reads && (!d_packed || !d_starts)) || (n_corr && !d_corr)) return fail(h, BRISK_HIP_EINVAL, "apply_corrections: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    int rc;
+    u64 unused = 0, last = 0;
+    if (n_reads) {
+        if ((rc = split_check_table(h, d_starts, n_reads, "apply_corrections", false, &unused))) return rc;
+        HIPCHK(h, hipMemcpyAsync(&last, d_starts + n_reads, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (n_corr) {
+        if (n_corr > 0x7fffffffull * 256) return fail(h, BRISK_HIP_EINVAL, "apply_corrections: more rows than one launch covers");
+        u64 bad = 0;
+        if (n_reads) {
+            if ((rc = ensure(h, h->corr_tmp, kCorrHead))) return rc;
+            unsigned long long* d_flag = (unsigned long long*)h->corr_tmp.p + 8;
+            HIPCHK(h, hipMemsetAsync(d_flag, 0xff, 8, h->stream));
+            hipLaunchKernelGGL(k_correct_row_check, dim3(nblocks(n_corr, 256)), dim3(256), 0, h->stream, (const CorrectRow*)d_corr, n_corr, d_packed, d_starts, n_reads, d_flag);
+            if ((rc = launch_check(h, "k_correct_row_check"))) return rc;
+            HIPCHK(h, hipMemcpyAsync(&bad, d_flag, 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+        if (bad != ~0ull)
+            return fail(h, BRISK_HIP_EINVAL, "apply_corrections: row " + std::to_string(bad) + " of the correction table names a read >= n_reads or a pos beyond its read, its `from` is not the base that is there, its `to` is `from` or no code, or it does not lie behind the row before it in (read, pos)");
+    }
+    const u64 n_words = (last + 15) / 16;
+    if (out_cap_words < n_words + 2)
+        return fail(h, BRISK_HIP_ECAPACITY, "apply_corrections: " + std::to_string(last) + " nucleotides need " + std::to_string(n_words + 2) + " words, out_cap_words is " + std::to_string(out_cap_words));
+    if (!n_reads) {
+        HIPCHK(h, hipMemsetAsync(d_out_packed, 0, 8, h->stream));
+    } else if ((rc = correct_apply_impl(h, d_packed, d_starts, (const CorrectRow*)d_corr, n_corr, n_words, d_out_packed, "apply_corrections"))) {
+        return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_correct_packed(brisk_hip_index* h, const uint32_t* d_packed, const uint64_t* d_starts, uint64_t n_reads, uint32_t solid_min, uint32_t min_cover,
+                                       uint32_t* d_out_packed, uint64_t out_cap_words, brisk_hip_correction* d_out_corrections, uint64_t corr_cap, brisk_hip_correct_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "correct_packed")) return wrc;
+    if (!stats || (n_reads && (!d_packed || !d_starts))) return fail(h, BRISK_HIP_EINVAL, "correct_packed: null pointer");
+    if (!d_out_packed && out_cap_words) return fail(h, BRISK_HIP_EINVAL, "correct_packed: out_cap_words without d_out_packed");
+    if (!d_out_corrections && corr_cap) return fail(h, BRISK_HIP_EINVAL, "correct_packed: corr_cap without d_out_corrections");
+    u32 c = 0;
+    if (int crc = check_min_cover(h, min_cover, "correct_packed", &c)) return crc;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    int rc;
+    memset(stats, 0, sizeof(*stats));
+    stats->n_reads = n_reads;
+    u64 last = 0;
+    if (n_reads) {
+        u64 n_nts = 0;
+        if ((rc = split_check_table(h, d_starts, n_reads, "correct_packed", true, &n_nts))) return rc;
+        HIPCHK(h, hipMemcpyAsync(&last, d_starts + n_reads, 8, hipMemcpyDeviceToHost, h->stream));
+        // a sibling of brisk_hip_split_packed's loop: a batch's slots into kout_tmp, and its corrections instead of its fragments
+        const u64 batch = profile_batch_limit(h);
+        for (u64 r0 = 0; r0 < n_reads; r0 += batch) {
+            const u64 nb = std::min<u64>(batch, n_reads - r0);
+            u64 ns = 0;
+            if ((rc = count_kmers(h, d_starts + r0, nb, &ns))) return rc;
+            if (ns) {
+                if ((rc = ensure(h, h->kout_tmp, ns * 2))) return rc;
+                HIPCHK(h, hipMemsetAsync(h->kout_tmp.p, 0, ns * 2, h->stream));
+                if ((rc = kmers_packed_impl(h, d_packed, d_starts + r0, nb, (uint16_t*)h->kout_tmp.p, ns))) return rc;
+            }
+            if ((rc = correct_batch(h, d_packed, (const uint16_t*)h->kout_tmp.p, d_starts + r0, nb, ns, r0, solid_min, c, stats))) return rc;
+        }
+        if ((rc = check_device_flags(h))) return rc;
+    }
+    const u64 nc = stats->n_corrected, n_words = (last + 15) / 16;
+    if (d_out_corrections && corr_cap < nc) return fail(h, BRISK_HIP_ECAPACITY, "correct_packed: " + std::to_string(nc) + " corrections, corr_cap is " + std::to_string(corr_cap));
+    if (d_out_packed && out_cap_words < n_words + 2)
+        return fail(h, BRISK_HIP_ECAPACITY, "correct_packed: " + std::to_string(last) + " nucleotides need " + std::to_string(n_words + 2) + " words, out_cap_words is " + std::to_string(out_cap_words));
+    if (d_out_packed) {
+        if (!n_reads) HIPCHK(h, hipMemsetAsync(d_out_packed, 0, 8, h->stream));
+        else if ((rc = correct_apply_impl(h, d_packed, d_starts, (const CorrectRow*)h->corr_tab.p, nc, n_words, d_out_packed, "correct_packed"))) return rc;
+    }
+    if (d_out_corrections && nc) HIPCHK(h, hipMemcpyAsync(d_out_corrections, h->corr_tab.p, nc * 16, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_correct_reads(brisk_hip_index* h, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint32_t solid_min, uint32_t min_cover,
+                                      brisk_hip_correction* out_corrections, uint64_t corr_cap, brisk_hip_correct_stats* stats) {
+    if (!h) return BRISK_HIP_EINVAL;
+    if (int wrc = need_whole_index(h, "correct_reads")) return wrc;
+    if (!stats || (corr_cap && !out_corrections) || (n_reads && (!bases || !offsets))) return fail(h, BRISK_HIP_EINVAL, "correct_reads: null pointer");
+    u32 c = 0;
+    if (int crc = check_min_cover(h, min_cover, "correct_reads", &c)) return crc;
+    for (u64 r = 0; r < n_reads; r++) {
+        if (offsets[r + 1] < offsets[r]) return fail(h, BRISK_HIP_EINVAL, "read offsets do not ascend (offsets[i + 1] < offsets[i])");
+        if (offsets[r + 1] - offsets[r] > 0xffffffffull) return fail(h, BRISK_HIP_EINVAL, "correct_reads: a read of 2^32 nucleotides or more does not fit the correction record");
+    }
+    memset(stats, 0, sizeof(*stats));
+    stats->n_reads = n_reads;
+    if (!n_reads) return BRISK_HIP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> call_lock(h->call_mu);
+    if (int frc = enter(h)) return frc;
+    // a sibling of profile_host_batches: a batch is uploaded and packed, its slots go to kout_tmp, and the stream is waited for before
+    // the next batch's upload overwrites the packed stream that this one's kernels read
+    const u64 saved = h->max_batch_reads;
+    h->max_batch_reads = profile_batch_limit(h);
+    int rc = for_each_host_batch(h, bases, offsets, n_reads, [&](u64 r0, u64 nr) -> int {
+        int rc2;
+        const u64 ns = host_slots(offsets, r0, r0 + nr, h->P.k);
+        if (ns) {
+            if ((rc2 = ensure(h, h->kout_tmp, ns * 2))) return rc2;
+            HIPCHK(h, hipMemsetAsync(h->kout_tmp.p, 0, ns * 2, h->stream));
+            if ((rc2 = kmers_packed_impl(h, (const u32*)h->packed_tmp.p, (const u64*)h->starts_tmp.p, nr, (uint16_t*)h->kout_tmp.p, ns))) return rc2;
+        }
+        if ((rc2 = correct_batch(h, (const u32*)h->packed_tmp.p, (const uint16_t*)h->kout_tmp.p, (const u64*)h->starts_tmp.p, nr, ns, r0, solid_min, c, stats))) return rc2;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BRISK_HIP_OK;
+    });
+    h->max_batch_reads = saved;
+    if (rc) return rc;
+    if ((rc = check_device_flags(h))) return rc;
+    const u64 nc = stats->n_corrected;
+    if (corr_cap < nc) return fail(h, BRISK_HIP_ECAPACITY, "correct_reads: " + std::to_string(nc) + " corrections, corr_cap is " + std::to_string(corr_cap));
+    if (nc) {
+        HIPCHK(h, hipMemcpyAsync(out_corrections, h->corr_tab.p, nc * 16, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return BRISK_HIP_OK;

@@ -1,6 +1,6 @@
 // brisk_kernels.hip -- HIP kernels of the Brisk hot path for gfx950 (MI355X).
 //
-// One translation unit, twelve parts:
+// One translation unit, thirteen parts:
 //   brisk_scan.hip       reads -> super-k-mer records (SuperKmerEnumerator::next, Kmers.cpp:522-603,
 //                        + hash_kmer_minimizer_inplace / get_compacted, Kmers.cpp:138-145,191-200); long sequences in chunks
 //   brisk_partition.hip  records -> partition order (histogram prefix, k_scatter) and -> owner order (multi-GPU routing)
@@ -13,6 +13,7 @@
 //   brisk_extract.hip    records -> nucleotide intervals, and the kept intervals of a packed stream gathered into a new one
 //   brisk_intake.hip     raw bytes and qualities -> fragments (maximal clean runs of a read), gathered into a packed stream
 //   brisk_split.hip      slots -> the solid runs of every read as fragments (over the intake's passes), a fragment table -> the gather's tables
+//   brisk_correct.hip    slots -> the weak runs that one substitution explains (sites), their candidate windows, the decisions, the patched stream
 //   brisk_pairs.hip      paired-end bookkeeping over intervals: one interval per raw read, the pair decision, two cuts chained, pairs / singles split
 //
 // All of it is integer / byte work (plus the FP64 decycling class); there is no MFMA-shaped work on this path.
@@ -33,4 +34,5 @@
 #include "brisk_extract.hip"
 #include "brisk_intake.hip"
 #include "brisk_split.hip"
+#include "brisk_correct.hip"
 #include "brisk_pairs.hip"

@@ -10,7 +10,7 @@
 // that mask as they are.  Positions are slot indices of the batch (the intake's a0 is 0).
 //
 // k_split_offsets     soff[r] = the first slot of read r, soff[n_reads] = the batch's slots: the read table the intake's passes take
-// k_split_mask        per lane of 16 slots: which are solid; per block of INTAKE_BLOCK slots the last position at which a run can begin
+// k_split_mask        per lane of 16 slots: which are solid (<true>: which are not: brisk_correct.hip); per block of INTAKE_BLOCK slots the last position at which a run can begin
 // k_split_rows        a run {read, first slot i, s slots} -> the fragment {read + r0, start = i, len = s + k - 1}: one vector store a row
 // k_split_frag_block  a caller's fragment table, per block of 4096 rows: the nucleotides, the first bad row flagged (count pass);
 //                     k_slot_top (brisk_scan.hip) scans the block sums
@@ -24,21 +24,26 @@ __global__ void __launch_bounds__(256) k_split_offsets(const u64* __restrict__ s
 }
 
 __device__ __forceinline__ u32 split_solid(u32 v, u32 solid_min) { return (v & 0x100u) != 0 && (v & 0xffu) >= solid_min; }
+__device__ __forceinline__ u64 split_min16(u64 n) { return n < 16 ? n : 16; }
 
 // mask[lane]: the read-start bits (<< 16, k_intake_bounds) stand; the valid bits are added.  carry[block]: as k_intake_mask leaves it.
+// WEAK (brisk_correct.hip): the mask inverted over the slots that exist -- valid = not solid, and the runs are the weak runs.
+template <bool WEAK>
 __global__ void __launch_bounds__(256) k_split_mask(const uint16_t* __restrict__ slots, u64 n_slots, u32 solid_min, u32* __restrict__ mask, u64* __restrict__ carry) {
     __shared__ u64 s_last[4];
     const u64 lane = (u64)blockIdx.x * 256 + threadIdx.x;
     const u64 x0 = lane * 16;
-    u32 valid = 0;
+    u32 valid = 0, exist = 0xffffu;  // exist: which of the lane's 16 positions are slots
     if (x0 + 16 <= n_slots && ((uintptr_t)slots & 15) == 0) {  // (a caller's slots are aligned as uint16 asks: 2 bytes)
         const uint4 a = reinterpret_cast<const uint4*>(slots + x0)[0], b = reinterpret_cast<const uint4*>(slots + x0)[1];
         const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
         for (int i = 0; i < 8; i++) valid |= (split_solid(w[i] & 0xffffu, solid_min) << (2 * i)) | (split_solid(w[i] >> 16, solid_min) << (2 * i + 1));
     } else {
+        exist = x0 < n_slots ? 0xffffu >> (16 - (u32)split_min16(n_slots - x0)) : 0u;
         for (u32 i = 0; i < 16 && x0 + i < n_slots; i++) valid |= split_solid(slots[x0 + i], solid_min) << i;
     }
+    if (WEAK) valid = ~valid & exist;
     const u32 bnd = mask[lane] >> 16;
     mask[lane] = valid | (bnd << 16);
     // where a run can begin: after a slot that is not solid, or at a read's first slot

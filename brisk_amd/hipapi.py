@@ -129,6 +129,7 @@ SYMBOLS = [
     "brisk_hip_fragment_intervals", "brisk_hip_pair_intervals", "brisk_hip_compose_intervals", "brisk_hip_extract_pairs_packed",
     "brisk_hip_trim_pairs_packed", "brisk_hip_trim_pairs_reads", "brisk_hip_clean_pairs_ascii", "brisk_hip_clean_pairs_reads",
     "brisk_hip_solid_runs", "brisk_hip_extract_fragments_packed", "brisk_hip_split_packed", "brisk_hip_split_reads",
+    "brisk_hip_weak_sites", "brisk_hip_candidate_windows", "brisk_hip_decide_sites", "brisk_hip_apply_corrections", "brisk_hip_correct_packed", "brisk_hip_correct_reads",
     "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_joint_spectrum", "brisk_hip_filter_joint", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
     "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
@@ -190,6 +191,13 @@ def load() -> C.CDLL:
     L.brisk_hip_extract_fragments_packed.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
     L.brisk_hip_split_packed.argtypes = [vp, vp, vp, u64, u32, u32, vp, u64, vp, vp, u64, C.POINTER(_SplitStats)]
     L.brisk_hip_split_reads.argtypes = [vp, _u8p, _u64p, u64, u32, u32, _fragp, u64, C.POINTER(_SplitStats)]
+    _corrp = np.ctypeslib.ndpointer(dtype=CORRECTION_DTYPE, flags="C_CONTIGUOUS")
+    L.brisk_hip_weak_sites.argtypes = [vp, vp, vp, u64, u32, u32, vp, u64, C.POINTER(_CorrectStats)]
+    L.brisk_hip_candidate_windows.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
+    L.brisk_hip_decide_sites.argtypes = [vp, vp, vp, u64, vp, vp, u64, u32, vp, u64, C.POINTER(_CorrectStats)]
+    L.brisk_hip_apply_corrections.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64]
+    L.brisk_hip_correct_packed.argtypes = [vp, vp, vp, u64, u32, u32, vp, u64, vp, u64, C.POINTER(_CorrectStats)]
+    L.brisk_hip_correct_reads.argtypes = [vp, _u8p, _u64p, u64, u32, u32, _corrp, u64, C.POINTER(_CorrectStats)]
     L.brisk_hip_enumerate.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64)]
     L.brisk_hip_stats.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.brisk_hip_checksum.argtypes = [vp, _u64p]
@@ -485,6 +493,102 @@ def fragments_from_slots(counts, found, base, k: int, solid_min: int = 2, min_le
         st["n_reads_kept"] += bool(keep.any())
         rows.extend((r, int(a), int(n) + k - 1) for a, n in zip(starts[keep], lens[keep]))
     return np.array(rows, FRAGMENT_DTYPE) if rows else np.zeros(0, FRAGMENT_DTYPE), st
+
+
+# ---- spectral read correction (include/brisk_hip.h, "spectral read correction"): isolated substitutions repaired ----
+SITE_DTYPE = np.dtype([("read", "<u8"), ("pos", "<u4"), ("cover", "<u4")])
+CORRECTION_DTYPE = np.dtype([("read", "<u8"), ("pos", "<u4"), ("from", "u1"), ("to", "u1"), ("cover", "<u2")])
+assert SITE_DTYPE.itemsize == 16 and CORRECTION_DTYPE.itemsize == 16
+CORRECT_STATS_FIELDS = ("n_reads", "n_slots", "n_weak", "n_runs", "n_sites", "n_skip_whole", "n_skip_long", "n_skip_short", "n_corrected", "n_ambiguous", "n_unresolved")
+
+
+class _CorrectStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in CORRECT_STATS_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in CORRECT_STATS_FIELDS}
+
+
+def sites_from_slots(counts, found, base, k: int, solid_min: int = 2, min_cover: Optional[int] = None):
+    """The rule of brisk_hip_weak_sites on the host: (SITE_DTYPE[n_sites], stats dict) from the three outputs of BriskHip.get_kmers.
+    The definition, written out; no device needed.  A weak run is a maximal stretch [i, i + w) of slots of one read (n slots) that
+    are not solid.  In this order: whole when i == 0 and i + w == n; long when w > k; short when it is interior (i > 0, i + w < n)
+    with w < k, or when w < C (C = min_cover; None or 0: k); else the site {read, pos, cover = w}, pos = i + w - 1 when a solid slot
+    follows the run and i + k - 1 when the run ends the read.  Sites are ordered by read, then by pos.  stats: CORRECT_STATS_FIELDS,
+    the three decision counters zero.  ValueError when min_cover is above k."""
+    counts = np.asarray(counts, np.uint8)
+    weak = ~(np.asarray(found, bool) & (counts.astype(np.int64) >= int(solid_min)))
+    base = np.asarray(base, np.uint64).astype(np.int64)
+    c = int(min_cover) if min_cover else k
+    if not 1 <= c <= k:
+        raise ValueError("min_cover must be in 1..k (0 or None: k)")
+    n_reads = len(base) - 1
+    st = dict.fromkeys(CORRECT_STATS_FIELDS, 0)
+    st["n_reads"] = n_reads
+    st["n_slots"] = int(base[-1]) if n_reads > 0 else 0
+    rows = []
+    for r in range(n_reads):
+        wk = weak[base[r]:base[r + 1]]
+        n = len(wk)
+        if not wk.any():
+            continue
+        edge = np.diff(np.concatenate(([0], wk.astype(np.int8), [0])))  # runs: where the padded mask rises and falls
+        begins, ends = np.nonzero(edge == 1)[0], np.nonzero(edge == -1)[0]
+        st["n_weak"] += int((ends - begins).sum())
+        st["n_runs"] += len(begins)
+        for i, e in zip(begins.tolist(), ends.tolist()):
+            w = e - i
+            if i == 0 and e == n:
+                st["n_skip_whole"] += 1
+            elif w > k:
+                st["n_skip_long"] += 1
+            elif (i > 0 and e < n and w < k) or w < c:
+                st["n_skip_short"] += 1
+            else:
+                st["n_sites"] += 1
+                rows.append((r, e - 1 if e < n else i + k - 1, w))
+    return np.array(rows, SITE_DTYPE) if rows else np.zeros(0, SITE_DTYPE), st
+
+
+def site_windows(sites, k: int) -> np.ndarray:
+    """The windows of a site table: FRAGMENT_DTYPE[n_sites] -- nucleotides [a, a + cover + k - 1) of the site's read, a = max(0, pos -
+    k + 1).  The slots of a window are the slots of the site's weak run; candidate c of the site is the window with the base at
+    pos - a replaced by the c-th of the three other codes of "ACTG" (codes 0..3), ascending."""
+    t = np.asarray(sites)
+    out = np.zeros(len(t), FRAGMENT_DTYPE)
+    out["read"] = t["read"]
+    out["start"] = np.maximum(t["pos"].astype(np.int64) - (k - 1), 0)
+    out["len"] = t["cover"] + (k - 1)
+    return out
+
+
+def corrections_from_candidates(cand_counts, cand_found, sites, solid_min: int = 2, from_codes=None):
+    """The rule of brisk_hip_decide_sites on the host: (CORRECTION_DTYPE[n_corrected], counts dict) from the slots of the candidate
+    stream (BriskHip.get_kmers over the 3 * n_sites candidate strings: 3 * cover slots a site, in site order).  A candidate passes
+    when all `cover` of its slots are solid; exactly one passes: a correction row; two or three: ambiguous; none: unresolved.
+    from_codes[s]: the packed code (A0 C1 T2 G3) of the base at the site in the input; candidate c stands for the c-th of the three
+    other codes, ascending, which becomes the row's `to` (None: from = 0 for every site).  counts: n_sites, n_corrected,
+    n_ambiguous, n_unresolved."""
+    t = np.asarray(sites)
+    solid = np.asarray(cand_found, bool) & (np.asarray(cand_counts, np.uint8).astype(np.int64) >= int(solid_min))
+    frm = np.zeros(len(t), np.int64) if from_codes is None else np.asarray(from_codes, np.int64)
+    rows, at = [], 0
+    cnt = {"n_sites": len(t), "n_corrected": 0, "n_ambiguous": 0, "n_unresolved": 0}
+    for s in range(len(t)):
+        cover = int(t["cover"][s])
+        passing = [c for c in range(3) if solid[at + c * cover:at + (c + 1) * cover].all()]
+        at += 3 * cover
+        if len(passing) == 1:
+            c, f = passing[0], int(frm[s])
+            rows.append((int(t["read"][s]), int(t["pos"][s]), f, c + (c >= f), cover))
+            cnt["n_corrected"] += 1
+        elif passing:
+            cnt["n_ambiguous"] += 1
+        else:
+            cnt["n_unresolved"] += 1
+    if at != len(solid):
+        raise ValueError("the candidate slots are not 3 * cover a site")
+    return np.array(rows, CORRECTION_DTYPE) if rows else np.zeros(0, CORRECTION_DTYPE), cnt
 
 
 # ---- paired-end reads (include/brisk_hip.h, "paired-end reads"): an interleaved stream, reads 2p and 2p + 1 the mates of pair p ----
@@ -821,6 +925,21 @@ class BriskHip:
         st = _SplitStats()
         self._chk(self.L.brisk_hip_split_reads(self.h, flat, offs, len(offs) - 1, solid_min, min_len, out, cap, C.byref(st)))
         return out[:st.n_fragments].copy(), st.as_dict()
+
+    def correct_reads(self, seqs: Sequence, solid_min: int = 2, min_cover: Optional[int] = None):
+        """Isolated substitutions found and decided on the device (brisk_hip_correct_reads): (CORRECTION_DTYPE[n_corrected], stats
+        dict) -- a row says that nucleotide pos of read `read` holds code `from` and should hold code `to` (codes of "ACTG"); the
+        caller patches its own strings.  What sites_from_slots, the candidate strings, get_kmers over them and
+        corrections_from_candidates give, computed on the device.  min_cover (None or 0: k): the fewest weak k-mers a run at a
+        read's edge may have and still be attempted.  stats: CORRECT_STATS_FIELDS."""
+        flat, offs = _pack_reads(seqs)
+        cap = max(1, (int(kmer_slots(offs, self.k)[-1]) + len(offs)) // 2)  # a read of n slots has at most (n + 1) / 2 weak runs
+        out = np.zeros(cap, CORRECTION_DTYPE)
+        if len(flat) == 0:
+            flat = np.zeros(1, np.uint8)
+        st = _CorrectStats()
+        self._chk(self.L.brisk_hip_correct_reads(self.h, flat, offs, len(offs) - 1, solid_min, int(min_cover or 0), out, cap, C.byref(st)))
+        return out[:st.n_corrected].copy(), st.as_dict()
 
     def intake(self, seqs: Sequence, quals: Optional[Sequence] = None, rule: Optional[_IntakeRule] = None):
         """The fragments of raw reads (brisk_hip_intake_reads): (FRAGMENT_DTYPE[n_fragments], stats dict) -- what
@@ -1215,6 +1334,50 @@ class BriskHip:
         st = _SplitStats()
         return self._split_call(self.L.brisk_hip_split_packed(self.h, d_packed or None, d_starts or None, n_reads, solid_min, min_len, d_out_packed or None, out_cap_words,
                                                               d_out_starts or None, d_out_frags or None, frag_cap, C.byref(st)), st, raise_on_capacity)
+
+    def _correct_call(self, rc: int, st: _CorrectStats, raise_on_capacity: bool) -> dict:
+        if rc == ECAPACITY and not raise_on_capacity:
+            return dict(st.as_dict(), rc=rc)
+        self._chk(rc)
+        return st.as_dict()
+
+    def weak_sites(self, d_slots: int, d_starts: int, n_reads: int, d_out_sites: int, site_cap: int, solid_min: int = 2, min_cover: Optional[int] = None,
+                   raise_on_capacity: bool = True) -> dict:
+        """The site table of slots the caller holds (brisk_hip_weak_sites), everything on the device; sites_from_slots is the
+        definition.  Returns the stats; with raise_on_capacity=False an ECAPACITY answer returns them too, with "rc" set.  Needs
+        no index state."""
+        st = _CorrectStats()
+        return self._correct_call(self.L.brisk_hip_weak_sites(self.h, d_slots or None, d_starts or None, n_reads, solid_min, int(min_cover or 0), d_out_sites or None, site_cap,
+                                                              C.byref(st)), st, raise_on_capacity)
+
+    def candidate_windows(self, d_packed: int, d_starts: int, n_reads: int, d_sites: int, n_sites: int, d_out_packed: int, out_cap_words: int, d_out_starts: int) -> int:
+        """The 3 * n_sites candidate windows of a site table as a packed stream, substituted (brisk_hip_candidate_windows), everything
+        on the device.  d_out_starts holds 3 * n_sites + 1 uint64.  Returns the nucleotides written.  Needs no index state."""
+        n_nts = C.c_uint64()
+        self._chk(self.L.brisk_hip_candidate_windows(self.h, d_packed or None, d_starts or None, n_reads, d_sites or None, n_sites, d_out_packed or None, out_cap_words,
+                                                     d_out_starts or None, C.byref(n_nts)))
+        return n_nts.value
+
+    def decide_sites(self, d_cand_slots: int, d_sites: int, n_sites: int, d_packed: int, d_starts: int, n_reads: int, d_out_corrections: int, corr_cap: int,
+                     solid_min: int = 2, raise_on_capacity: bool = True) -> dict:
+        """Candidate slots to correction rows (brisk_hip_decide_sites), everything on the device; corrections_from_candidates is the
+        definition.  Returns the stats (n_sites and the three decision counters).  Needs no index state."""
+        st = _CorrectStats()
+        return self._correct_call(self.L.brisk_hip_decide_sites(self.h, d_cand_slots or None, d_sites or None, n_sites, d_packed or None, d_starts or None, n_reads, solid_min,
+                                                                d_out_corrections or None, corr_cap, C.byref(st)), st, raise_on_capacity)
+
+    def apply_corrections(self, d_packed: int, d_starts: int, n_reads: int, d_corr: int, n_corr: int, d_out_packed: int, out_cap_words: int):
+        """The patched copy of a packed stream (brisk_hip_apply_corrections), everything on the device.  Needs no index state."""
+        self._chk(self.L.brisk_hip_apply_corrections(self.h, d_packed or None, d_starts or None, n_reads, d_corr or None, n_corr, d_out_packed or None, out_cap_words))
+
+    def correct_packed(self, d_packed: int, d_starts: int, n_reads: int, d_out_packed: int, out_cap_words: int, d_out_corrections: int, corr_cap: int,
+                       solid_min: int = 2, min_cover: Optional[int] = None, raise_on_capacity: bool = True) -> dict:
+        """Lookups, sites, candidates, decisions and the patched copy in one call (brisk_hip_correct_packed): the corrected stream
+        has the input's read table and goes straight to insert_packed, get_packed or read_profile_packed; d_out_packed (with
+        out_cap_words 0) and d_out_corrections (with corr_cap 0) may be 0.  Returns the stats, as weak_sites does."""
+        st = _CorrectStats()
+        return self._correct_call(self.L.brisk_hip_correct_packed(self.h, d_packed or None, d_starts or None, n_reads, solid_min, int(min_cover or 0), d_out_packed or None,
+                                                                  out_cap_words, d_out_corrections or None, corr_cap, C.byref(st)), st, raise_on_capacity)
 
     def pack_ascii(self, d_bases: int, n_bases: int, d_packed: int):
         self._chk(self.L.brisk_hip_pack_ascii(self.h, d_bases, n_bases, d_packed))

@@ -66,6 +66,11 @@
  *   brisk_hip_solid_runs / brisk_hip_extract_fragments_packed / brisk_hip_split_packed / brisk_hip_split_reads
  *                               no reference counterpart; Quake, BFC and khmer's trim-low-abund -V are the usual tools: a read is
  *                               cut at its weak k-mers and every run of solid k-mers leaves as a fragment of its own
+ *   brisk_hip_weak_sites / brisk_hip_candidate_windows / brisk_hip_decide_sites / brisk_hip_apply_corrections /
+ *   brisk_hip_correct_packed / brisk_hip_correct_reads
+ *                               no reference counterpart; Quake and BFC are the usual tools: a run of weak k-mers that one
+ *                               substitution explains names the nucleotide, the three other bases are tried there, and the read is
+ *                               repaired, whole, when exactly one of them makes every k-mer of the run solid
  *   brisk_hip_lookup            Brisk::get (brisk/Brisk.hpp:64-69)
  *   brisk_hip_enumerate         Brisk::next / restart_kmer_enumeration
  *                               (brisk/Brisk.hpp:166-179, brisk/DenseMenuYo.hpp:476-521)
@@ -561,6 +566,101 @@ int brisk_hip_split_packed(brisk_hip_index *h, const uint32_t *d_packed, const u
 int brisk_hip_split_reads(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
                           uint32_t solid_min, uint32_t min_len, brisk_hip_fragment *out_frags /* HOST */, uint64_t frag_cap,
                           brisk_hip_split_stats *stats /* HOST */);
+
+/* ---- spectral read correction: isolated substitutions repaired (no reference counterpart; kernels: brisk_correct.hip) ---- */
+/* SLOT, PRESENT and SOLID mean what they mean in brisk_hip_read_profile; read r has n = max(0, len - k + 1) slots.  A WEAK RUN is a
+ * maximal stretch [i, i + w) of consecutive slots of one read that are not solid; it never crosses a read boundary.  Every weak run
+ * falls into exactly one class, the tests applied in this order:
+ *   whole   i == 0 && i + w == n: nothing solid anchors it
+ *   long    w > k: more than one error
+ *   short   (i > 0 && i + w < n && w < k): an interior run that an isolated substitution cannot explain; or w < C, where C =
+ *           min_cover, 0 meaning k (allowed: 0..k, else EINVAL)
+ *   else a SITE {read, pos, cover = w}: pos = i + w - 1 when a solid slot follows the run (i + w < n: interior runs of w == k, and
+ *           runs at the read's left edge), pos = i + k - 1 when the run ends the read (i + w == n, i > 0).  A single substitution
+ *           at nucleotide pos is the only one-error explanation of the run.
+ * With min_cover = k only errors at least k - 1 nucleotides from both ends are attempted; smaller values reach towards the ends with
+ * fewer witnesses.  Sites are ordered by read, then by pos; two sites of one read are at least k + 1 nucleotides apart, so no
+ * site's window holds another site.  The WINDOW of a site is nucleotides [a, a + cover + k - 1) of its read, a = max(0, pos - k + 1):
+ * its slots are exactly the run's.  A site has three CANDIDATES: the window with the base at pos replaced by one of the three other
+ * 2-bit codes of the packed layout (A0 C1 T2 G3), in ascending code order.  Each candidate is looked up as a read of its own
+ * (brisk_hip_get_kmers over the candidate stream): a k-mer is looked up under the (kmer_s, minimizer_idx) that the scan of the
+ * WINDOW gives it, as brisk_hip_get_kmers does for whole reads (where that differs from its identity in the read the k-mer is absent
+ * and the candidate fails: a true base can stay unresolved, a wrong one is never put in).  A candidate PASSES when all `cover` of its slots are solid at the
+ * same solid_min.  Exactly one passes: the site is CORRECTED; two or three: AMBIGUOUS, and the read stays as it is there; none:
+ * UNRESOLVED.  The OUTPUT is the input stream with the two bits of every corrected site replaced and nothing else changed: the word
+ * count, the read table, the zero bits after the last nucleotide and the two readable words behind the stream are the input's.
+ * Not covered: insertions, deletions and errors within k of each other (they leave long or short runs); iterating to a fixed point
+ * (call it again on its output); qualities; sharded handles in the composed calls; FASTQ output.  brisk_amd.sites_from_slots and
+ * corrections_from_candidates are the same rules in numpy: the definitions the tests compare with. */
+typedef struct brisk_hip_site { uint64_t read; uint32_t pos, cover; } brisk_hip_site; /* 16 bytes; pos is relative to the read */
+typedef struct brisk_hip_correction { uint64_t read; uint32_t pos; uint8_t from, to; uint16_t cover; } brisk_hip_correction; /* 16 bytes; from, to: packed codes */
+typedef struct brisk_hip_correct_stats {
+    uint64_t n_reads;
+    uint64_t n_slots;
+    uint64_t n_weak;        /* slots that are not solid */
+    uint64_t n_runs;        /* weak runs: n_sites + n_skip_whole + n_skip_long + n_skip_short, always */
+    uint64_t n_sites;       /* n_corrected + n_ambiguous + n_unresolved, always (calls that decide) */
+    uint64_t n_skip_whole;
+    uint64_t n_skip_long;
+    uint64_t n_skip_short;
+    uint64_t n_corrected;
+    uint64_t n_ambiguous;
+    uint64_t n_unresolved;
+} brisk_hip_correct_stats;  /* 88 bytes */
+/* The sites of slots the caller holds (d_slots, DEVICE, read by d_starts exactly as brisk_hip_solid_runs reads them) -> d_out_sites
+ * (DEVICE, site_cap rows of room).  Fills every field of *stats (HOST) but the three decision counters.  BRISK_HIP_ECAPACITY when
+ * site_cap < n_sites: nothing is written, *stats is filled, and the call can be repeated with room (what always suffices: a read of n
+ * slots has at most (n + 1) / 2 weak runs).  EINVAL: min_cover > k, a read table that does not ascend, a read of 2^32 nucleotides
+ * or more, null pointers.  Every row is stored once, by a plain vector store.  Needs no index state: works on any handle. */
+int brisk_hip_weak_sites(brisk_hip_index *h, const uint16_t *d_slots, const uint64_t *d_starts, uint64_t n_reads,
+                         uint32_t solid_min, uint32_t min_cover, brisk_hip_site *d_out_sites, uint64_t site_cap,
+                         brisk_hip_correct_stats *stats /* HOST */);
+/* The 3 * n_sites candidate windows of a site table (d_sites[n_sites], DEVICE; any table) as a packed stream in the layout of
+ * brisk_hip_extract_packed, the substitution already in them: candidate c of site s is read 3 s + c of the output, and
+ * d_out_starts[0 .. 3 * n_sites] ascends from 0.  EINVAL, nothing written, the message naming the first bad row: read >= n_reads, a
+ * cover of 0 or above k, pos or the window beyond the read; also a read table that does not ascend and null pointers.
+ * BRISK_HIP_ECAPACITY, nothing written, *n_out_nts (HOST) filled: out_cap_words < ceil(n_nts / 16) + 2.  The output may not overlap
+ * the inputs.  Every output word is stored once by a plain vector store.  Needs no index state: works on any handle. */
+int brisk_hip_candidate_windows(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                                const brisk_hip_site *d_sites, uint64_t n_sites,
+                                uint32_t *d_out_packed, uint64_t out_cap_words, uint64_t *d_out_starts /* 3 * n_sites + 1 room */,
+                                uint64_t *n_out_nts /* HOST */);
+/* The decisions: d_cand_slots (DEVICE) holds the slots of the candidate stream of d_sites as brisk_hip_get_kmers_packed answers
+ * them (3 * cover slots a site, in site order) -> one correction row per corrected site, in site order, d_out_corrections (DEVICE,
+ * corr_cap rows of room); `from` is read from the input stream.  Fills n_sites and the three decision counters of *stats (HOST), zero
+ * elsewhere.  BRISK_HIP_ECAPACITY when corr_cap < n_corrected: nothing is written, *stats is filled.  EINVAL as for
+ * brisk_hip_candidate_windows.  Needs no index state: works on any handle. */
+int brisk_hip_decide_sites(brisk_hip_index *h, const uint16_t *d_cand_slots, const brisk_hip_site *d_sites, uint64_t n_sites,
+                           const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads, uint32_t solid_min,
+                           brisk_hip_correction *d_out_corrections, uint64_t corr_cap, brisk_hip_correct_stats *stats /* HOST */);
+/* The patched copy of a packed stream: every word of the input, its two readable words included (out_cap_words >=
+ * ceil(d_starts[n_reads] / 16) + 2, else BRISK_HIP_ECAPACITY), with `to` at nucleotide pos of read `read` for every row of
+ * d_corr[n_corr] (DEVICE).  EINVAL, nothing written, the message naming the first bad row: read >= n_reads, pos beyond the read, `from`
+ * is not the base that is there, to == from or no code, or the table does not strictly ascend by (read, pos); also a read table that
+ * does not ascend and null pointers.  The output may not overlap the input.  Every output word is stored once by a plain vector
+ * store: the lane that owns a word searches the table, which ascends in absolute nucleotide position.  Works on any handle. */
+int brisk_hip_apply_corrections(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                                const brisk_hip_correction *d_corr, uint64_t n_corr, uint32_t *d_out_packed, uint64_t out_cap_words);
+/* brisk_hip_get_kmers_packed, weak_sites, candidate_windows, get_kmers_packed over the candidates, decide_sites and
+ * apply_corrections in one call, batch by batch like brisk_hip_split_packed.  A batch's slots exist for one internal batch at a time;
+ * its sites are decided in rounds of at most BRISK_CORRECT_BATCH sites (environment, read once per process; default 2^22; a test
+ * hook), which bounds the scratch memory of a round at roughly 3 * (2 k - 1) / 4 + 6 k bytes a site for the candidate stream and its
+ * slots, plus about 128 bytes a site of tables; the correction table accumulates in scratch memory (16 bytes a row, reads numbered as in
+ * the call).  Nothing is written to the caller's outputs before the capacities are known to suffice: BRISK_HIP_ECAPACITY when
+ * corr_cap < n_corrected (with d_out_corrections != NULL) or out_cap_words < ceil(d_starts[n_reads] / 16) + 2 (with d_out_packed !=
+ * NULL), *stats filled.  d_out_corrections may be NULL; d_out_packed == NULL with out_cap_words == 0: the table and the stats only.
+ * Inherits brisk_hip_split_packed: pending deferred inserts are completed first; EINVAL on a sharded index, on an entry-id index, on
+ * offsets that do not ascend (and on a read of 2^32 nucleotides or more); the answer does not depend on max_batch_reads,
+ * BRISK_PROFILE_BATCH, BRISK_PROFILE_SEG, BRISK_CORRECT_BATCH or on which kernels run.  correct_reads takes HOST reads (layout of
+ * brisk_hip_get_reads) and returns only the table, out_corrections[corr_cap] HOST, written when it fits: the caller patches its
+ * own strings. */
+int brisk_hip_correct_packed(brisk_hip_index *h, const uint32_t *d_packed, const uint64_t *d_starts, uint64_t n_reads,
+                             uint32_t solid_min, uint32_t min_cover, uint32_t *d_out_packed, uint64_t out_cap_words,
+                             brisk_hip_correction *d_out_corrections /* corr_cap room, may be NULL */, uint64_t corr_cap,
+                             brisk_hip_correct_stats *stats /* HOST */);
+int brisk_hip_correct_reads(brisk_hip_index *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
+                            uint32_t solid_min, uint32_t min_cover, brisk_hip_correction *out_corrections /* HOST */, uint64_t corr_cap,
+                            brisk_hip_correct_stats *stats /* HOST */);
 
 /* point lookups of UNHASHED (kmer_s, minimizer_idx) pairs, as Brisk::get takes them.
  * HOST arrays; out_found[i] in {0,1}; out_data[i] valid when found. */
