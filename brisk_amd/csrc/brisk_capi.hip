@@ -791,7 +791,7 @@ int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
         // instantiations: {k and m compile-time for the common parameter sets (the class tables' layout folds into the
         // instructions), or from P with the chunk count unrolled (6: m 27..29, 4: m 17..19, 3: m 11..15 at CLS_W 5; else a loop)} x mode
 #define LAUNCH_SCAN2(NCH, MODE, KK, MM) \
-    hipLaunchKernelGGL((k_scan2<NCH, MODE, KK, MM>), grid, block, h->scan_lds - scan_fixed_tabs(MM) * 8, h->stream, h->P, h->scfg, d_packed, d_starts, n_items, h->d_tabs, out, cc)
+    hipLaunchKernelGGL((k_scan2<NCH, MODE, KK, MM>), grid, block, h->scan_lds - scan_fixed_tabs(MM) * 8, h->stream, ScanArgs{h->P, h->scfg, d_packed, d_starts, n_items, h->d_tabs, out, cc})
 #define LAUNCH_SCAN2_MODES(NCH, KK, MM)                    \
     {                                                      \
         if (pos && cc.vreads) LAUNCH_SCAN2(NCH, 4, KK, MM);  \

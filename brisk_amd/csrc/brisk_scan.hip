@@ -588,6 +588,19 @@ __device__ __forceinline__ unsigned long long lanes_below(u32 lane) { return (1u
 // CU (4 waves per SIMD, all that fits): 30.3; CLS_W 4 / 5, three blocks (6 waves per SIMD, 80 registers, no scratch):
 // 26.1 / 25.6; four blocks (64 registers, 16 of them spilled): 33.9; one 16-wave block per CU 43.9, 10-wave blocks 49
 // (profiles/r02_scan_attribution.txt).  Occupancy is worth more than a look-up, scratch costs more than occupancy.
+// The wave-uniform branches of k_scan2 that are taken a few times per wave or practically never: the flush of the emit queue, the
+// guard band's exact fold, a re-scan round's 64-bit fallback and its canonical-form test.  Without the hint every branch counts as
+// taken every other time, and the register allocator then keeps what such a branch needs in scalar registers at the price of the
+// step loop's own values, which go to the lanes of a vector register (a v_readlane / v_writelane per use, per step); with it the
+// moves are made where the rare branch is entered and left.  0: no hints (A/B).
+#ifndef SCAN_EXPECT
+#define SCAN_EXPECT 1
+#endif
+#if SCAN_EXPECT
+#define SCAN_RARE(c) __builtin_expect(!!(c), 0)
+#else
+#define SCAN_RARE(c) (c)
+#endif
 #ifndef CLS_W
 #define CLS_W 5
 #endif
@@ -701,7 +714,7 @@ __device__ __forceinline__ u32 decy_class_fast(u64 x, u32 m, const ScanCfg& cfg,
 #endif
     bool guard = false;
     u32 cls = decy_class_guarded<NCH, MM>(x, cfg, tabs, guard);
-    if (__ballot(guard)) {  // wave-uniform and practically never taken: no lane-level branch on the way of the others
+    if (SCAN_RARE(__ballot(guard) != 0)) {  // wave-uniform and practically never taken: no lane-level branch on the way of the others
         if (guard) cls = decy_class(x, m, coef);
     }
     if (took_guard) *took_guard = guard;  // (k_debug_keys counts them)
@@ -1226,6 +1239,72 @@ __device__ unsigned long long g_scan_cnt[8];  // [0] wave-steps [1] expiries [2]
 #define SCNT(i, v)
 #endif
 
+// ---- k_scan2's arguments, and what of them the record builders need --------------------------------------------------------------
+// One struct by value, so that every field has a known offset in the kernel-argument segment.  The step loop runs 88 times per
+// 150-nt read and needs a handful of these; the record builders (emit_queue, scan_final_flush) run four or five times per wave
+// and need nearly all of ScanOut and BriskParams.  Loaded once at the kernel's entry, those ~40 scalars are live across every step,
+// the body has 102 scalar registers, and the allocator parks the excess in the lanes of a vector register: a v_readlane or
+// v_writelane -- a vector instruction at full issue cost in a kernel bound by vector issue -- at every use, the step loop's own
+// scalars among them.  So a flush reads its arguments again, from the kernel-argument segment: scalar loads, which take no vector
+// issue slot, a few times per wave.  The segment's address goes through an empty asm so that these loads are not merged with the
+// entry's (which would give the long live ranges back).
+struct ScanArgs {
+    BriskParams P;
+    ScanCfg cfg;
+    const u32* packed;
+    const u64* starts;
+    u64 n_reads;
+    const double* g_tabs;
+    ScanOut out;
+    ChunkCtl cc;
+};
+struct ScanFlushArgs {
+    BriskParams P;
+    const u32* packed;
+    ScanOut out;
+    const u64* slot_base;  // ChunkCtl::slot_base
+};
+typedef const __attribute__((address_space(4))) u32* kernarg_words;
+template <class T>
+__device__ __forceinline__ T kernarg_field(kernarg_words ka, size_t off) {  // dword by dword: the compiler merges them into wide scalar loads
+    static_assert(sizeof(T) % 4 == 0 && alignof(T) <= 8, "whole dwords");
+    struct Words {
+        u32 w[sizeof(T) / 4];
+    } v;
+#pragma unroll
+    for (u32 i = 0; i < sizeof(T) / 4; i++) v.w[i] = ka[off / 4 + i];
+    return __builtin_bit_cast(T, v);
+}
+#ifndef SCAN_FLUSH_RELOAD
+#define SCAN_FLUSH_RELOAD 1   // 0: the builders take the values loaded at the kernel's entry (A/B)
+#endif
+template <int KK, int MM>
+__device__ __forceinline__ ScanFlushArgs scan_flush_args(const ScanArgs& A) {
+    ScanFlushArgs f;
+#if !SCAN_FLUSH_RELOAD
+    f.P = A.P;
+    f.packed = A.packed;
+    f.out = A.out;
+    f.slot_base = A.cc.slot_base;
+#else
+    kernarg_words ka = (kernarg_words)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    f.P = kernarg_field<BriskParams>(ka, offsetof(ScanArgs, P));
+    f.packed = kernarg_field<const u32*>(ka, offsetof(ScanArgs, packed));
+    f.out = kernarg_field<ScanOut>(ka, offsetof(ScanArgs, out));
+    f.slot_base = kernarg_field<const u64*>(ka, offsetof(ScanArgs, cc) + offsetof(ChunkCtl, slot_base));
+#endif
+    if (KK) {  // as in k_scan2: the builders fold on them
+        f.P.k = KK;
+        f.P.w = KK - MM;
+    }
+    if (MM) {
+        f.P.m = MM;
+        f.P.m_mask = (1ull << (2 * MM)) - 1;
+    }
+    return f;
+}
+
 // MODE 0: reads, insert; 1: reads, query (stops a read at a returned minimizer of 0); 2: virtual reads (chunks of long sequences);
 // 3 / 4: reads / virtual reads in per-position mode (brisk_hip_get_kmers): the insert's records, each with its slot anchor in out.ret
 // KK, MM: k and m as compile-time constants for the common parameter sets (0: from P) -- folds the shifts and masks and,
@@ -1238,8 +1317,14 @@ __device__ unsigned long long g_scan_cnt[8];  // [0] wave-steps [1] expiries [2]
 #endif
 __host__ __device__ constexpr int scan_waves_per_eu(int KK, int MM) { return KK && MM >= 12 ? SCAN_WAVES_PER_EU : 4; }
 template <int NCH, int MODE, int KK, int MM>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_waves_per_eu(KK, MM), 8))) k_scan2(BriskParams P, ScanCfg cfg, const u32* __restrict__ packed, const u64* __restrict__ starts,
-                                                u64 n_reads, const double* __restrict__ g_tabs, ScanOut out, ChunkCtl cc) {
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_waves_per_eu(KK, MM), 8))) k_scan2(ScanArgs A) {
+    BriskParams P = A.P;
+    const ScanCfg& cfg = A.cfg;
+    const u32* __restrict__ packed = A.packed;
+    const u64* __restrict__ starts = A.starts;
+    const u64 n_reads = A.n_reads;
+    const double* __restrict__ g_tabs = A.g_tabs;
+    const ChunkCtl& cc = A.cc;
     constexpr bool VR = MODE == 2 || MODE == 4, query_mode = MODE == 1, POS = MODE >= 3;
     constexpr bool CLS = MM < 12;  // minimizer_idx classes in the routing id exist only where 2m < 24 (brisk_hip_create)
     constexpr bool ANCH = KK == AF_K && MM == AF_M;  // records through the anchored frame (anchored_record)
@@ -1321,8 +1406,19 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
         const u32 y = __shfl_xor(max_nk, o, 64);
         max_nk = y > max_nk ? y : max_nk;
     }
+#ifndef SCAN_UNIFORM_TRIP
+#define SCAN_UNIFORM_TRIP 1   // 0: the trip count as the butterfly leaves it, in a vector register (A/B)
+#endif
+#if SCAN_UNIFORM_TRIP
+    // The same value in every lane, and in a scalar register: the compiler cannot see that a butterfly's result is uniform, takes the
+    // step loop for one that lanes leave at different steps, and keeps, per step, the mask of the lanes that have left and a merged
+    // copy of every lane mask that is live after the loop (`reversed`: two scalar registers more, parked in vector lanes, read and
+    // written in the loop's latch at every step).
+    max_nk = (u32)__builtin_amdgcn_readfirstlane((int)max_nk);
+#endif
     if (max_nk == 0) {  // nothing to scan in this wave; it still takes part in the block's final reservation
-        scan_final_flush<CLS, POS, ANCH>(P, packed, out, q_ent, s_q0, s_tag, 0, s_wcnt, s_wbase, cc.slot_base, hi_word);
+        const ScanFlushArgs fa = scan_flush_args<KK, MM>(A);
+        scan_final_flush<CLS, POS, ANCH>(fa.P, fa.packed, fa.out, q_ent, s_q0, s_tag, 0, s_wcnt, s_wbase, fa.slot_base, hi_word);
         return;
     }
     const u64 KEY0 = order_key_fast<NCH, MM>(0, m, M, cfg, s_tabs, s_coef);
@@ -1569,7 +1665,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
             const unsigned long long rvb = __ballot(rv);
             const bool unique = __popc((u32)tie) == 1 && (!two || __popc((u32)(tie >> 32)) == 1);  // wave-uniform
             u64 hm = key;  // slow path only: minimum of this lane's half on the full keys
-            if (!unique) {
+            if (SCAN_RARE(!unique)) {
                 for (int o = 16; o > 0; o >>= 1) {
                     const u64 y = __shfl_xor(hm, o, 64);
                     hm = y < hm ? y : hm;
@@ -1604,7 +1700,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
                 u32 pos;
                 bool rev, need_canon;
                 resolve_ties(first, last, rf, rl, Km, false, false, &pos, &rev, &need_canon);
-                if (need_canon) {  // wave-uniform
+                if (SCAN_RARE(need_canon)) {  // wave-uniform
                     const u64 lowX = half ? lowB : lowA;
                     const u64 qL = read_lane_u64(q0, L) + p;
                     const u64 hi = k > 32 ? load_nts(packed, qL, k - 32) : 0;
@@ -1629,17 +1725,18 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
         if (closed && (p > 0 || seeded)) p0 = p;
         // turn queued super-k-mers into records with full waves.  All waves append to one record counter, and
         // same-address atomics serialise device-wide (~15 ns each): one reservation per flush, not per record
-        if (qcount + 64 > cfg.qcap) {
+        if (SCAN_RARE(qcount + 64 > cfg.qcap)) {
 #ifndef SCAN_ATTR_NOEMIT
-            const u32 n_out = queue_records<CLS>(P, q_ent, qcount);
+            const ScanFlushArgs fa = scan_flush_args<KK, MM>(A);  // (nothing the records need is held across the steps: see ScanArgs)
+            const u32 n_out = queue_records<CLS>(fa.P, q_ent, qcount);
             unsigned long long base = 0;
-            if (out.bins) {  // binned records take their slots from the partitions' counters: the record counter is a total, nobody waits for it
-                if (lane == 0) atomicAdd(out.n_rec, (unsigned long long)n_out);
+            if (fa.out.bins) {  // binned records take their slots from the partitions' counters: the record counter is a total, nobody waits for it
+                if (lane == 0) atomicAdd(fa.out.n_rec, (unsigned long long)n_out);
             } else {
-                if (lane == 0) base = atomicAdd(out.n_rec, (unsigned long long)n_out);
+                if (lane == 0) base = atomicAdd(fa.out.n_rec, (unsigned long long)n_out);
                 base = read_lane_u64(base, 0);
             }
-            emit_queue<CLS, POS, ANCH>(P, packed, out, q_ent, s_q0, s_tag, qcount, base, cc.slot_base, hi_word);
+            emit_queue<CLS, POS, ANCH>(fa.P, fa.packed, fa.out, q_ent, s_q0, s_tag, qcount, base, fa.slot_base, hi_word);
 #endif
             qcount = 0;
         }
@@ -1665,5 +1762,6 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
 #ifdef SCAN_ATTR_NOEMIT
     qcount = 0;
 #endif
-    scan_final_flush<CLS, POS, ANCH>(P, packed, out, q_ent, s_q0, s_tag, qcount, s_wcnt, s_wbase, cc.slot_base, hi_word);
+    const ScanFlushArgs fa = scan_flush_args<KK, MM>(A);
+    scan_final_flush<CLS, POS, ANCH>(fa.P, fa.packed, fa.out, q_ent, s_q0, s_tag, qcount, s_wcnt, s_wbase, fa.slot_base, hi_word);
 }
