@@ -6,7 +6,7 @@ Python package is a thin ctypes view of the C-ABI used by tests, ``bench.py``
 and ``__graft_entry__``; it never computes anything itself and raises if the
 library is missing (there is no CPU fallback).
 """
-from .hipapi import BriskHip, BriskHipError, build_apps, build_library, library_path, coef_table, kmer_slots, snapshot_info, READ_PROFILE_DTYPE, profile_from_slots, COUNT_MODES  # noqa: F401
+from .hipapi import BriskHip, BriskHipError, build_apps, build_library, library_path, coef_table, kmer_slots, snapshot_info, READ_PROFILE_DTYPE, profile_from_slots, COUNT_MODES, MINIMIZER_MODES  # noqa: F401
 from .hipapi import READ_INTERVAL_DTYPE, SELECT_KINDS, intervals_from_profile, select_rule  # noqa: F401
 from .hipapi import JOINT_ABSENT, joint_figures, joint_spectrum_from_entries  # noqa: F401
 from .hipapi import FRAGMENT_DTYPE, INTAKE_BLOCK, INTAKE_STATS_FIELDS, fragments_from_reads, intake_rule  # noqa: F401

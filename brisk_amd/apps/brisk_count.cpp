@@ -17,6 +17,10 @@
 //                    second index of --merge / --subtract / --intersect FILE, are created in that mode; --load FILE (or a set operation's
 //                    FILE) of a snapshot of the other mode fails with the library's message.  The --histo file then starts with a
 //                    "#" comment line saying so, and its last line is "255+<TAB>entries": the entries seen 255 times or more
+//   --full-minimizers   full-width minimizers (brisk_hip_options.minimizer_mode = BRISK_HIP_MINIMIZER_FULL): the re-scan of a k-mer sees all
+//                    of it at k > 32 too, so that one canonical k-mer is one entry (the reference's truncation splits it among several); the
+//                    index and the second index of a set operation are created in that mode, and a snapshot of the other mode is refused
+//                    with the library's message.  --bulk only: --facade and --mixed stay the reference's
 //   --min-count N / --max-count N   the dump and the KFF file hold only the entries with N <= count (<= N): brisk_hip_enumerate_range
 //   --merge FILE / --subtract FILE / --intersect FILE   each at most once, applied in that order: FILE is counted into a second index with
 //                    the same parameters and combined with the first on the device (brisk_hip_merge / _subtract / _intersect, counts of
@@ -418,6 +422,7 @@ int main(int argc_in, char** argv_in) {
     bool have_solid = false;
     bool have_range = false;
     bool saturate = false;
+    bool full_minimizers = false;
     bool paired = false;
     const char* mate_file = nullptr;
     const char* pair_mode_text = nullptr;
@@ -428,14 +433,15 @@ int main(int argc_in, char** argv_in) {
     const char* filter_joint_file = nullptr;
     const char* window_text = nullptr;
     static const char* const usage =
-        "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] "
+        "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--full-minimizers] [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] "
         "[--subtract FILE] [--intersect FILE] [--filter-joint FILE --window SLO:SHI:OLO:OHI[:absent]] [--joint FILE --joint-histo OUT] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]] [--min-qual Q] [--qual-base 33|64] "
         "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]] [--paired [--mate FILE] [--pair-mode each|all|any]]; FASTA \"-\": no reads; a FILE may be a snapshot; an input that starts with '@' is FASTQ)\n"
         "  --min-qual Q   FASTQ input: a base of quality below Q (0..93) is cut like an N, on the device; --qual-base 33|64 (default 33)\n"
         "  --paired   one record a read, interleaved or zipped with --mate FILE; --extract PREFIX then writes PREFIX.1.fa PREFIX.2.fa PREFIX.s.fa (FASTQ input allowed)\n"
         "  --rule correct [--min-cover C]   with --extract FILE: every read whole, \">read_index n_corrected\", its isolated substitutions repaired; the counters go to stderr\n"
         "  --rule split   with --extract FILE: every run of k-mers with count >= N (--solid) as a record of its own, \">read_index start len\"; the counters go to stderr\n"
-        "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+";
+        "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+\n"
+        "  --full-minimizers   the minimizer re-scan sees the whole k-mer at k > 32 too (minimizer_mode full): one canonical k-mer, one entry; snapshots carry the mode";
     for (int i = 0; i < argc_in; i++) {
         if (i > 0 && (!strcmp(argv_in[i], "--help") || !strcmp(argv_in[i], "-h"))) {
             std::cout << usage << std::endl;
@@ -443,6 +449,10 @@ int main(int argc_in, char** argv_in) {
         }
         if (i > 0 && !strcmp(argv_in[i], "--saturate")) {
             saturate = true;
+            continue;
+        }
+        if (i > 0 && !strcmp(argv_in[i], "--full-minimizers")) {
+            full_minimizers = true;
             continue;
         }
         if (i > 0 && !strcmp(argv_in[i], "--paired")) {
@@ -534,8 +544,8 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || extract_file || rule_text || min_len || have_qual || paired || mate_file || pair_mode_text) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--saturate, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule, --min-len, --min-qual, --qual-base, --paired, --mate and --pair-mode work on the device "
+    if ((histo || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || full_minimizers || extract_file || rule_text || min_len || have_qual || paired || mate_file || pair_mode_text) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--saturate, --full-minimizers, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule, --min-len, --min-qual, --qual-base, --paired, --mate and --pair-mode work on the device "
                      "index: --bulk only" << std::endl;
         return 2;
     }
@@ -740,6 +750,7 @@ int main(int argc_in, char** argv_in) {
             brisk_hip_options o{};
             o.struct_size = sizeof o;
             o.count_mode = saturate ? BRISK_HIP_COUNTS_SATURATE : BRISK_HIP_COUNTS_WRAP;  // (also the second index's of a set operation)
+            o.minimizer_mode = full_minimizers ? BRISK_HIP_MINIMIZER_FULL : BRISK_HIP_MINIMIZER_REFERENCE;
             brisk_hip_index* h = nullptr;
             int rc = brisk_hip_create(&h, k, m, b, 1, params.dede->coef(), &o);
             if (rc != BRISK_HIP_OK) {

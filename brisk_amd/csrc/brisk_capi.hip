@@ -116,6 +116,7 @@ struct brisk_hip_index {
     bool scan_v1 = false;       // BRISK_SCAN_V1=1: the plain restatement kernel
     bool entry_ids = false;
     u32 count_mode = 0;         // brisk_hip_options.count_mode: BRISK_HIP_COUNTS_WRAP, or _SATURATE (the insert kernels' SAT instantiations)
+    u32 minimizer_mode = 0;     // brisk_hip_options.minimizer_mode: BRISK_HIP_MINIMIZER_REFERENCE, or _FULL (the scans' FULL instantiations where k > 32)
     bool use_vmm = false;
     bool scan_hist_valid = false;  // d_hist holds the per-partition histogram of the last brisk_hip_scan_packed
     u64 arena_limit = 0;        // BRISK_ARENA_LIMIT (entries): artificial ceiling, for tests of the out-of-memory path
@@ -777,6 +778,8 @@ int insert_records_once(brisk_hip_index* h, const u64* d_rec, u64 n_rec, bool ha
 int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u64 n_items, const ScanOut& out, bool query_mode, bool plain,
                 const ChunkCtl& cc, bool pos = false) {
     ProfScope ps(h, S_SCAN);
+    // full-width minimizers differ from the reference's only where a k-mer has more than 32 nts: below that both modes run the same kernels
+    const bool full = h->minimizer_mode == BRISK_HIP_MINIMIZER_FULL && h->P.k > 32;
     if (plain && !pos) {  // sequence mode needs the minimizer values: the plain kernel carries them
         BriskParams P = h->P;
         if (out.ret) {  // and whole vectors: see brisk_hip_scan_sequence
@@ -784,24 +787,34 @@ int launch_scan(brisk_hip_index* h, const u32* d_packed, const u64* d_starts, u6
             P.cls_bits = 0;
         }
         hipLaunchKernelGGL(k_scan, dim3(nblocks(n_items, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, h->stream, P, d_packed, d_starts, n_items, h->d_coef,
-                           out, query_mode ? 1 : 0);
+                           out, query_mode ? 1 : 0, full ? 1 : 0);
+        if (h->trace) fprintf(stderr, "[brisk_hip] body: k_scan (plain), %s minimizers\n", full ? "full" : "reference");
     } else {
         const u32 bt = h->scan_waves * 64;
         const dim3 grid(nblocks(n_items, bt)), block(bt);
         // instantiations: {k and m compile-time for the common parameter sets (the class tables' layout folds into the
         // instructions), or from P with the chunk count unrolled (6: m 27..29, 4: m 17..19, 3: m 11..15 at CLS_W 5; else a loop)} x mode
-#define LAUNCH_SCAN2(NCH, MODE, KK, MM) \
-    hipLaunchKernelGGL((k_scan2<NCH, MODE, KK, MM>), grid, block, h->scan_lds - scan_fixed_tabs(MM) * 8, h->stream, ScanArgs{h->P, h->scfg, d_packed, d_starts, n_items, h->d_tabs, out, cc})
-#define LAUNCH_SCAN2_MODES(NCH, KK, MM)                    \
-    {                                                      \
-        if (pos && cc.vreads) LAUNCH_SCAN2(NCH, 4, KK, MM);  \
-        else if (pos) LAUNCH_SCAN2(NCH, 3, KK, MM);        \
-        else if (cc.vreads) LAUNCH_SCAN2(NCH, 2, KK, MM);  \
-        else if (query_mode) LAUNCH_SCAN2(NCH, 1, KK, MM); \
-        else LAUNCH_SCAN2(NCH, 0, KK, MM);                 \
+#define LAUNCH_SCAN2(NCH, MODE, KK, MM, ...)                                                                                                                   \
+    {                                                                                                                                                         \
+        hipLaunchKernelGGL((k_scan2<NCH, MODE, KK, MM, ##__VA_ARGS__>), grid, block, h->scan_lds - scan_fixed_tabs(MM) * 8, h->stream,                        \
+                           ScanArgs{h->P, h->scfg, d_packed, d_starts, n_items, h->d_tabs, out, cc});                                                         \
+        if (h->trace) fprintf(stderr, "[brisk_hip] body: k_scan2<%d,%d,%d,%d>, %s minimizers\n", NCH, MODE, KK, MM, sizeof(#__VA_ARGS__) > 1 ? "full" : "reference"); \
+    }
+#define LAUNCH_SCAN2_MODES(NCH, KK, MM, ...)                              \
+    {                                                                     \
+        if (pos && cc.vreads) LAUNCH_SCAN2(NCH, 4, KK, MM, ##__VA_ARGS__)  \
+        else if (pos) LAUNCH_SCAN2(NCH, 3, KK, MM, ##__VA_ARGS__)         \
+        else if (cc.vreads) LAUNCH_SCAN2(NCH, 2, KK, MM, ##__VA_ARGS__)   \
+        else if (query_mode) LAUNCH_SCAN2(NCH, 1, KK, MM, ##__VA_ARGS__)  \
+        else LAUNCH_SCAN2(NCH, 0, KK, MM, ##__VA_ARGS__)                  \
     }
         const u32 k = h->P.k, m = h->P.m;
-        if (k == 63 && m == 21) LAUNCH_SCAN2_MODES(0, 63, 21)
+        if (full) {  // run-time k and m, the chunk count unrolled as below
+            if (h->scfg.nch == 6) LAUNCH_SCAN2_MODES(6, 0, 0, true)
+            else if (h->scfg.nch == 4) LAUNCH_SCAN2_MODES(4, 0, 0, true)
+            else if (h->scfg.nch == 3) LAUNCH_SCAN2_MODES(3, 0, 0, true)
+            else LAUNCH_SCAN2_MODES(0, 0, 0, true)
+        } else if (k == 63 && m == 21) LAUNCH_SCAN2_MODES(0, 63, 21)
         else if (k == 31 && m == 15) LAUNCH_SCAN2_MODES(0, 31, 15)  // the reference's default parameters (apps/counter.cpp:355)
         else if (k == 31 && m == 11) LAUNCH_SCAN2_MODES(0, 31, 11)
         else if (h->scfg.nch == 6) LAUNCH_SCAN2_MODES(6, 0, 0)
@@ -1852,9 +1865,12 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
     // (a caller that passes the struct as it was before count_mode existed leaves it 0: counts wrap)
     if (o.count_mode != BRISK_HIP_COUNTS_WRAP && o.count_mode != BRISK_HIP_COUNTS_SATURATE) return BRISK_HIP_EINVAL;
     if (o.count_mode == BRISK_HIP_COUNTS_SATURATE && o.entry_ids) return BRISK_HIP_EINVAL;  // that DATA lives with the caller: nothing here counts
+    // (likewise minimizer_mode: without the field, the reference's minimizers)
+    if (o.minimizer_mode != BRISK_HIP_MINIMIZER_REFERENCE && o.minimizer_mode != BRISK_HIP_MINIMIZER_FULL) return BRISK_HIP_EINVAL;
     brisk_hip_index* h = new (std::nothrow) brisk_hip_index();
     if (!h) return BRISK_HIP_ENOMEM;
     h->count_mode = o.count_mode;
+    h->minimizer_mode = o.minimizer_mode;
 
     BriskParams& P = h->P;
     P.k = k; P.m = m; P.b = b;
@@ -1971,7 +1987,8 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
             const size_t lds_max = 160 * 1024;
             // as many 8-wave blocks per CU as the kernel's registers allow (SCAN_WAVES_PER_EU waves per SIMD), the queues
             // shortened if that is what it takes (not below 224 entries); if the tables are too big for that, fewer blocks
-            const bool spec = (k == 63 && m == 21) || (k == 31 && m == 15) || (k == 31 && m == 11);  // launch_scan's instantiations with k and m as constants
+            const bool spec = ((k == 63 && m == 21) || (k == 31 && m == 15) || (k == 31 && m == 11)) &&  // launch_scan's instantiations with k and m as constants
+                              !(h->minimizer_mode == BRISK_HIP_MINIMIZER_FULL && k > 32);                // (full-width minimizers: run-time k and m)
             u32 blocks_per_cu = std::max<u32>(1, (u32)(scan_waves_per_eu(spec ? (int)k : 0, spec ? (int)m : 0) * 4) / 8);
             auto lds_of = [&](u32 q, u32 waves) { return fixed + waves * (size_t)(q + 96) * 8; };  // queue + the lanes' read starts and tags
             while (blocks_per_cu > 1 && blocks_per_cu * lds_of(224, 8) > lds_max - 2048) blocks_per_cu--;
@@ -1993,10 +2010,14 @@ BRISK_API int brisk_hip_create(brisk_hip_index** out, uint8_t k, uint8_t m, uint
 #define SCAN2_FNS(NCH, KK, MM) FnLds{(const void*)k_scan2<NCH, 0, KK, MM>, scan_fixed_tabs(MM) * 8}, FnLds{(const void*)k_scan2<NCH, 1, KK, MM>, scan_fixed_tabs(MM) * 8}, \
                                FnLds{(const void*)k_scan2<NCH, 2, KK, MM>, scan_fixed_tabs(MM) * 8}, FnLds{(const void*)k_scan2<NCH, 3, KK, MM>, scan_fixed_tabs(MM) * 8}, \
                                FnLds{(const void*)k_scan2<NCH, 4, KK, MM>, scan_fixed_tabs(MM) * 8}
+#define SCAN2_FNS_FULL(NCH) FnLds{(const void*)k_scan2<NCH, 0, 0, 0, true>, 0}, FnLds{(const void*)k_scan2<NCH, 1, 0, 0, true>, 0}, FnLds{(const void*)k_scan2<NCH, 2, 0, 0, true>, 0}, \
+                            FnLds{(const void*)k_scan2<NCH, 3, 0, 0, true>, 0}, FnLds{(const void*)k_scan2<NCH, 4, 0, 0, true>, 0}
 #define DEBUG_FN(NCH, MM) FnLds{(const void*)k_debug_keys<NCH, MM>, scan_fixed_tabs(MM) * 8}
                 const FnLds fns[] = {SCAN2_FNS(0, 0, 0), SCAN2_FNS(3, 0, 0), SCAN2_FNS(4, 0, 0), SCAN2_FNS(6, 0, 0), SCAN2_FNS(0, 31, 11), SCAN2_FNS(0, 31, 15), SCAN2_FNS(0, 63, 21),
+                                     SCAN2_FNS_FULL(0), SCAN2_FNS_FULL(3), SCAN2_FNS_FULL(4), SCAN2_FNS_FULL(6),
                                      DEBUG_FN(0, 0), DEBUG_FN(3, 0), DEBUG_FN(4, 0), DEBUG_FN(6, 0), DEBUG_FN(0, 11), DEBUG_FN(0, 15), DEBUG_FN(0, 21)};
 #undef DEBUG_FN
+#undef SCAN2_FNS_FULL
 #undef SCAN2_FNS
                 for (const FnLds& f : fns) HIPCHK(h, hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min(lds_attr, lds_max - f.fixed)));
             }
@@ -2151,6 +2172,12 @@ BRISK_API int brisk_hip_get_layout(const brisk_hip_index* h, brisk_hip_layout* o
     out->n_owners = P.n_owners;
     out->owner_rank = P.owner_rank;
     out->count_mode = h->count_mode;
+    return BRISK_HIP_OK;
+}
+
+BRISK_API int brisk_hip_get_minimizer_mode(const brisk_hip_index* h, uint32_t* out) {
+    if (!h || !out) return BRISK_HIP_EINVAL;
+    *out = h->minimizer_mode;
     return BRISK_HIP_OK;
 }
 
@@ -2506,6 +2533,7 @@ BRISK_API int brisk_hip_reallocate(brisk_hip_index* from, brisk_hip_index* to) {
     if (from->entry_ids || to->entry_ids) return fail(h, BRISK_HIP_EINVAL, "reallocate: entry-id indexes are re-bucketed by the facade (DATA lives on the host)");
     if (to->P.n_owners > 1 || from->P.n_owners > 1) return fail(h, BRISK_HIP_EINVAL, "reallocate on a sharded index");
     if (from->count_mode != to->count_mode) return fail(h, BRISK_HIP_EINVAL, "reallocate: the two indexes differ in count_mode");
+    if (from->minimizer_mode != to->minimizer_mode) return fail(h, BRISK_HIP_EINVAL, "reallocate: the two indexes differ in minimizer_mode");
     HIPCHK(h, hipSetDevice(h->device));
     if (int frc = enter(from)) return fail(h, frc, "reallocate: " + from->err);
     if (int frc = enter(to)) return frc;
@@ -2586,6 +2614,7 @@ int setop_compatible(brisk_hip_index* h, const brisk_hip_index* a, const brisk_h
     else if (a->ix.key_words != b->ix.key_words) field = "key width";
     else if (a->device != b->device) field = "device";
     else if (a->count_mode != b->count_mode) field = "count_mode";
+    else if (a->minimizer_mode != b->minimizer_mode) field = "minimizer_mode";
     if (field) return fail(h, BRISK_HIP_EINVAL, who + "the two indexes differ in " + field);
     return BRISK_HIP_OK;
 }
@@ -2849,11 +2878,14 @@ int snap_parse_header(const unsigned char* hd, u64 file_bytes, brisk_hip_snapsho
     for (int i = 0; i < 3; i++) s->checksum[i] = get64(hd + 80 + 8 * i);
     s->n_blocks = get64(hd + 104);
     s->count_mode = get32(hd + 112);  // (zero in every file written before the field existed: counts wrap)
+    s->minimizer_mode = get32(hd + 116);  // (likewise: the reference's minimizers)
     s->file_bytes = file_bytes;
     if (s->data_bytes != 1 || (s->key_words != 1 && s->key_words != 2) || s->part_bits > 30 || s->k > 63)
         return *why = "snapshot header: inconsistent layout fields", BRISK_HIP_EFORMAT;
     if (s->count_mode != BRISK_HIP_COUNTS_WRAP && s->count_mode != BRISK_HIP_COUNTS_SATURATE)
         return *why = "snapshot header: unknown count_mode " + std::to_string(s->count_mode), BRISK_HIP_EFORMAT;
+    if (s->minimizer_mode != BRISK_HIP_MINIMIZER_REFERENCE && s->minimizer_mode != BRISK_HIP_MINIMIZER_FULL)
+        return *why = "snapshot header: unknown minimizer_mode " + std::to_string(s->minimizer_mode), BRISK_HIP_EFORMAT;
     // the sizes against the file's length: every block has 16 bytes of its own and at most 7 of padding
     const u64 body = file_bytes - kSnapHeader;
     bool ok = s->n_partitions <= (1ull << s->part_bits) && s->n_partitions <= s->n_entries && s->n_blocks <= s->n_partitions && (s->n_entries == 0) == (s->n_blocks == 0) &&
@@ -3044,6 +3076,7 @@ int save_impl(brisk_hip_index* h, int fd, uint64_t* entries_written) {
     for (int i = 0; i < 3; i++) put64(hd + 80 + 8 * i, ck[i]);
     put64(hd + 104, blocks.size());
     put32(hd + 112, h->count_mode);
+    put32(hd + 116, h->minimizer_mode);
     if (!write_all(fd, hd, sizeof hd)) return fail(h, BRISK_HIP_EIO, std::string("save: write: ") + strerror(errno));
     if (!blocks.empty()) {
         SnapPin pin(h->stream);
@@ -3244,6 +3277,7 @@ BRISK_API int brisk_hip_load(brisk_hip_index* h, const char* path, uint32_t flag
         else if (s.key_words != h->ix.key_words) field = "key_words";
         else if (s.shift != P.shift) field = "shift";
         else if (s.count_mode != h->count_mode) field = "count_mode";
+        else if (s.minimizer_mode != h->minimizer_mode) field = "minimizer_mode";
         if (field) rc = fail(h, BRISK_HIP_EINVAL, std::string("load: the file and the index differ in ") + field);
     }
     if (!rc) {

@@ -134,11 +134,13 @@ struct MiniState {
 
 // get_minimizer (Kmers.cpp:367-408) of the K-mer at stream nts [q, q+K): the
 // re-scan runs over the LOW 64 BITS of the k-mer only (line 371, F2).
-__device__ MiniState rescan_minimizer(const u32* __restrict__ packed, u64 q, u32 K, u32 m, u64 M, const double* coef) {
+// full (brisk_hip_options.minimizer_mode == BRISK_HIP_MINIMIZER_FULL): that truncation removed -- the windows come out of the
+// whole K-mer, none is zero-padded; everything else as the reference has it.  The same function where K <= 32.
+__device__ MiniState rescan_minimizer(const u32* __restrict__ packed, u64 q, u32 K, u32 m, u64 M, const double* coef, bool full = false) {
     const u32 nlow = K < 32 ? K : 32;
     const u64 low = load_nts(packed, q + K - nlow, nlow);
-    u64 cur = low;
-    u64 fwd = cur & M;
+    u128x cur{low, full && K > 32 ? load_nts(packed, q, K - 32) : 0ull};
+    u64 fwd = cur.lo & M;
     u64 rc = rc64(fwd, m);
     MiniState s;
     s.mini = fwd < rc ? fwd : rc;
@@ -147,8 +149,8 @@ __device__ MiniState rescan_minimizer(const u32* __restrict__ packed, u64 q, u32
     u64 best = order_key(s.mini, m, M, coef);
     int canon = -1;  // canonized(seq,K), evaluated on first use
     for (u32 i = 1; i <= K - m; i++) {
-        cur >>= 2;
-        fwd = cur & M;
+        cur = shr128(cur, 2);
+        fwd = cur.lo & M;
         rc = rc64(fwd, m);
         const u64 c = fwd < rc ? fwd : rc;
         const u64 h = order_key(c, m, M, coef);
@@ -493,7 +495,7 @@ __device__ __forceinline__ void emit_record_anchored(const BriskParams& P, const
 // query_mode: stop after the first super-k-mer whose returned minimizer is 0,
 // the first one excepted (counter.cpp:296-307)
 __global__ void __launch_bounds__(SCAN_BLOCK) k_scan(BriskParams P, const u32* __restrict__ packed, const u64* __restrict__ starts,
-                                                     u64 n_reads, const double* __restrict__ g_coef, ScanOut out, int query_mode) {
+                                                     u64 n_reads, const double* __restrict__ g_coef, ScanOut out, int query_mode, int full) {
     __shared__ double s_coef[128];
     for (u32 i = threadIdx.x; i < 4 * P.m; i += blockDim.x) s_coef[i] = g_coef[i];
     __syncthreads();
@@ -512,7 +514,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan(BriskParams P, const u32* _
         cf = ((cf << 2) + c) & (M >> 2);
         cr = (cr >> 2) + ((u64)(c ^ 2u) << (2 * m - 2));
     }
-    MiniState st = rescan_minimizer(packed, q0, k - 1, m, M, s_coef);  // Kmers.cpp:533
+    MiniState st = rescan_minimizer(packed, q0, k - 1, m, M, s_coef, full);  // Kmers.cpp:533
     u64 mini_hash = order_key(st.mini, m, M, s_coef);
     u32 mini_pos = st.pos;
     bool reversed = st.rev;
@@ -533,7 +535,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan(BriskParams P, const u32* _
         if (mini_pos > w) {  // the minimizer left the k-mer (Kmers.cpp:551-562)
             closed = true;
             ret = mini;
-            st = rescan_minimizer(packed, q0 + p, k, m, M, s_coef);
+            st = rescan_minimizer(packed, q0 + p, k, m, M, s_coef, full);
             mini = st.mini;
             mini_pos = st.pos;
             reversed = st.rev;
@@ -1316,8 +1318,15 @@ __device__ __forceinline__ ScanFlushArgs scan_flush_args(const ScanArgs& A) {
 #define SCAN_WAVES_PER_EU 6
 #endif
 __host__ __device__ constexpr int scan_waves_per_eu(int KK, int MM) { return KK && MM >= 12 ? SCAN_WAVES_PER_EU : 4; }
-template <int NCH, int MODE, int KK, int MM>
+// FULL (brisk_hip_options.minimizer_mode == BRISK_HIP_MINIMIZER_FULL at k > 32; run-time k and m only): the re-scans see the whole
+// k-mer.  The lane carries the k-mer's nts 32.. beside low64 (hi64), a re-scan round takes ONE k-mer, a window per lane of the whole
+// wave out of the 128-bit value (k - m + 1 <= 61 windows), and nothing is folded in as the all-A m-mer.  get_minimizer is then the
+// true minimum over the k-mer's windows with the reference's tie rules, which is exactly what it is at k <= 32: the window-minimum
+// queue (MinQueue) holds for the reason given there, and serves most expiries.  Where FULL is false every line below that names
+// FULL folds away at compile time.
+template <int NCH, int MODE, int KK, int MM, bool FULL = false>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_waves_per_eu(KK, MM), 8))) k_scan2(ScanArgs A) {
+    static_assert(!FULL || (KK == 0 && MM == 0), "full-width minimizers: run-time k and m only");
     BriskParams P = A.P;
     const ScanCfg& cfg = A.cfg;
     const u32* __restrict__ packed = A.packed;
@@ -1428,6 +1437,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
     u64 cr = 0, low64 = 0;
     if (live) low64 = load_nts(packed, q0 + (k - 1) - nlow1, nlow1);
     cr = rc64(low64 & M, m);
+    u64 hi64 = 0;  // FULL: the nts above low64 (of the (k-1)-mer here, k - 33 of them; of the k-mer in the step loop, whatever lies above its k nts never read)
+    if (FULL && live && k - 1 > 32) hi64 = load_nts(packed, q0, k - 1 - 32);
 
     // ---- minimizer of the (k-1)-mer (Kmers.cpp:533): every lane at once, windows in lockstep
     u64 mini_hash;
@@ -1441,11 +1452,11 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
 #endif
 #define BRISK_PRAGMA_(x) _Pragma(#x)
 #define BRISK_PRAGMA(x) BRISK_PRAGMA_(x)
-    const bool mq_on = SCAN_MINQUEUE && (KK ? (KK <= 32) : (k <= 32));  // wave-uniform: the window minimum from a per-lane queue (MinQueue) instead of re-scans
+    const bool mq_on = SCAN_MINQUEUE && (FULL || (KK ? (KK <= 32) : (k <= 32)));  // wave-uniform: the window minimum from a per-lane queue (MinQueue) instead of re-scans
     MinQueue mq{MQ_EMPTY, MQ_EMPTY, MQ_EMPTY, 0u};
     {
         const u32 Km = k - 1 - m;
-        const u32 nwin = Km + 1 < nlow1 ? Km + 1 : nlow1;  // windows inside the low 64 bits; those that stick out of them are zero-padded (F2)
+        const u32 nwin = FULL || Km + 1 < nlow1 ? Km + 1 : nlow1;  // windows inside the low 64 bits; those that stick out of them are zero-padded (F2)
         // One pass over the windows, every lane its own (k-1)-mer.  Nothing in the pass branches: a class sum inside the guard band
         // (decy_class_guarded) only raises a flag, and the wave then repeats the pass with the exact fold (practically never).  Ascending
         // windows roll: window i + 1 drops window i's last nucleotide and takes the next one of the low 64 bits (or an A) in front.
@@ -1470,7 +1481,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
                 const u32 i = mq_on ? Km - ii : ii;  // (the queue takes the windows oldest first: window i of the (k-1)-mer is the candidate of step -1 - i)
                 u64 fwd, rcv;
                 if (mq_on) {
-                    fwd = (low64 >> (2 * i)) & M;
+                    fwd = (FULL ? shr128(u128x{low64, hi64}, 2 * i).lo : low64 >> (2 * i)) & M;
                     rcv = rc64(fwd, m);
                 } else {
                     fwd = fw;
@@ -1517,7 +1528,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
         u64 best = wm.best;
         u32 first = wm.first, last = wm.last;
         bool rf = wm.flags & 1u, rl = wm.flags & 2u;
-        if (Km >= nwin) {  // windows nlow1..Km of a (k-1)-mer longer than 32: the all-A m-mer (k - 1 > 32 only: never with the queue)
+        if (!FULL && Km >= nwin) {  // windows nlow1..Km of a (k-1)-mer longer than 32: the all-A m-mer (k - 1 > 32 only: never with the queue)
             if (KEY0 < best) {
                 best = KEY0;
                 first = nwin;
@@ -1577,6 +1588,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
         const u32 c = (u32)(buf >> 62);
         buf <<= 2;
         cr = (cr >> 2) + ((u64)(c ^ 2u) << (2 * m - 2));
+        if (FULL) hi64 = (hi64 << 2) | (low64 >> 62);
         low64 = (low64 << 2) | c;
         const u64 cf = low64 & M;
         const bool revf = cr < cf;
@@ -1632,6 +1644,55 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(scan_
         }
         need = 0;
 #endif
+        if constexpr (FULL) {
+            // one k-mer per round: window i = lane i of the wave, out of the 128-bit k-mer (what hi64 holds above the k-mer's own nts lies
+            // above every window: window k - m ends at nt k - 1)
+            while (need) {
+                const int LA = __ffsll((long long)need) - 1;
+                need &= need - 1;
+                SCNT(2, 1)
+                const u128x kmA{read_lane_u64(low64, LA), read_lane_u64(hi64, LA)};
+                const u64 fwd = shr128(kmA, 2 * lane).lo & M;
+                const u64 rcv = rc64(fwd, m);
+                const bool rv = rcv < fwd;
+                u64 key = order_key_fast<NCH, MM>(rv ? rcv : fwd, m, M, cfg, s_tabs, s_coef);
+                u32 k32 = ((u32)(key >> 62) << 30) | (u32)((key & M) >> ksh);  // (as below: an order-preserving 32-bit prefix)
+                if (lane > Km) {
+                    key = ~0ull;
+                    k32 = ~0u;
+                }
+                const u32 rm = row_min_u32(k32);
+                const u32 r0 = (u32)__builtin_amdgcn_readlane((int)rm, 0), r1 = (u32)__builtin_amdgcn_readlane((int)rm, 16);
+                const u32 r2 = (u32)__builtin_amdgcn_readlane((int)rm, 32), r3 = (u32)__builtin_amdgcn_readlane((int)rm, 48);
+                const u32 m01 = r0 < r1 ? r0 : r1, m23 = r2 < r3 ? r2 : r3, mW = m01 < m23 ? m01 : m23;
+                unsigned long long tie = __ballot(k32 == mW);
+                const unsigned long long rvb = __ballot(rv);
+                const bool unique = __popcll(tie) == 1;  // wave-uniform
+                u64 hm = key;  // slow path only: the wave's minimum on the full keys
+                if (SCAN_RARE(!unique)) {
+                    for (int o = 32; o > 0; o >>= 1) {
+                        const u64 y = __shfl_xor(hm, o, 64);
+                        hm = y < hm ? y : hm;
+                    }
+                    tie = __ballot(key == hm);
+                }
+                const u32 first = (u32)__ffsll((long long)tie) - 1, last = 63u - (u32)__clzll((long long)tie);
+                const u64 hmin = unique ? read_lane_u64(key, (int)first) : read_lane_u64(hm, 0);
+                const bool rf = (rvb >> first) & 1, rl = (rvb >> last) & 1;
+                u32 pos;
+                bool rev, need_canon;
+                resolve_ties(first, last, rf, rl, Km, false, false, &pos, &rev, &need_canon);
+                if (SCAN_RARE(need_canon)) {  // wave-uniform
+                    if (!canonized_as_executed(and128(kmA, mask128(2 * k)), k)) rev = false;
+                }
+                if ((int)lane == LA) {
+                    mini_hash = hmin;
+                    mini_pos = pos;
+                    reversed = rev;
+                    mq_reset(mq, hmin, p - pos, rev, pos != 0);  // (as below)
+                }
+            }
+        } else
         while (need) {
             const int LA = __ffsll((long long)need) - 1;
             need &= need - 1;

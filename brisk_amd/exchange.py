@@ -254,15 +254,16 @@ def suggest_part_bits(b: int, reads_per_batch: int, kmers_per_read: int = 0, min
 
 class ShardedCounter:
     """A rank's share of a k-mer counting job: owns the buckets of its partition range.  count_mode ("wrap" / "saturate", the
-    same on every rank) is the owners' handles': exchanged records carry no multiplicity, so the sharded path works in either."""
+    same on every rank) is the owners' handles': exchanged records carry no multiplicity, so the sharded path works in either.
+    minimizer_mode ("reference" / "full", the same on every rank) likewise: every rank scans in its handle's mode."""
 
     def __init__(self, k: int, m: int, b: int, rank: int, world: int, device: int, stream: torch.cuda.Stream,
-                 part_bits: int = 0, group=None, count_mode: str = "wrap"):
+                 part_bits: int = 0, group=None, count_mode: str = "wrap", minimizer_mode: str = "reference"):
         import brisk_amd
         self.rank, self.world, self.group, self.stream = rank, world, group, stream
         self.dev = torch.device("cuda", device)
         self.ix = brisk_amd.BriskHip(k, m, b, device=device, stream=stream.cuda_stream, owner_rank=rank, n_owners=world,
-                                     part_bits=part_bits, count_mode=count_mode)
+                                     part_bits=part_bits, count_mode=count_mode, minimizer_mode=minimizer_mode)
         self.W = self.ix.record_words
         self._rec = self._out = self._inbox = self._hist = self._slices = self._pay = self._stage = None
         self._cap = 0

@@ -84,13 +84,15 @@ def coef_table(m: int) -> np.ndarray:
 
 class _Options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("stream", C.c_void_p), ("part_bits", C.c_uint32),
-                ("owner_rank", C.c_uint32), ("n_owners", C.c_uint32), ("arena_entries", C.c_uint64),
+                ("owner_rank", C.c_uint32), ("n_owners", C.c_uint32), ("minimizer_mode", C.c_uint32), ("arena_entries", C.c_uint64),
                 ("max_batch_reads", C.c_uint64), ("entry_ids", C.c_uint32), ("immediate_inserts", C.c_uint32),
                 ("count_mode", C.c_uint32)]
 
 
 # brisk_hip_options.count_mode: BRISK_HIP_COUNTS_WRAP / BRISK_HIP_COUNTS_SATURATE
 COUNT_MODES = {"wrap": 0, "saturate": 1}
+# brisk_hip_options.minimizer_mode: BRISK_HIP_MINIMIZER_REFERENCE / BRISK_HIP_MINIMIZER_FULL
+MINIMIZER_MODES = {"reference": 0, "full": 1}
 
 
 class _Layout(C.Structure):
@@ -100,7 +102,7 @@ class _Layout(C.Structure):
 
 class _SnapshotInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "version", "header_bytes", "k", "m", "b", "data_bytes", "part_bits", "ext_bits", "cls_bits",
-                                          "cls_width", "key_words", "shift")] + \
+                                          "cls_width", "key_words", "shift", "minimizer_mode")] + \
                [(n, C.c_uint64) for n in ("n_entries", "n_partitions", "nb_skmers")] + [("checksum", C.c_uint64 * 3), ("n_blocks", C.c_uint64), ("file_bytes", C.c_uint64), ("count_mode", C.c_uint32)]
 
 
@@ -118,7 +120,7 @@ _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 # every symbol include/brisk_hip.h declares
 SYMBOLS = [
     "brisk_hip_abi_version", "brisk_hip_create", "brisk_hip_destroy", "brisk_hip_clear", "brisk_hip_last_error", "brisk_hip_sync",
-    "brisk_hip_get_layout", "brisk_hip_insert_reads", "brisk_hip_insert_packed", "brisk_hip_get_reads", "brisk_hip_lookup",
+    "brisk_hip_get_layout", "brisk_hip_get_minimizer_mode", "brisk_hip_insert_reads", "brisk_hip_insert_packed", "brisk_hip_get_reads", "brisk_hip_lookup",
     "brisk_hip_enumerate", "brisk_hip_stats", "brisk_hip_memory_info", "brisk_hip_insert_slack", "brisk_hip_reallocate", "brisk_hip_checksum", "brisk_hip_scan_packed", "brisk_hip_scan_bound", "brisk_hip_route_records",
     "brisk_hip_get_packed", "brisk_hip_get_kmers", "brisk_hip_get_kmers_packed", "brisk_hip_insert_records", "brisk_hip_set_owner_cuts", "brisk_hip_export_hist", "brisk_hip_export_hist_add", "brisk_hip_insert_records_hist", "brisk_hip_scan_query", "brisk_hip_route_tagged", "brisk_hip_query_records", "brisk_hip_pack_ascii", "brisk_hip_synth_reads", "brisk_hip_debug_order_keys", "brisk_hip_debug_guard_count", "brisk_hip_debug_touched", "brisk_hip_debug_directory", "brisk_hip_scan_sequence", "brisk_hip_upsert_kmers", "brisk_hip_find_kmers",
     "brisk_hip_enumerate_ids", "brisk_hip_count_spectrum", "brisk_hip_enumerate_range", "brisk_hip_prune",
@@ -155,6 +157,7 @@ def load() -> C.CDLL:
     L.brisk_hip_last_error.restype = C.c_char_p
     L.brisk_hip_sync.argtypes = [vp]
     L.brisk_hip_get_layout.argtypes = [vp, C.POINTER(_Layout)]
+    L.brisk_hip_get_minimizer_mode.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.brisk_hip_insert_reads.argtypes = [vp, _u8p, _u64p, u64]
     L.brisk_hip_insert_packed.argtypes = [vp, vp, vp, u64]
     L.brisk_hip_get_packed.argtypes = [vp, vp, vp, u64, vp]
@@ -778,7 +781,8 @@ def joint_figures(joint, k: int, solid_min: int = 2) -> dict:
 def snapshot_info(path) -> dict:
     """The header of a snapshot file (brisk_hip_snapshot_info_read; host only: no device, no handle): k, m, b, data_bytes, part_bits,
     ext_bits, cls_bits, cls_width, key_words, shift, n_entries, n_partitions (the non-empty ones), nb_skmers, checksum (the three
-    words of BriskHip.checksum at save time), n_blocks, version, header_bytes, file_bytes and count_mode (0 wrap, 1 saturate: COUNT_MODES)."""
+    words of BriskHip.checksum at save time), n_blocks, version, header_bytes, file_bytes, count_mode (0 wrap, 1 saturate: COUNT_MODES)
+    and minimizer_mode (0 reference, 1 full: MINIMIZER_MODES; 0 in files from before the field existed)."""
     info = _SnapshotInfo(C.sizeof(_SnapshotInfo))
     rc = load().brisk_hip_snapshot_info_read(os.fsencode(path), C.byref(info))
     if rc:
@@ -807,18 +811,28 @@ class BriskHip:
 
     count_mode: "wrap" (the default: the count byte wraps at 256, as the reference's) or "saturate": an entry's count is
     min(255, the times its identity was inserted) -- 255 means "255 or more" and no present entry has count 0.  The mode is fixed
-    at create time (the attribute `count_mode`), travels with snapshots, and two indexes of a set operation must agree in it."""
+    at create time (the attribute `count_mode`), travels with snapshots, and two indexes of a set operation must agree in it.
+
+    minimizer_mode: "reference" (the default: the reference's get_minimizer as executed -- at k > 32 its re-scan reads the last 32
+    nucleotides of the k-mer only, and one canonical k-mer enters the index under several identities, its count split among them)
+    or "full": the re-scan sees the whole k-mer, everything else is the reference's algorithm.  For k <= 32 both build the same
+    index bit for bit.  Fixed at create time (the attribute `minimizer_mode`), it travels with snapshots (`open` creates the handle
+    in the file's mode, `load` refuses the other one), every scan of the handle follows it, and the two indexes of merge, intersect,
+    subtract, compare, joint_spectrum, filter_joint and reallocate must agree in it (EINVAL, the message names minimizer_mode)."""
 
     def __init__(self, k: int, m: int, b: int, device: int = 0, stream: Optional[int] = None, part_bits: int = 0,
                  owner_rank: int = 0, n_owners: int = 1, arena_entries: int = 0, max_batch_reads: int = 0,
-                 entry_ids: bool = False, immediate_inserts: bool = False, count_mode: str = "wrap"):
+                 entry_ids: bool = False, immediate_inserts: bool = False, count_mode: str = "wrap",
+                 minimizer_mode: str = "reference"):
         if count_mode not in COUNT_MODES:
             raise ValueError(f"count_mode must be one of {sorted(COUNT_MODES)}, not {count_mode!r}")
+        if minimizer_mode not in MINIMIZER_MODES:
+            raise ValueError(f"minimizer_mode must be one of {sorted(MINIMIZER_MODES)}, not {minimizer_mode!r}")
         self.L = load()
         self.h = C.c_void_p()
         self.k, self.m, self.b = k, m, b
-        opt = _Options(C.sizeof(_Options), device, stream, part_bits, owner_rank, n_owners, arena_entries, max_batch_reads,
-                       1 if entry_ids else 0, 1 if immediate_inserts else 0, COUNT_MODES[count_mode])
+        opt = _Options(C.sizeof(_Options), device, stream, part_bits, owner_rank, n_owners, MINIMIZER_MODES[minimizer_mode], arena_entries,
+                       max_batch_reads, 1 if entry_ids else 0, 1 if immediate_inserts else 0, COUNT_MODES[count_mode])
         coef = coef_table(m) if 1 <= m <= 31 else np.zeros(4, np.float64)
         rc = self.L.brisk_hip_create(C.byref(self.h), k, m, b, 1, coef.ctypes.data_as(C.POINTER(C.c_double)), C.byref(opt))
         if rc:
@@ -830,6 +844,10 @@ class BriskHip:
         self.layout = {n: getattr(lay, n) for n, _ in _Layout._fields_}
         self.record_words = lay.record_words
         self.count_mode = {v: n for n, v in COUNT_MODES.items()}[lay.count_mode]
+        mode = C.c_uint32()
+        self._chk(self.L.brisk_hip_get_minimizer_mode(self.h, C.byref(mode)))
+        self.layout["minimizer_mode"] = mode.value  # (brisk_hip_get_minimizer_mode: brisk_hip_layout cannot grow)
+        self.minimizer_mode = {v: n for n, v in MINIMIZER_MODES.items()}[mode.value]
 
     def _chk(self, rc: int):
         if rc:
@@ -1124,7 +1142,7 @@ class BriskHip:
     @classmethod
     def open(cls, path, device: int = 0, room: bool = False, **kw) -> "BriskHip":
         """A new handle with the layout of the snapshot at `path`, and the snapshot loaded into it.  The create options come from
-        the header: k, m, b and count_mode as stored and part_bits = 0 if ext_bits > 0 else part_bits -- brisk_hip_create extends the routing id
+        the header: k, m, b, count_mode and minimizer_mode as stored and part_bits = 0 if ext_bits > 0 else part_bits -- brisk_hip_create extends the routing id
         (ext_bits > 0) only when part_bits was left at its default of 0, and without an extension the stored part_bits is what an
         explicit part_bits gives (min(part_bits, 2b), 2^24 partitions at most by default).  cls_bits also depends on the environment
         (BRISK_CLS_BITS): a file saved under another setting is refused by load (EINVAL, the field named) -- and so is one saved under
@@ -1132,6 +1150,7 @@ class BriskHip:
         constructor options (max_batch_reads, immediate_inserts, ...)."""
         info = snapshot_info(path)
         kw.setdefault("count_mode", {v: n for n, v in COUNT_MODES.items()}[info["count_mode"]])
+        kw.setdefault("minimizer_mode", {v: n for n, v in MINIMIZER_MODES.items()}[info["minimizer_mode"]])
         ix = cls(info["k"], info["m"], info["b"], device=device, part_bits=0 if info["ext_bits"] > 0 else info["part_bits"], **kw)
         try:
             ix.load(path, room=room)

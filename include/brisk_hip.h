@@ -162,6 +162,23 @@ typedef struct brisk_hip_options {
                                  * than 2^24).  brisk_amd.exchange.suggest_part_bits states the rule bench.py uses */
     uint32_t owner_rank;        /* this process' rank among n_owners bucket-range owners */
     uint32_t n_owners;          /* 0 or 1: this index owns every bucket; at most 256 (else EUNSUPPORTED) */
+    uint32_t minimizer_mode;    /* BRISK_HIP_MINIMIZER_REFERENCE (0, also what a caller passing the struct without this field gets -- the field
+                                 * lies in what was padding between n_owners and arena_entries, so no other member moved and the
+                                 * struct's size is what it was; count_mode stays the last member):
+                                 * the reference's get_minimizer as executed -- at k > 32 its re-scan reads the low 64 bits of the
+                                 * k-mer only (Kmers.cpp:371), the minimizer it leaves depends on how the read arrived there and on
+                                 * the strand, and one canonical k-mer enters the index under several identities (kmer_s,
+                                 * minimizer_idx), its count split among them.  BRISK_HIP_MINIMIZER_FULL: that one truncation
+                                 * removed -- the re-scan of the k-mer at an expiry and of the (k - 1)-mer at a read's start see all
+                                 * of it, whatever k is; the step rule, the tie rules over all k - m + 1 windows, the canonical-form
+                                 * test as executed, the ignored close at a read's first k-mer and the identity (kmer_s,
+                                 * minimizer_idx) are the reference's.  For k <= 32 both modes are one function and build the same
+                                 * index bit for bit.  Any other value: EINVAL.  The mode is the index's for life, like count_mode:
+                                 * brisk_hip_get_minimizer_mode reports it, snapshots carry it (header offset 116), brisk_hip_load
+                                 * refuses a file of the other mode, every scan of the handle follows it (brisk_hip_scan_sequence and
+                                 * entry-id indexes included; upsert, find and lookup take identities from the caller), and the two
+                                 * handles of a set operation, a joint spectrum or filter, or brisk_hip_reallocate must agree in it
+                                 * (EINVAL, the message names minimizer_mode). */
     uint64_t arena_entries;     /* initial entry capacity of the k-mer arena; 0: grow on demand */
     uint64_t max_batch_reads;   /* reads per internal scan batch; 0: default */
     uint32_t entry_ids;         /* 1: entry-id mode (per-call facade API): every entry gets a stable dense id in
@@ -184,6 +201,7 @@ typedef struct brisk_hip_options {
                                  * operation or of brisk_hip_reallocate must agree in it. */
 } brisk_hip_options;
 enum { BRISK_HIP_COUNTS_WRAP = 0, BRISK_HIP_COUNTS_SATURATE = 1 };
+enum { BRISK_HIP_MINIMIZER_REFERENCE = 0, BRISK_HIP_MINIMIZER_FULL = 1 };
 
 /* ---- lifetime ----------------------------------------------------------- */
 /* coef_table: the 4*m doubles of DecyclingSet(m) computed on the HOST with libm
@@ -218,6 +236,9 @@ typedef struct brisk_hip_layout {
     uint32_t count_mode;        /* brisk_hip_options.count_mode of the handle: BRISK_HIP_COUNTS_WRAP or BRISK_HIP_COUNTS_SATURATE */
 } brisk_hip_layout;
 int brisk_hip_get_layout(const brisk_hip_index *h, brisk_hip_layout *out);
+/* brisk_hip_options.minimizer_mode of the handle: BRISK_HIP_MINIMIZER_REFERENCE or BRISK_HIP_MINIMIZER_FULL.  (A call of its own:
+ * brisk_hip_layout has no struct_size to grow behind and no padding to grow into.)  EINVAL on a null argument. */
+int brisk_hip_get_minimizer_mode(const brisk_hip_index *h, uint32_t *out);
 
 /* ---- bulk count (DATA = uint8_t counter: first touch = 1, then ++ mod 256; with BRISK_HIP_COUNTS_SATURATE: ++ up to 255) -- */
 /* HOST buffers: `bases` = concatenated sequences, `offsets[n_reads+1]`.  Sequences
@@ -809,6 +830,9 @@ typedef struct brisk_hip_snapshot_info {
     uint32_t part_bits, ext_bits, cls_bits, cls_width; /* as brisk_hip_layout */
     uint32_t key_words;         /* u64 words per stored key: 1 or 2 */
     uint32_t shift;             /* 2b + ext_bits - part_bits: routing-id bits kept inside a key */
+    uint32_t minimizer_mode;    /* brisk_hip_options.minimizer_mode of the saved index (header offset 116; 0 in files written before
+                                 * the field existed: the reference's minimizers).  It lies in what was padding before n_entries: no
+                                 * other member moved */
     uint64_t n_entries, n_partitions /* non-empty ones */, nb_skmers;
     uint64_t checksum[3];       /* brisk_hip_checksum at save time */
     uint64_t n_blocks;
@@ -817,7 +841,7 @@ typedef struct brisk_hip_snapshot_info {
                                  * the field existed: counts wrap).  A caller whose struct_size ends before it sees no change */
 } brisk_hip_snapshot_info;
 /* The header of a snapshot file.  Host only: no device and no handle are needed.  EIO: the file cannot be opened or is shorter than
- * a header; EFORMAT: wrong magic, a version other than 1, an unknown count_mode, or sizes that disagree with the file's length (brisk_hip_load
+ * a header; EFORMAT: wrong magic, a version other than 1, an unknown count_mode or minimizer_mode, or sizes that disagree with the file's length (brisk_hip_load
  * answers EIO for a file that is shorter than its header says: it ends early). */
 int brisk_hip_snapshot_info_read(const char *path, brisk_hip_snapshot_info *out);
 /* Writes the index to `path`; *entries_written (may be NULL) receives the entries.  The bytes go to `path` plus a temporary suffix
@@ -827,7 +851,7 @@ int brisk_hip_snapshot_info_read(const char *path, brisk_hip_snapshot_info *out)
  * 2^24 entries; the environment variable BRISK_SNAPSHOT_BLOCK=<entries>, read at each call, sets another limit (a test hook). */
 int brisk_hip_save(brisk_hip_index *h, const char *path, uint64_t *entries_written);
 /* Reads a snapshot into an EMPTY bulk-count index (EINVAL otherwise: "load into an empty index, or load into a second handle and
- * merge") whose k, m, b, data_bytes, part_bits, ext_bits, cls_bits, cls_width, key_words, shift and count_mode are the file's (EINVAL otherwise;
+ * merge") whose k, m, b, data_bytes, part_bits, ext_bits, cls_bits, cls_width, key_words, shift, count_mode and minimizer_mode are the file's (EINVAL otherwise;
  * the message names the first field that differs).  Afterwards the handle is what it would be had it inserted the entries: every
  * call behaves so, enumeration order is the saved index's, nb_skmers is the saved one.  flags: BRISK_HIP_LOAD_COMPACT -- every slice
  * exactly as large as its entries, slices back to back: the file's bytes go straight into the arena, and this is the compaction
