@@ -21,6 +21,12 @@
 //                    of it at k > 32 too, so that one canonical k-mer is one entry (the reference's truncation splits it among several); the
 //                    index and the second index of a set operation are created in that mode, and a snapshot of the other mode is refused
 //                    with the library's message.  --bulk only: --facade and --mixed stay the reference's
+//   --degrees FILE   the degree spectrum of the index as a de Bruijn graph (brisk_hip_degree_spectrum, nodes: count >= --min-count): five lines
+//                    "n0<TAB>..<TAB>n4" -- line `left`, column `right` -- and a line "below<TAB>n" for the entries under the threshold; the figures
+//                    (nodes, edge ends, isolated, dead ends, simple, branching) go to stderr.  At k > 32 give --full-minimizers.
+//   --prune-degrees L:R[,L:R...]   remove the nodes (--min-count <= count <= --max-count) with L neighbours on the left and R on the right
+//                    (brisk_hip_prune_degrees; 0:0 the isolated ones, 0:1,1:0 the tips' ends); one line on stderr says how many went.  Both run where
+//                    --histo runs, --degrees first: after load, the set operations and a count prune
 //   --min-count N / --max-count N   the dump and the KFF file hold only the entries with N <= count (<= N): brisk_hip_enumerate_range
 //   --merge FILE / --subtract FILE / --intersect FILE   each at most once, applied in that order: FILE is counted into a second index with
 //                    the same parameters and combined with the first on the device (brisk_hip_merge / _subtract / _intersect, counts of
@@ -409,6 +415,9 @@ int main(int argc_in, char** argv_in) {
     // named options first: what is left is the positional command line as it always was
     std::vector<char*> args;
     const char* histo = nullptr;
+    const char* degrees_file = nullptr;
+    const char* prune_degrees_text = nullptr;
+    uint32_t degree_mask = 0;
     const char* save_file = nullptr;
     const char* load_file = nullptr;
     const char* profile_file = nullptr;
@@ -433,13 +442,15 @@ int main(int argc_in, char** argv_in) {
     const char* filter_joint_file = nullptr;
     const char* window_text = nullptr;
     static const char* const usage =
-        "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--full-minimizers] [--histo FILE] [--min-count N] [--max-count N] [--merge FILE] "
+        "usage: brisk_count --facade|--bulk|--mixed FASTA k m b [dump.txt [out.kff]]  (--bulk: [--saturate] [--full-minimizers] [--histo FILE] [--degrees FILE] [--prune-degrees L:R[,L:R...]] [--min-count N] [--max-count N] [--merge FILE] "
         "[--subtract FILE] [--intersect FILE] [--filter-joint FILE --window SLO:SHI:OLO:OHI[:absent]] [--joint FILE --joint-histo OUT] [--load SNAPSHOT] [--save SNAPSHOT] [--profile FILE [--solid N]] [--min-qual Q] [--qual-base 33|64] "
         "[--extract FILE --rule trim|median:LO:HI|present:LO:HI [--solid N] [--min-len L]] [--paired [--mate FILE] [--pair-mode each|all|any]]; FASTA \"-\": no reads; a FILE may be a snapshot; an input that starts with '@' is FASTQ)\n"
         "  --min-qual Q   FASTQ input: a base of quality below Q (0..93) is cut like an N, on the device; --qual-base 33|64 (default 33)\n"
         "  --paired   one record a read, interleaved or zipped with --mate FILE; --extract PREFIX then writes PREFIX.1.fa PREFIX.2.fa PREFIX.s.fa (FASTQ input allowed)\n"
         "  --rule correct [--min-cover C]   with --extract FILE: every read whole, \">read_index n_corrected\", its isolated substitutions repaired; the counters go to stderr\n"
         "  --rule split   with --extract FILE: every run of k-mers with count >= N (--solid) as a record of its own, \">read_index start len\"; the counters go to stderr\n"
+        "  --degrees FILE   the index as a de Bruijn graph: the 5 x 5 matrix of (left, right) degrees of the nodes (count >= --min-count) and a line \"below\" as TSV, the figures on stderr; k > 32 wants --full-minimizers\n"
+        "  --prune-degrees L:R[,L:R...]   remove the nodes (--min-count <= count <= --max-count) with L left and R right neighbours, e.g. 0:0 the isolated ones; prints how many went\n"
         "  --saturate   counts stop at 255 (\"255 or more\") instead of wrapping at 256; snapshots carry the mode, and --histo labels its last line 255+\n"
         "  --full-minimizers   the minimizer re-scan sees the whole k-mer at k > 32 too (minimizer_mode full): one canonical k-mer, one entry; snapshots carry the mode";
     for (int i = 0; i < argc_in; i++) {
@@ -462,7 +473,7 @@ int main(int argc_in, char** argv_in) {
         int setop = -1;
         for (int q = 0; q < 3; q++)
             if (i > 0 && !strcmp(argv_in[i], setop_names[q])) setop = q;
-        const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count") ||
+        const bool named = i > 0 && (setop >= 0 || !strcmp(argv_in[i], "--histo") || !strcmp(argv_in[i], "--degrees") || !strcmp(argv_in[i], "--prune-degrees") || !strcmp(argv_in[i], "--save") || !strcmp(argv_in[i], "--load") || !strcmp(argv_in[i], "--min-count") || !strcmp(argv_in[i], "--max-count") ||
                                     !strcmp(argv_in[i], "--profile") || !strcmp(argv_in[i], "--solid") || !strcmp(argv_in[i], "--extract") || !strcmp(argv_in[i], "--rule") ||
                                     !strcmp(argv_in[i], "--min-len") || !strcmp(argv_in[i], "--min-cover") || !strcmp(argv_in[i], "--joint") || !strcmp(argv_in[i], "--joint-histo") || !strcmp(argv_in[i], "--filter-joint") ||
                                     !strcmp(argv_in[i], "--window") || !strcmp(argv_in[i], "--min-qual") || !strcmp(argv_in[i], "--qual-base") || !strcmp(argv_in[i], "--mate") ||
@@ -477,6 +488,19 @@ int main(int argc_in, char** argv_in) {
         }
         const char* opt = argv_in[i++];
         if (!strcmp(opt, "--histo")) histo = argv_in[i];
+        else if (!strcmp(opt, "--degrees")) degrees_file = argv_in[i];
+        else if (!strcmp(opt, "--prune-degrees")) {
+            prune_degrees_text = argv_in[i];
+            for (const char* q = prune_degrees_text;;) {  // L:R[,L:R...], a degree is 0..4
+                if (q[0] < '0' || q[0] > '4' || q[1] != ':' || q[2] < '0' || q[2] > '4' || (q[3] && q[3] != ',')) {
+                    std::cerr << "--prune-degrees: L:R[,L:R...] with L and R in 0..4, got " << prune_degrees_text << std::endl;
+                    return 2;
+                }
+                degree_mask |= 1u << (5 * (q[0] - '0') + (q[2] - '0'));
+                if (!q[3]) break;
+                q += 4;
+            }
+        }
         else if (!strcmp(opt, "--save")) save_file = argv_in[i];
         else if (!strcmp(opt, "--load")) load_file = argv_in[i];
         else if (!strcmp(opt, "--profile")) profile_file = argv_in[i];
@@ -544,8 +568,8 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     const bool have_setop = setop_file[0] || setop_file[1] || setop_file[2];
-    if ((histo || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || full_minimizers || extract_file || rule_text || min_len || have_qual || paired || mate_file || pair_mode_text) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
-        std::cerr << "--saturate, --full-minimizers, --histo, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule, --min-len, --min-qual, --qual-base, --paired, --mate and --pair-mode work on the device "
+    if ((histo || degrees_file || prune_degrees_text || have_range || have_setop || joint_file || joint_histo || filter_joint_file || window_text || save_file || load_file || profile_file || have_solid || saturate || full_minimizers || extract_file || rule_text || min_len || have_qual || paired || mate_file || pair_mode_text) && (argc < 2 || strcmp(argv[1], "--bulk"))) {
+        std::cerr << "--saturate, --full-minimizers, --histo, --degrees, --prune-degrees, --min-count, --max-count, --merge, --subtract, --intersect, --filter-joint, --window, --joint, --joint-histo, --save, --load, --profile, --solid, --extract, --rule, --min-len, --min-qual, --qual-base, --paired, --mate and --pair-mode work on the device "
                      "index: --bulk only" << std::endl;
         return 2;
     }
@@ -1072,6 +1096,42 @@ int main(int argc_in, char** argv_in) {
                 if (saturate) out << "# counts saturate (--saturate): the last line, 255+, is the entries seen 255 times or more\n";
                 for (int c = 0; c < 255; c++) out << c << "\t" << spectrum[c] << "\n";
                 out << (saturate ? "255+" : "255") << "\t" << spectrum[255] << "\n";
+            }
+            if (degrees_file) {
+                uint64_t sp[26];
+                if (brisk_hip_degree_spectrum(h, (uint32_t)min_count, sp) != BRISK_HIP_OK) {
+                    std::cerr << "--degrees: " << brisk_hip_last_error(h) << std::endl;
+                    return 1;
+                }
+                std::ofstream out(degrees_file);
+                uint64_t nodes = 0, ends = 0, dead = 0, branching = 0;
+                for (int l = 0; l < 5; l++) {
+                    for (int r = 0; r < 5; r++) {
+                        const uint64_t v = sp[5 * l + r];
+                        out << v << (r < 4 ? "\t" : "\n");
+                        nodes += v;
+                        ends += v * (uint64_t)(l + r);
+                        if ((l == 0) != (r == 0)) dead += v;
+                        if (l > 1 || r > 1) branching += v;
+                    }
+                }
+                out << "below\t" << sp[25] << "\n";
+                out.close();
+                if (!out) {
+                    std::cerr << "--degrees " << degrees_file << ": write failed" << std::endl;
+                    return 1;
+                }
+                std::cerr << "degrees " << degrees_file << ": " << nodes << " nodes, " << ends << " edge ends, " << sp[0] << " isolated, " << dead << " dead ends, " << sp[6] << " simple, "
+                          << branching << " branching, " << sp[25] << " below --min-count" << std::endl;
+            }
+            if (prune_degrees_text) {
+                uint64_t gone = 0;
+                if (brisk_hip_prune_degrees(h, (uint32_t)min_count, (uint32_t)max_count, degree_mask, &gone) != BRISK_HIP_OK) {
+                    std::cerr << "--prune-degrees: " << brisk_hip_last_error(h) << std::endl;
+                    return 1;
+                }
+                std::cerr << "prune-degrees " << prune_degrees_text << ": " << gone << " entries removed" << std::endl;
+                brisk_hip_stats(h, &nb_buckets, &nb_skmers, &nb_kmers, &mem, &largest);
             }
             uint64_t cursor = 0, n = 0;
             const uint64_t cap = 1u << 20;

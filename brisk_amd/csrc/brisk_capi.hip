@@ -3,9 +3,10 @@
 // is in brisk_kernels.hip.  There is deliberately NO CPU fallback: without a
 // gfx950 device brisk_hip_create fails with BRISK_HIP_ENODEVICE.
 //
-// One translation unit with brisk_kernels.hip, two host parts:
+// One translation unit with brisk_kernels.hip, two host parts and the graph:
 //   brisk_capi.hip        the handle and its memory, scan / insert / query / upload, get_kmers, set operations, snapshots, the sharded round trips, the per-call API
 //   brisk_host_reads.hip  read cleaning (included where its calls stand among the others): per-read profiles, select / extract / trim, raw read intake, paired-end reads
+//   brisk_graph.hip       de Bruijn adjacency (included behind the last call, kernels and host part together): adjacency, degree spectrum, prune by degree
 #include "brisk_kernels.hip"
 
 #include <algorithm>
@@ -154,6 +155,9 @@ struct brisk_hip_index {
     DevBuf split_off, split_tab;         // brisk_hip_solid_runs / _split_*: a batch's slot offsets (the read table of the run passes); a call's fragment table as it accumulates
     DevBuf corr_sites, corr_rows, corr_cand, corr_slots, corr_tmp, corr_tab;  // brisk_hip_weak_sites / _correct_*: a batch's sites; a round's candidate rows; its stream and starts; its slots; flags,
                                                                    // counters, block sums and decisions; a call's correction table as it accumulates
+    DevBuf graph_base, graph_reads, graph_slots, graph_cnt, graph_radj, graph_adj, graph_hist;  // brisk_hip_adjacency / _degree_spectrum / _prune_degrees: the partitions' first rows; a round's read table and
+                                                                   // stream; its slots; its entries' own counts; its bytes; a call's whole byte array; the 26 bins
+    double graph_ms[3] = {0, 0, 0};      // the last graph call's device time: neighbour reads, lookups, fold (while profiling; brisk_hip_graph_phase_ms)
     u64 intake_piece = 1ull << 28;       // BRISK_INTAKE_PIECE (bytes of bases): the piece size of the host intake calls
     u32* d_ovf_cnt = nullptr;              // OVF_REGIONS counters of the binned scan's overflow area
     std::vector<u64> owner_cut;            // sharded index: owner o holds partitions [owner_cut[o], owner_cut[o + 1]) (n_owners + 1 entries)
@@ -1801,7 +1805,7 @@ void free_all(brisk_hip_index* h) {
     hipStreamSynchronize(h->stream);  // nothing of ours may be in flight when the arena is unmapped
     auto fr = [](void* p) { if (p) hipFree(p); };
     for (DevBuf* b : {&h->huge, &h->left, &h->pend, &h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp, &h->enum_out,
-                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed, &h->pair_tab, &h->pair_iv, &h->pair_raw, &h->pair_fs, &h->split_off, &h->split_tab, &h->corr_sites, &h->corr_rows, &h->corr_cand, &h->corr_slots, &h->corr_tmp, &h->corr_tab})
+                      &h->lookup_buf, &h->packed_tmp2, &h->starts_tmp2, &h->anchors, &h->slot_buf, &h->kout_tmp, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed, &h->pair_tab, &h->pair_iv, &h->pair_raw, &h->pair_fs, &h->split_off, &h->split_tab, &h->corr_sites, &h->corr_rows, &h->corr_cand, &h->corr_slots, &h->corr_tmp, &h->corr_tab, &h->graph_base, &h->graph_reads, &h->graph_slots, &h->graph_cnt, &h->graph_radj, &h->graph_adj, &h->graph_hist})
         fr(b->p);
     fr(h->d_coef);
     fr(h->d_tabs);
@@ -2507,7 +2511,7 @@ BRISK_API int brisk_hip_stats(brisk_hip_index* h, uint64_t* nb_buckets, uint64_t
     if (memory_bytes) {
         u64 m = h->arena_cap * (8ull * h->ix.key_words + 1) + h->n_parts * 16 + (h->n_buckets + 7) / 8 + (h->n_parts + 1) * 20;
         for (const DevBuf* b : {&h->bins, &h->staging, &h->parted, &h->desc, &h->chunk_buf, &h->route_buf, &h->tags_a, &h->tags_b, &h->packed_tmp, &h->bases_tmp, &h->starts_tmp, &h->sums_tmp,
-                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed, &h->pair_tab, &h->pair_iv, &h->pair_raw, &h->pair_fs, &h->split_off, &h->split_tab, &h->corr_sites, &h->corr_rows, &h->corr_cand, &h->corr_slots, &h->corr_tmp, &h->corr_tab})
+                                &h->enum_out, &h->lookup_buf, &h->pend, &h->huge, &h->left, &h->seq_buf, &h->packed_tmp2, &h->starts_tmp2, &h->prof_out, &h->prof_plan, &h->reck_buf, &h->ext_iv, &h->ext_tmp, &h->ext_src, &h->ink_mask, &h->ink_tmp, &h->ink_tab, &h->ink_raw, &h->ink_offs, &h->ink_packed, &h->pair_tab, &h->pair_iv, &h->pair_raw, &h->pair_fs, &h->split_off, &h->split_tab, &h->corr_sites, &h->corr_rows, &h->corr_cand, &h->corr_slots, &h->corr_tmp, &h->corr_tab, &h->graph_base, &h->graph_reads, &h->graph_slots, &h->graph_cnt, &h->graph_radj, &h->graph_adj, &h->graph_hist})
             m += b->bytes;
         *memory_bytes = m;
     }
@@ -4012,3 +4016,5 @@ BRISK_API int brisk_hip_profile_read(brisk_hip_index* h, uint32_t* n_slots, cons
 }
 
 }  // extern "C"
+
+#include "brisk_graph.hip"  // its kernels, its helpers, then its own extern "C" block

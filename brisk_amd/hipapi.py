@@ -133,6 +133,7 @@ SYMBOLS = [
     "brisk_hip_solid_runs", "brisk_hip_extract_fragments_packed", "brisk_hip_split_packed", "brisk_hip_split_reads",
     "brisk_hip_weak_sites", "brisk_hip_candidate_windows", "brisk_hip_decide_sites", "brisk_hip_apply_corrections", "brisk_hip_correct_packed", "brisk_hip_correct_reads",
     "brisk_hip_merge", "brisk_hip_intersect", "brisk_hip_subtract", "brisk_hip_compare", "brisk_hip_joint_spectrum", "brisk_hip_filter_joint", "brisk_hip_snapshot_info_read", "brisk_hip_save", "brisk_hip_load",
+    "brisk_hip_adjacency", "brisk_hip_degree_spectrum", "brisk_hip_prune_degrees", "brisk_hip_graph_phase_ms",
     "brisk_hip_profile_enable",
     "brisk_hip_profile_read", "brisk_hip_profile_reset",
 ]
@@ -233,6 +234,10 @@ def load() -> C.CDLL:
     L.brisk_hip_count_spectrum.argtypes = [vp, _u64p]
     L.brisk_hip_enumerate_range.argtypes = [vp, C.POINTER(u64), _u64p, _u64p, _u8p, _u8p, u64, C.POINTER(u64), u32, u32]
     L.brisk_hip_prune.argtypes = [vp, u32, u32, C.POINTER(u64)]
+    L.brisk_hip_adjacency.argtypes = [vp, u32, vp, u64, C.POINTER(u64)]
+    L.brisk_hip_degree_spectrum.argtypes = [vp, u32, _u64p]
+    L.brisk_hip_prune_degrees.argtypes = [vp, u32, u32, u32, C.POINTER(u64)]
+    L.brisk_hip_graph_phase_ms.argtypes = [vp, np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")]
     L.brisk_hip_merge.argtypes = [vp, vp, C.POINTER(u64)]
     L.brisk_hip_intersect.argtypes = [vp, vp, u32, C.POINTER(u64)]
     L.brisk_hip_subtract.argtypes = [vp, vp, C.POINTER(u64)]
@@ -778,6 +783,88 @@ def joint_figures(joint, k: int, solid_min: int = 2) -> dict:
                 error_rate=error_rate, qv=qv)
 
 
+# ---- de Bruijn adjacency (brisk_hip_adjacency / _degree_spectrum / _prune_degrees): the definition on the host
+DEGREE_CLASSES = 26  # 5 * left + right for left, right in 0..4, and 25: "below min_count, not a node"
+
+
+def degree_class(left: int, right: int) -> int:
+    """The class of a node with `left` neighbours on its left and `right` on its right (0..4 each): the index into
+    BriskHip.degree_spectrum and the bit of a prune_degrees mask."""
+    if not (0 <= left <= 4 and 0 <= right <= 4):
+        raise ValueError(f"a side has 0..4 neighbours, not ({left}, {right})")
+    return 5 * left + right
+
+
+def neighbour_strings(lo, hi, k: int) -> list:
+    """The 8 * n neighbour strings of n entries as BriskHip.enumerate returns them (lo, hi: kmer_s, leftmost nucleotide in the
+    highest bits, codes of "ACTG"): for entry i with string x, rows 8 i .. 8 i + 3 are R_c = x[1:] + c and rows 8 i + 4 .. 8 i + 7 are
+    L_c = c + x[:-1], c = "ACTG"[0..3].  A list of bytes objects, what get_kmers takes.  No device needed."""
+    lo, hi = np.asarray(lo, np.uint64), np.asarray(hi, np.uint64)
+    n = len(lo)
+    codes = np.zeros((n, k), np.uint8)
+    for j in range(k):  # nucleotide j from the left: bits [2 (k - 1 - j), 2 (k - j)) of hi:lo
+        sh = 2 * (k - 1 - j)
+        codes[:, j] = ((lo >> np.uint64(sh)) if sh < 64 else (hi >> np.uint64(sh - 64))) & np.uint64(3)
+    out = np.zeros((n, 8, k), np.uint8)
+    for c in range(4):
+        out[:, c, : k - 1] = codes[:, 1:]
+        out[:, c, k - 1] = c
+        out[:, 4 + c, 1:] = codes[:, : k - 1]
+        out[:, 4 + c, 0] = c
+    flat = np.frombuffer(b"ACTG", np.uint8)[out].tobytes()
+    return [flat[i * k:(i + 1) * k] for i in range(8 * n)]
+
+
+def adjacency_from_slots(counts, found, min_count: int = 0) -> np.ndarray:
+    """The adjacency bytes from the slots of the neighbour strings (counts uint8[8 n], found bool[8 n], as BriskHip.get_kmers
+    returns them for neighbour_strings(...)): bit j of byte i is set when slot 8 i + j is found and its count is >= min_count.
+    adjacency_from_slots(*h.get_kmers(neighbour_strings(lo, hi, k))[:2], min_count) is by definition h.adjacency(min_count)."""
+    counts, found = np.asarray(counts, np.uint8), np.asarray(found, bool)
+    if len(counts) != len(found) or len(counts) % 8:
+        raise ValueError("eight slots an entry")
+    ok = (found & (counts.astype(np.int64) >= int(min_count))).reshape(-1, 8).astype(np.uint8)
+    return (ok << np.arange(8, dtype=np.uint8)).sum(axis=1).astype(np.uint8)
+
+
+_POP4 = np.array([bin(i).count("1") for i in range(16)], np.int64)
+
+
+def degree_spectrum_from_adjacency(adj, counts, min_count: int = 0) -> np.ndarray:
+    """BriskHip.degree_spectrum on the host, from the adjacency bytes and the entries' own counts (row for row, as enumerate
+    returns them): uint64[26].  A node is an entry whose count is >= min_count; out[5 * left + right] counts the nodes with `left`
+    set bits among bits 4..7 and `right` among bits 0..3; out[25] the entries that are no nodes.  The values sum to len(adj)."""
+    adj, counts = np.asarray(adj, np.uint8), np.asarray(counts, np.uint8)
+    if len(adj) != len(counts):
+        raise ValueError("one byte and one count an entry")
+    node = counts.astype(np.int64) >= int(min_count)
+    cls = np.where(node, 5 * _POP4[adj >> 4] + _POP4[adj & 15], DEGREE_CLASSES - 1)
+    return np.bincount(cls, minlength=DEGREE_CLASSES).astype(np.uint64)
+
+
+def graph_figures(spectrum) -> dict:
+    """The usual figures off a degree spectrum -- host arithmetic only.  nodes; edge_ends (the sum of all degrees: every edge between
+    two nodes is seen from both of its ends); isolated (0, 0); dead_ends (exactly one side empty); simple (1, 1); branching (a side
+    above 1); below (entries under min_count, not nodes).  Symmetric in left and right."""
+    s = np.asarray(spectrum)
+    if s.shape != (DEGREE_CLASSES,):
+        raise ValueError(f"a degree spectrum has {DEGREE_CLASSES} values, not {s.shape}")
+    m = s[:25].astype(np.int64).reshape(5, 5)
+    left, right = np.arange(5)[:, None], np.arange(5)[None, :]
+    return dict(nodes=int(m.sum()), edge_ends=int((m * (left + right)).sum()), isolated=int(m[0, 0]),
+                dead_ends=int(m[(left == 0) != (right == 0)].sum()), simple=int(m[1, 1]),
+                branching=int(m[(left > 1) | (right > 1)].sum()), below=int(s[25]))
+
+
+def degree_mask(classes) -> int:
+    """a prune_degrees mask from a mask or an iterable of (left, right) pairs"""
+    if isinstance(classes, (int, np.integer)):
+        return int(classes)
+    mask = 0
+    for left, right in classes:
+        mask |= 1 << degree_class(left, right)
+    return mask
+
+
 def snapshot_info(path) -> dict:
     """The header of a snapshot file (brisk_hip_snapshot_info_read; host only: no device, no handle): k, m, b, data_bytes, part_bits,
     ext_bits, cls_bits, cls_width, key_words, shift, n_entries, n_partitions (the non-empty ones), nb_skmers, checksum (the three
@@ -831,6 +918,7 @@ class BriskHip:
         self.L = load()
         self.h = C.c_void_p()
         self.k, self.m, self.b = k, m, b
+        self.device = device
         opt = _Options(C.sizeof(_Options), device, stream, part_bits, owner_rank, n_owners, MINIMIZER_MODES[minimizer_mode], arena_entries,
                        max_batch_reads, 1 if entry_ids else 0, 1 if immediate_inserts else 0, COUNT_MODES[count_mode])
         coef = coef_table(m) if 1 <= m <= 31 else np.zeros(4, np.float64)
@@ -1065,6 +1153,46 @@ class BriskHip:
         v = C.c_uint64()
         self._chk(self.L.brisk_hip_prune(self.h, min_count, max_count, C.byref(v)))
         return v.value
+
+    # ---- de Bruijn adjacency: at k > 32 the graph wants a minimizer_mode="full" index
+    def adjacency_device(self, d_adj: int, cap: int, min_count: int = 0) -> int:
+        """One adjacency byte per entry into the caller's device buffer of `cap` bytes (brisk_hip_adjacency), in enumerate()'s order;
+        returns the number of entries.  Bit c: x[1:] + "ACTG"[c] is present with count >= min_count; bit 4 + c: "ACTG"[c] + x[:-1] is.
+        BriskHipError(ECAPACITY), with nothing written, when cap is too small."""
+        n = C.c_uint64()
+        self._chk(self.L.brisk_hip_adjacency(self.h, min_count, d_adj or None, cap, C.byref(n)))
+        return n.value
+
+    def adjacency(self, min_count: int = 0) -> np.ndarray:
+        """uint8[n_entries], aligned with enumerate(): row i's neighbours (adjacency_device through a device buffer of its own)."""
+        import torch  # the device buffer only; the bytes are the library's
+
+        n = self.stats()["nb_kmers"]
+        buf = torch.zeros(max(n, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        torch.cuda.synchronize(self.device)
+        got = self.adjacency_device(buf.data_ptr(), n, min_count)
+        return buf[:got].cpu().numpy()
+
+    def degree_spectrum(self, min_count: int = 0) -> np.ndarray:
+        """uint64[26]: out[degree_class(left, right)] = the nodes (entries with count >= min_count) with that many neighbours on each
+        side, out[25] = the entries below min_count.  Sums to nb_kmers.  graph_figures reads it."""
+        out = np.zeros(DEGREE_CLASSES, np.uint64)
+        self._chk(self.L.brisk_hip_degree_spectrum(self.h, min_count, out))
+        return out
+
+    def prune_degrees(self, classes, min_count: int = 0, max_count: int = 255) -> int:
+        """remove, in place, every node (count >= min_count) of count <= max_count whose degree class is in `classes` -- a mask of
+        1 << degree_class(left, right) bits or an iterable of (left, right) pairs; returns how many were removed.  The graph is taken
+        once, before anything is removed.  Everything prune() promises holds afterwards."""
+        v = C.c_uint64()
+        self._chk(self.L.brisk_hip_prune_degrees(self.h, min_count, max_count, degree_mask(classes), C.byref(v)))
+        return v.value
+
+    def graph_phase_ms(self) -> dict:
+        """device ms of the last graph call's phases while profile_enable() is on: neighbour_reads, lookups, fold"""
+        out = np.zeros(3, np.float64)
+        self._chk(self.L.brisk_hip_graph_phase_ms(self.h, out))
+        return dict(neighbour_reads=float(out[0]), lookups=float(out[1]), fold=float(out[2]))
 
     # ---- set operations (brisk_hip_merge / intersect / subtract / compare): `other` has the same geometry and is left as it is
     COUNT_RULES = {"left": 0, "min": 1, "max": 2, "sum": 3}

@@ -81,6 +81,10 @@
  *                               no reference counterpart (Brisk::stats and Brisk::next are all it has): the abundance
  *                               spectrum, the entries of a count range, and the index without the entries outside one,
  *                               each one pass over the arena on the device
+ *   brisk_hip_adjacency / brisk_hip_degree_spectrum / brisk_hip_prune_degrees
+ *                               no reference counterpart (it answers for nodes only; assemblers and cuttlefish build this graph):
+ *                               the index as the node set of a de Bruijn graph -- which of its eight possible neighbours every
+ *                               entry has, the histogram of (left, right) degrees, and the index without the nodes of given degrees
  *   brisk_hip_merge / brisk_hip_intersect / brisk_hip_subtract / brisk_hip_compare
  *                               no reference counterpart (the reference holds one index; kmc_tools and jellyfish merge are
  *                               the usual tools): two indexes of one geometry combined on the device, partition by partition
@@ -751,6 +755,41 @@ int brisk_hip_enumerate_range(brisk_hip_index *h, uint64_t *cursor, uint64_t *ou
  * no device memory is returned and memory_bytes / brisk_hip_memory_info do not shrink (brisk_hip_clear, or a new index, do
  * that).  EINVAL if min_count > max_count. */
 int brisk_hip_prune(brisk_hip_index *h, uint32_t min_count, uint32_t max_count, uint64_t *removed);
+
+/* ---- de Bruijn adjacency: neighbours, degree spectrum, prune by degree (no reference counterpart) ---- */
+/* Entry e has the nucleotide string x: the k nucleotides of kmer_s as brisk_hip_enumerate unhashes it, leftmost nucleotide in the
+ * highest bits, codes of "ACTG" (0..3).  Its eight neighbour strings, in this order: R_c = x[1:] + c for c = 0..3, then
+ * L_c = c + x[:-1] for c = 0..3.  The adjacency byte of e has bit c set when R_c is a neighbour and bit 4 + c when L_c is.  A string
+ * is a neighbour when, looked up as a read of exactly k nucleotides -- one brisk_hip_get_kmers slot, under the identity the scan
+ * gives that read on its own -- it is present and its stored count byte is >= min_count.  min_count 0 is plain presence (in a
+ * wrapping index a present entry with count 0 passes).  Self-loops (homopolymers), palindromes and an entry that is its own
+ * reverse complement's neighbour need no rule of their own: the string lookup decides.  "Left" and "right" are relative to the
+ * stored orientation of x, which the minimizer's strand chooses, so degree classes are (left, right) pairs and every derived
+ * figure is symmetric in them.
+ * One canonical k-mer is one entry at k <= 32, and at k > 32 in a full-mode index (brisk_hip_options.minimizer_mode): THE GRAPH
+ * WANTS A FULL-MODE INDEX AT k > 32.  In reference mode there a k-mer looked up on its own is not always found (its identity
+ * depends on the read around it); the calls are allowed and mean what the lookup means.
+ * All three complete pending deferred inserts first, are valid in either count_mode and either minimizer_mode, answer
+ * independently of batching, and return EINVAL on an entry-id index and on a sharded handle (n_owners > 1: an entry's neighbours
+ * live with other owners; the sharded route is a follow-up). */
+/* d_adj (DEVICE, cap bytes): one byte per entry in brisk_hip_enumerate's order -- ascending partition, storage order inside one --
+ * so row i of a full enumeration and d_adj[i] are the same entry.  *n_entries receives nb_kmers.  ECAPACITY, with nothing
+ * written, when cap < nb_kmers. */
+int brisk_hip_adjacency(brisk_hip_index *h, uint32_t min_count, uint8_t *d_adj, uint64_t cap, uint64_t *n_entries);
+/* out (HOST): the nodes are the entries whose own count is >= min_count; out[5 * left + right] counts the nodes with `left` set
+ * bits among bits 4..7 of their byte and `right` among bits 0..3; out[25] counts the entries below min_count (not nodes).
+ * The 26 values always sum to nb_kmers of brisk_hip_stats. */
+int brisk_hip_degree_spectrum(brisk_hip_index *h, uint32_t min_count, uint64_t out[26]);
+/* Removes, in place, every node (count >= min_count) whose count is <= max_count and whose class bit 1u << (5 * left + right) is
+ * set in class_mask; *removed (may be NULL) receives how many.  Adjacency is taken once, over the index as it stands when the
+ * call begins, and is not iterated: two dead ends that touch each other are both judged by the graph before the call.  Entries
+ * below min_count are never removed here (that is brisk_hip_prune's job).  Afterwards everything brisk_hip_prune promises
+ * holds: storage order of the survivors, stats including nb_buckets, checksum, lookups, later inserts (a removed k-mer starts
+ * at 1 again), no memory returned.  EINVAL if min_count > max_count or class_mask has a bit above 24. */
+int brisk_hip_prune_degrees(brisk_hip_index *h, uint32_t min_count, uint32_t max_count, uint32_t class_mask, uint64_t *removed);
+/* Device time in ms of the last of the three calls above, while brisk_hip_profile_enable is on (zeros otherwise):
+ * out[0] the neighbour-read kernel, out[1] the lookups, out[2] the fold (and the histogram), summed over the call's rounds. */
+int brisk_hip_graph_phase_ms(brisk_hip_index *h, double out[3]);
 
 /* ---- set operations: merge, intersect, subtract, compare (no reference counterpart) ---- */
 /* Two indexes created with the same (k, m, b) and the same partition layout route an identity to the same partition and store it
